@@ -19,9 +19,16 @@ The timed model is built with pipeline=True (tf_raft_amd/model.py "pipelined for
 loop runs on lane n % 3 (a stream of its own) while the next calls' encoders, volume builds and loops proceed -- the timed region is
 still K complete model([a, b]) calls between two device synchronisations.  RAFT_PIPELINE=0 times the serial schedule.
 
-Rank 0 prints ONE JSON line; besides the contract fields it carries
-  schedule            what was timed: loops in flight, launch-shape hint, the same K steps on the serial schedule, the latency of ONE call
-                      consumed at once on both schedules
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs DIR) and prints the line: the contract fields,
+`config` and `schedule` (what was timed: loops in flight, launch-shape hint).  Everything else below is measured only with --full.
+
+--dump-outputs DIR  what the LAST timed step computed (rank 0's model([a, b]) call), float32, after the timed region:
+  flow_final.npy               flow_predictions[-1] of the first 16 pairs of the batch, (min(B, 16), H, W, 2)
+  flow_predictions_sample.npy  all 24 predictions of those pairs at 4096 pixels drawn once with seed 0, (24, min(B, 16), 4096, 2)
+  The inputs and weights are seeded, so two builds run with the same arguments can be compared file for file.
+
+Rank 0 prints ONE JSON line; with --full, besides the contract fields it carries
+  schedule            the same K steps on the serial schedule, the latency of ONE call consumed at once on both schedules
   final_iter_epe      the EPE half of BASELINE's metric ON THE TIMED CONFIGURATION: max-abs EPE of flow_predictions[-1] (element 0 of the
                       timed batch, Keras-default weights) against the CPU oracle; an untrained RAFT is ill conditioned there, so
                       final_iter_epe_within_tolerance is false and final_iter_epe_default_horizon says how far 1e-3 holds.
@@ -44,7 +51,7 @@ Rank 0 prints ONE JSON line; besides the contract fields it carries
                       scaled per pair to this run's batch; `evidence` says whether those passes were taken on the running sources
   stage_ms            per-kernel average milliseconds per launch (HIP events, instrumented replay)
   cpu_baseline        the CPU oracle (reference restatement, torch-CPU) timed on this box's host cores, thread count probed
-  preflight           (N > 1) announced on stderr before timing: ranks seen, devices, libraft_hip.so mapped / not rebuilt per rank
+  preflight           (N > 1, plain runs too) announced on stderr before timing: ranks seen, devices, libraft_hip.so mapped / not rebuilt per rank
 """
 import argparse
 import contextlib
@@ -317,6 +324,23 @@ def best_oracle_threads(run, candidates):
     return best
 
 
+DUMP_PAIRS, DUMP_PIXELS = 16, 4096      # --dump-outputs stays under 64 MB at any batch: 29.4 + 12.6 MB at 16 pairs
+
+
+def dump_outputs(out_dir, preds):
+    """--dump-outputs: flow_predictions (a list of (B, H, W, 2) device tensors) of the last timed step -> out_dir as float32:
+    the final prediction of the first DUMP_PAIRS pairs, and every prediction of those pairs at DUMP_PIXELS pixels drawn once
+    with a fixed seed (the same pixels in every run)."""
+    from tf_raft_amd import _dev
+    os.makedirs(out_dir, exist_ok=True)
+    preds = [p.as_subclass(torch.Tensor)[:DUMP_PAIRS] for p in _dev.join(preds)]
+    n, h, w, _ = preds[-1].shape
+    pix = torch.from_numpy(np.sort(np.random.default_rng(0).choice(h * w, DUMP_PIXELS, replace=False))).to(preds[-1].device)
+    sample = torch.stack([p.reshape(n, h * w, 2)[:, pix] for p in preds])
+    np.save(os.path.join(out_dir, 'flow_final.npy'), preds[-1].float().cpu().numpy())
+    np.save(os.path.join(out_dir, 'flow_predictions_sample.npy'), sample.float().cpu().numpy())
+
+
 def preflight(dist, world, rank, local_rank, device, backend):
     """Before anything is timed with N > 1 ranks: every rank reports its device, whether libraft_hip.so is mapped into the
     process and whether this process had to COMPILE it (a box that received the prebuilt .so must not), through an
@@ -466,6 +490,10 @@ def train_bench(args, world, rank, device, backend):
         res = model.train_step(data)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:          # what train_step returns: the running means of its metrics
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, v in res.items():
+            np.save(os.path.join(args.dump_outputs, f'train_{k}.npy'), np.asarray(float(v), dtype=np.float64))
     seen = 1
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
@@ -505,7 +533,14 @@ def main():
     ap.add_argument('--tape', default='f32', choices=['f32', 'bf16'], help='--train: storage type of the activation tape')
     ap.add_argument('--cpu-runs', type=int, default=4, help='minimum number of timed CPU-oracle forwards (one per weight regime first)')
     ap.add_argument('--no-parity', action='store_true', help='skip the per-regime timing + EPE legs (profiling runs)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, measure everything else: regimes + EPE against the CPU oracle, serial schedule, other '
+                         'batches, per-kernel rooflines, host-fed rates, CPU baseline (N > 1: the collective alone, one-GPU rate)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (float32, < 64 MB)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher -- one rank per GPU under torch.distributed.run on
@@ -564,8 +599,10 @@ def main():
     # preds[-1] joins the touching stream with the loop, so it is touched on `comm`, and RCCL orders its own stream behind `comm`.
     comm = torch.cuda.Stream(device=device) if (world > 1 and device.type == 'cuda') else None
 
-    def step(a=img1, b=img2):
+    def step(a=img1, b=img2, keep=None):
         preds = model([a, b], training=False)
+        if keep is not None:
+            keep[:] = preds
         if world > 1:
             with (torch.cuda.stream(comm) if comm is not None else contextlib.nullcontext()):
                 last = preds[-1].as_subclass(torch.Tensor)
@@ -595,11 +632,15 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
+    last_preds = []       # the last timed step's predictions, for --dump-outputs (no earlier step's outputs are held)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        step(keep=last_preds if i == args.steps - 1 else None)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_preds)
+    del last_preds
     rank_elapsed = [elapsed]
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
@@ -614,7 +655,7 @@ def main():
     # ---------------- the same step in every weight regime: throughput must not depend on the weights (no data-dependent work
     # is skipped when the flow runs off the map), and element 0's 24 predictions are kept for the EPE half of the metric
     regime_weights, regime_pred0, regime_rate, regime_rounds = {}, {}, {}, {}
-    if world == 1 and not args.no_parity:
+    if args.full and world == 1 and not args.no_parity:
         models = {}
         for reg in REGIMES:
             regime_weights[reg] = wts if reg == 'default' else wm.condition_weights('raft', wts, reg)
@@ -638,7 +679,7 @@ def main():
             regime_pred0[reg] = [p_.as_subclass(torch.Tensor)[:1].cpu().numpy() for p_ in preds]
             del preds
         del models
-    elif world > 1 and rank == 0 and not args.no_parity:
+    elif args.full and world > 1 and rank == 0 and not args.no_parity:
         # N > 1: rank 0 alone evaluates the two provable regimes on ITS shard's element 0 (the other ranks wait at the closing
         # barrier); the CPU oracle runs below, untimed -- cpu_baseline is an N = 1 figure
         for reg in ('conditioned', 'jump0'):
@@ -671,7 +712,7 @@ def main():
                 'inside it.  Consecutive calls are independent; call n runs its loop on lane n % loops_in_flight while the next calls\' '
                 'encoders, volume builds and loops proceed (tf_raft_amd/model.py "pipelined forward"); per-call results equal the serial '
                 'schedule\'s bit for bit under the same launch-shape hint (tests/test_gpu_model.py::test_pipelined_calls_are_bitwise_the_serial_calls)'}
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         # the same K steps on the serial schedule (RAFT(pipeline=False): the default of a model object, what a caller that consumes
         # every result at once gets), and the latency of ONE call whose result is consumed at once, on both schedules
         serial_model = tf_raft_amd.RAFT(iters_pred=ITERS, weights=wts, pipeline=False)
@@ -704,6 +745,9 @@ def main():
         result['preflight'] = pre                        # announced on stderr BEFORE the timed region (devices, .so mapped / not rebuilt)
         result['scaling_curve'] = 'none measured by this repository: 8-GPU runs are the driver\'s (DESIGN.md section 6)'
         result['backend'] = 'RCCL ' + '.'.join(str(v) for v in torch.cuda.nccl.version()) if backend == 'nccl' else backend
+        result['rank_step_ms'] = {'min': round(1e3 * min(rank_elapsed) / args.steps, 3), 'max': round(1e3 * max(rank_elapsed) / args.steps, 3),
+                                  'per_rank': [round(1e3 * e / args.steps, 3) for e in rank_elapsed]}
+    if args.full and world > 1:
         # the collective alone: one all-gather of flow_predictions[-1] (every rank takes part), barrier-to-sync, median of 5
         last = model([img1, img2], training=False)[-1].as_subclass(torch.Tensor)
         torch.cuda.synchronize()
@@ -735,10 +779,8 @@ def main():
             result['scaling_efficiency'] = round(value / world / result['one_gpu_same_shape_pairs_per_s'], 4)
             result['scaling_efficiency_basis'] = ('whole-job pairs/s / n_gpus / one_gpu_same_shape_pairs_per_s (rank 0 alone, the same '
                                                   f'{B} pairs per step, no collective, measured in this job after the timed region)')
-        result['rank_step_ms'] = {'min': round(1e3 * min(rank_elapsed) / args.steps, 3), 'max': round(1e3 * max(rank_elapsed) / args.steps, 3),
-                                  'per_rank': [round(1e3 * e / args.steps, 3) for e in rank_elapsed]}
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # ---------------- informational: RAFT.predict_step (flow_predictions[-1] only: mask head + upsampling in the
         # last iteration only, reference model.py:160-166) -- NOT the headline, which produces all 24 predictions
         for _ in range(2):
@@ -776,7 +818,7 @@ def main():
             result['pairs_per_s_at_8_pairs_per_gpu'] = round(8 * n / (time.perf_counter() - t0), 3)
             del i8a, i8b
 
-    if rank == 0:
+    if args.full and rank == 0:
         # ---------------- instrumented replay: per-kernel HIP-event timing on the launch stream, with the launch shapes the
         # product's loops run (the thread-local hint of the multi-lane schedule; reset before the line is printed)
         _dev.lib().raft_set_thread_concurrency(conc)
@@ -813,7 +855,7 @@ def main():
         per_launch_ms = acc / (reps * ITERS)
         return per_launch_ms
 
-    if rank == 0:
+    if args.full and rank == 0:
         # per-kernel numbers come from the TWO-kernel path (stand-alone lookup, stand-alone convc1: the kernels the
         # roofline entries name); the product loop runs them fused (RAFT_LOOKUP_FUSED, default on), timed separately
         _ffi.set_option('RAFT_LOOKUP_FUSED', 0)
@@ -1180,17 +1222,12 @@ def main():
             result['regime_timing'] = (f'{len(next(iter(regime_rounds.values())))} interleaved rounds of {args.steps} steps per regime in this '
                                        'process (same inputs, same launches; only the weights differ), median per regime; `value` is the '
                                        'separately timed headline on the default weights')
+    if rank == 0:
         front = ['metric', 'value', 'unit', 'final_iter_epe', 'final_iter_epe_regime', 'final_iter_epe_within_tolerance',
                  'final_iter_epe_default_horizon', 'final_iter_epe_conditioned', 'final_iter_epe_conditioned_regimes',
                  'final_iter_epe_conditioned_within_tolerance', 'final_iter_epe_by_regime', 'pairs_per_s_by_regime', 'regime_spread_frac']
         result = {**{k: result[k] for k in front if k in result}, **{k: v for k, v in result.items() if k not in front}}
         print(json.dumps(result), flush=True)
-        try:
-            os.makedirs(os.path.join(ROOT, 'gpurun_out'), exist_ok=True)
-            with open(os.path.join(ROOT, 'gpurun_out', f'bench_n{world}.json'), 'w') as f:
-                json.dump(result, f, indent=1)
-        except OSError:
-            pass
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -156,3 +156,23 @@ def test_f4x4_launch_shape_follows_the_library_rule_and_its_hints():
     finally:
         for k in names:
             _ffi.set_option(k, None)
+
+
+def test_dump_outputs_writes_the_last_step_within_64_mb(tmp_path):
+    """--dump-outputs: float32 arrays of what the timed call returned, the same sampled pixels in every run, under 64 MB at any batch."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(0)
+    preds = [torch.rand((4, bench.H, bench.W, 2), generator=g) for _ in range(bench.ITERS)]
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), preds)
+    final, sample = np.load(tmp_path / 'a' / 'flow_final.npy'), np.load(tmp_path / 'a' / 'flow_predictions_sample.npy')
+    assert final.dtype == np.float32 and sample.dtype == np.float32
+    np.testing.assert_array_equal(final, preds[-1].numpy())
+    assert sample.shape == (bench.ITERS, 4, bench.DUMP_PIXELS, 2)
+    np.testing.assert_array_equal(sample, np.load(tmp_path / 'b' / 'flow_predictions_sample.npy'))
+    flat = preds[5].reshape(4, -1, 2).numpy()
+    assert all((flat[1] == v).all(-1).any() for v in sample[5, 1, :16])           # sampled pixels of the right prediction and pair
+    big = [torch.zeros((40, bench.H, bench.W, 2))] * bench.ITERS
+    bench.dump_outputs(str(tmp_path / 'c'), big)
+    assert sum(f.stat().st_size for f in (tmp_path / 'c').iterdir()) < 64e6

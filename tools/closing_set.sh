@@ -2,7 +2,7 @@
 # Closing set of a state of the tree (GPU box, repo root).  Everything bench.py's evidence fields point to is regenerated here
 # from the library that is loaded in the same call:
 #   <tag>_pytest_gpu.log, <tag>_smoke.log, <tag>_parity_tests.log   the GPU suite, smoke(), the model parity tests with their errors (skipped with SKIP_TESTS=1)
-#   <tag>_bench_b4.log                              the default bench line (BASELINE configs[1])
+#   <tag>_bench_b4.log                              the bench line with every --full field (BASELINE configs[1])
 #   <tag>_bench_b4_rocprofv3_kernel_stats.csv       rocprofv3 --kernel-trace --stats of the same command (product loop)
 #   <tag>_single_stream_b{4,8}_rocprofv3_kernel_stats.csv + kernel_durations.json   single-stream loop, per-stage durations
 #   <tag>_pmc_per_kernel.csv + pmc_traffic.json     FETCH_SIZE / WRITE_SIZE passes at 8 pairs      (skipped with SKIP_PMC=1)
@@ -53,7 +53,7 @@ if [ -n "$t" ]; then
   cp $(ls $out/${tag}_conc/*kernel_stats.csv | head -1) $out/${tag}_concurrent_convc2_rocprofv3_kernel_stats.csv
 fi
 rm -rf $out/${tag}_conc
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/${tag}_bench_b4.log 2>&1
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/${tag}_bench_b4.log 2>&1
 # round 6: the schedules of consecutive calls side by side, ONE PROCESS PER SETTING (streams map onto hardware queues in creation
 # order: several settings in one process disturb each other) -- serial, one lane on three streams (round 5), 2 / 3 / 4 single-stream lanes
 for s in serial 1:1 2:0 3:0 4:0 serial 3:0; do
@@ -76,7 +76,7 @@ t=$(ls $out/${tag}_lt/*kernel_trace.csv 2>/dev/null | head -1)
 rm -rf $out/${tag}_lt
 [ -z "${SKIP_PMC:-}" ] && bash tools/instruction_mix.sh $tag 4 > /dev/null 2>&1 && rm -rf $out/${tag}_mix
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $out/${tag}_prof -o bench -- python $root/bench.py --gpus 1 --steps 20 --warmup 5 > $out/${tag}_bench_b4_under_rocprof.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $out/${tag}_prof -o bench -- python $root/bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/${tag}_bench_b4_under_rocprof.log 2>&1
 f=$(ls $out/${tag}_prof/*kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && cp "$f" $out/${tag}_bench_b4_rocprofv3_kernel_stats.csv
 rm -rf $out/${tag}_prof
 timeout 200 rocprofv3 --kernel-trace -f csv -d $out/${tag}_tl -o tl -- python $root/tools/graph_probe.py 4 3 > $out/${tag}_tl.log 2>&1

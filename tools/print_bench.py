@@ -1,4 +1,4 @@
-"""Print the headline numbers of a bench.py log.  usage: python tools/print_bench.py <log>"""
+"""Print the headline numbers of a `bench.py --full` log.  usage: python tools/print_bench.py <log>"""
 import json
 import sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])
