@@ -12,8 +12,8 @@
  *   - all tensors are fp32, NHWC (channels contiguous), exactly the reference's layouts;
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream); calls only
  *     enqueue work, they never synchronise and never allocate.  Two documented exceptions:
- *     raft_loop_ctx_create / _destroy (the caller-owned context of the three-stream loops: 4 HIP
- *     events + a cache of instantiated hipGraphs) and the bench-only raft_iterate_basic_timed_f32;
+ *     raft_loop_ctx_create / _destroy, which create and destroy the four cross-stream HIP events of
+ *     the three-stream loops, and the bench-only raft_iterate_basic_timed_f32, which synchronises;
  *   - return value: RAFT_OK (0), a negative RAFT_E_* argument error, or a positive
  *     hipError_t from the launch; no exception or abort crosses the ABI;
  *   - the library keeps no per-call state and is re-entrant (ordering only through `stream`).  Its
@@ -57,8 +57,6 @@
  *                            summation order, corr.py:106-114).  1 needs even map sizes and an even number of 4x8 tiles per
  *                            row and column (448x512 and 1024x1024 frames have them), else 0 is used         (default 1)
  *   RAFT_ONDEMAND_BLOCK 0/1  on-demand lookup: wave per query / 4x8 query blocks on MFMA         (default 1)
- *   RAFT_LOOP_GRAPH     0/1  three-stream loops replayed as one hipGraph launch                  (default 0: measured
- *                       slower than stream launches on ROCm 7.2 at every batch size)
  */
 #ifndef RAFT_HIP_H_
 #define RAFT_HIP_H_
@@ -70,7 +68,7 @@
 extern "C" {
 #endif
 
-#define RAFT_HIP_VERSION 219          /* 0.2.0: ABI stamp, checked by the Python binding -- bump on ANY struct / signature change */
+#define RAFT_HIP_VERSION 220          /* 0.2.0: ABI stamp, checked by the Python binding -- bump on ANY struct / signature change */
 #define RAFT_MAX_LEVELS 4
 
 enum {
@@ -330,10 +328,10 @@ int raft_iterate_basic_f32(const raft_basic_update_weights *wts, const float *py
                            const int64_t *level_offsets, int B, int h, int w, int iters,
                            const raft_state *st, float *flow_up, void *stream);
 
-/* Caller-owned context of the three-stream loops below: the four cross-stream events of the schedule and a cache of up
- * to four instantiated hipGraphs of whole prediction loops.  Create once per model / thread on the device the loops run
- * on (the only entry point that allocates), pass to every raft_iterate_basic_{overlap,ondemand,final}_f32 call, destroy
- * after the last loop has drained.  Not thread-safe: one context per launching thread. */
+/* Caller-owned context of the three-stream loops below: the four cross-stream events of the schedule.  Create once per
+ * model / thread on the device the loops run on (the only entry point that allocates), pass to every
+ * raft_iterate_basic_{overlap,ondemand,final}_f32 call, destroy after the last loop has drained.  Not thread-safe: one
+ * context per launching thread. */
 typedef struct raft_loop_ctx raft_loop_ctx;
 int raft_loop_ctx_create(raft_loop_ctx **ctx);
 int raft_loop_ctx_destroy(raft_loop_ctx *ctx);
@@ -345,12 +343,7 @@ int raft_loop_ctx_destroy(raft_loop_ctx *ctx);
  * aux0 == aux1 == stream selects the SINGLE-STREAM schedule (the launches of raft_iterate_basic_f32, no events) for
  * this and the two entry points below: what a caller that keeps several loops in flight on streams of their own
  * (tf_raft_amd/model.py, lanes of the pipelined forward) runs on each.  Any other coincidence of the three streams is
- * RAFT_E_UNSUPPORTED.
- * With RAFT_LOOP_GRAPH on (off by default) the first call with a given set of arguments (pointers, sizes,
- * streams) captures these launches into a hipGraph kept in `ctx`; later calls with the same arguments replay it with ONE
- * hipGraphLaunch on `stream` -- the reference's canonical (1,448,512,3) call is bound by the host's ~350 launches + ~100
- * event operations otherwise.  A non-NULL `stream` is required for that (the legacy default stream cannot be captured;
- * the plain launches are used on it). */
+ * RAFT_E_UNSUPPORTED. */
 int raft_iterate_basic_overlap_f32(const raft_basic_update_weights *wts, const float *pyr,
                                    const int64_t *level_offsets, int B, int h, int w, int iters,
                                    const raft_state *st, float *flow_up, void *stream, void *aux0, void *aux1,

@@ -171,6 +171,7 @@ def test_shim_import_path_and_bad_inputs():
     from tf_raft.model import RAFT
     from tf_raft.layers.corr import CorrBlock, bilinear_sampler, coords_grid, upflow8  # noqa: F401
     model = RAFT(iters_pred=1)
+    assert RAFT(iters_pred=1, name='raft_named').name == 'raft_named'     # reference model.py:11-12: **kwargs reach keras.Model(name=)
     i1, i2 = _images(0, 1, 64, 64)
     with pytest.raises(ValueError):
         model([i1[:, :60], i2[:, :60]])                      # H not a multiple of 8
@@ -761,6 +762,41 @@ def test_pipelined_calls_are_bitwise_the_serial_calls(variant, kw, shape, iters)
         np.testing.assert_array_equal(other.cpu().numpy(), serial.predict_step(small_in).cpu().numpy())
 
 
+def test_pipelined_serial_and_predict_calls_interleave_on_one_model():
+    """One pipelined model driven three ways in turn: pipelined calls (lane n % lanes, single-stream loops), serial
+    ``predict_step(_pipelined=False)`` calls (lane 0, three-stream loop, no launch-shape hint) and ``predict()``.  Whatever
+    one kind of call chooses must not leak into the next: each result is bitwise the same call on a fresh model built for
+    that one schedule."""
+    import tf_raft_amd
+    from tf_raft_amd import weights as wm
+    from tf_raft_amd.model import DEFAULT_LANES
+    wts = wm.init_weights('raft', seed=13, perturb=True)
+    iters = 6
+    model = tf_raft_amd.RAFT(weights=wts, iters_pred=iters, pipeline=True)
+    assert model.lanes == DEFAULT_LANES
+    overlap = model.overlap
+    wide = tf_raft_amd.RAFT(weights=wts, iters_pred=iters, pipeline=False, loop_concurrency=DEFAULT_LANES)
+    serial = tf_raft_amd.RAFT(weights=wts, iters_pred=iters, pipeline=False)
+    pairs = [tuple(torch.as_tensor(a).cuda() for a in _images(60 + k, 2, 128, 192)) for k in range(6)]
+    x1, x2 = _images(70, 5, 64, 96)
+    piped, serial_got, predicted = [], [], []
+    for k, (a, b) in enumerate(pairs):
+        piped.append(model([a, b]))                                      # left in flight until the end
+        if k % 2:
+            serial_got.append(_np(model.predict_step((a, b), _pipelined=False)))
+        if k % 3 == 1:
+            predicted.append(model.predict([x1, x2], batch_size=2))
+    for k, (a, b) in enumerate(pairs):
+        for g, w_ in zip(piped[k], wide([a, b])):
+            np.testing.assert_array_equal(_np(g), _np(w_))
+    for got, (a, b) in zip(serial_got, pairs[1::2]):
+        np.testing.assert_array_equal(got, _np(serial.predict_step((a, b))))
+    want = np.concatenate([_np(wide.predict_step((x1[i:i + 2], x2[i:i + 2]))) for i in range(0, 5, 2)], axis=0)
+    for got in predicted:
+        np.testing.assert_array_equal(got, want)
+    assert model.overlap == overlap and model.pipeline               # what the calls chose did not stick to the model
+
+
 def test_weights_replaced_while_a_pipelined_call_is_in_flight():
     """set_weights frees the packed device blobs of the old weights; a loop still in flight on the loop stream must be waited for
     first (stream order does not cover it any more).  The in-flight call keeps the OLD weights' result, the next call has the new."""
@@ -843,38 +879,6 @@ def test_rotating_buffer_loop_is_bitwise_the_single_stream_loop(shape, iters, ra
             for a, b_ in zip(got, ref):
                 np.testing.assert_array_equal(a, b_)
     report(f'rotating-buffer loop {shape} x{iters}', predictions_compared=2 * 4 * iters)
-
-
-def test_graph_replayed_loop_is_bitwise_the_launched_loop(raft_opt):
-    """RAFT_LOOP_GRAPH (include/raft_hip.h): the three-stream loop captured into a hipGraph and replayed with one launch
-    must reproduce the host-launched loop bit for bit -- first call (capture + launch), repeated calls (cached graph),
-    another input of the same shape (same graph, new data), predict_step (its own graph), and the reference's canonical
-    single-pair shape class (B = 1)."""
-    import tf_raft_amd
-    from tf_raft_amd import weights as wm
-    wts = wm.init_weights('raft', seed=2)
-    model = tf_raft_amd.RAFT(weights=wts, iters_pred=6, overlap=True, name='raft_graph')
-    assert model.name == 'raft_graph'                       # reference model.py:11-12: **kwargs reach keras.Model(name=)
-    pairs = [_images(4, 1, 128, 192), _images(5, 1, 128, 192)]
-    raft_opt.set('RAFT_LOOP_GRAPH', '0')
-    ref = [[_np(p) for p in model([a, b])] for a, b in pairs]
-    ref_last = [_np(model.predict_step((a, b))) for a, b in pairs]
-    raft_opt.set('RAFT_LOOP_GRAPH', '1')
-    for _ in range(3):
-        for k, (a, b) in enumerate(pairs):
-            got = [_np(p) for p in model([a, b])]
-            for x, y in zip(got, ref[k]):
-                assert np.array_equal(x, y)
-            assert np.array_equal(_np(model.predict_step((a, b))), ref_last[k])
-    # a switch flipped between calls must not replay a stale graph (the key carries the option generation)
-    raft_opt.set('RAFT_GRU_WINO4', '0')
-    raft_opt.set('RAFT_GRU_WINO', '0')
-    direct = [_np(p) for p in model(list(pairs[0]))]
-    raft_opt.set('RAFT_LOOP_GRAPH', '0')
-    direct_ref = [_np(p) for p in model(list(pairs[0]))]
-    for x, y in zip(direct, direct_ref):
-        assert np.array_equal(x, y)
-    assert not np.array_equal(direct[-1], ref[0][-1])       # the direct GRU kernels round differently from F(4,5)
 
 
 def test_fused_lookup_loop_matches_two_kernel_loop(raft_opt):

@@ -313,6 +313,23 @@ def test_tuning_switches_are_a_table_not_getenv():
             assert 'getenv' not in re.sub(r'//.*', '', f.read()), f'{name} reads the environment on a launch path'
 
 
+def test_switch_table_of_the_header_is_the_library_table():
+    """Every switch the header documents is one raft_get_option knows, and every name of the library's table is documented;
+    a removed switch is rejected like a name that never existed."""
+    with open(os.path.join(ROOT, 'include', 'raft_hip.h')) as f:
+        header = f.read()
+    documented = re.findall(r'^ \*   (RAFT_[A-Z0-9_]+)\s', header[:header.index('*/')], re.M)
+    with open(os.path.join(ROOT, 'tf_raft_amd', 'csrc', 'host_util.hip')) as f:
+        src = f.read()
+    table = re.findall(r'"(RAFT_[A-Z0-9_]+)"', src[src.index('kOptNames['):src.index('};', src.index('kOptNames['))])
+    assert sorted(documented) == sorted(table + ['RAFT_CONV_TILE'])
+    for name in documented:
+        _ffi.get_option(name)
+    for name in ('RAFT_LOOP_GRAPH', 'RAFT_NO_SUCH_SWITCH'):
+        with pytest.raises(ValueError):
+            _ffi.get_option(name)
+
+
 @pytest.mark.parametrize('path', ['tf_raft.model', 'tf_raft.losses', 'tf_raft.losses.losses', 'tf_raft.layers.corr',
                                   'tf_raft.layers.update', 'tf_raft.layers.extractor', 'tf_raft.training'])
 def test_every_reference_import_path_resolves(path):

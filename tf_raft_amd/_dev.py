@@ -169,22 +169,14 @@ def stream_ptr() -> int:
 _SIDE_STREAMS = {}
 
 
-# Priority of EVERY side stream of the package (one pool: streams of two priorities come from two pools whose members collide on the
-# hardware queues, see model.py _loop_priority).  RAFT_STREAM_PRIORITY=-1: all of them high -- i.e. above the caller's stream.
-import os as _os
-STREAM_PRIORITY = int(_os.environ.get('RAFT_STREAM_PRIORITY', '0'))
-
-
-def side_stream(device, role: str, priority: int = None) -> 'torch.cuda.Stream':
+def side_stream(device, role: str) -> 'torch.cuda.Stream':
     """The process-wide side stream of ``role`` ('flow', 'mask', 'encoder', 'loop'; lane k > 0 of the pipelined forward:
-    'loop1', 'flow1', ...) and ``priority`` on ``device``.  Streams of different priorities are different streams (a
-    stream's priority is fixed when it is created)."""
+    'loop1', 'flow1', ...) on ``device``."""
     device = torch.device(device)
-    priority = STREAM_PRIORITY if priority is None else priority
-    key = (device.index if device.index is not None else torch.cuda.current_device(), role, int(priority))
+    key = (device.index if device.index is not None else torch.cuda.current_device(), role)
     s = _SIDE_STREAMS.get(key)
     if s is None:
-        s = _SIDE_STREAMS[key] = torch.cuda.Stream(device=device, priority=priority)
+        s = _SIDE_STREAMS[key] = torch.cuda.Stream(device=device)
     return s
 
 

@@ -67,7 +67,7 @@ __host__ __device__ inline void raft_untiled_yx(int n, int tiles_x, int *y, int 
 enum RaftOptionId {
     RAFT_OPT_CONV_WINO, RAFT_OPT_SMALL_WINO, RAFT_OPT_GRU_WINO, RAFT_OPT_GRU_WINO4, RAFT_OPT_WINO_TNW, RAFT_OPT_WINO_SB,
     RAFT_OPT_WINO_CK, RAFT_OPT_WINO1D_TM,
-    RAFT_OPT_LOOKUP_FUSED, RAFT_OPT_ONDEMAND_BLOCK, RAFT_OPT_ENC_WINO, RAFT_OPT_LOOP_GRAPH,
+    RAFT_OPT_LOOKUP_FUSED, RAFT_OPT_ONDEMAND_BLOCK, RAFT_OPT_ENC_WINO,
     RAFT_OPT_WINO_KS, RAFT_OPT_CONV_WINO4, RAFT_OPT_WINO4_KS, RAFT_OPT_MASK_FUSED, RAFT_OPT_ENC_WINO4, RAFT_OPT_CONVC2_KS, RAFT_OPT_CONVF2_KS,
     RAFT_OPT_EVENT_FENCE, RAFT_OPT_CORR_XCD, RAFT_OPT_CORR_POOL,
     RAFT_OPT_COUNT
@@ -77,7 +77,6 @@ int raft_opt(int id, int dflt);
 // with the calling thread's launches (>= 1).  The launchers' "does this grid fill the chip?" rules count a grid n times.
 int raft_concurrency();
 bool raft_opt_is_set(int id);
-int raft_opt_generation();   // bumped by every raft_set_option call
 // RAFT_CONV_TILE ("<code>" or "<npad>:<taps>:<code>,..."): the tile code forced for a convolution, or -1
 int raft_opt_conv_tile(int npad, int taps, bool (*valid)(int code, int npad));
 

@@ -818,27 +818,9 @@ static int loop_lookup(const LookupSource &src, const raft_state *st, int B, int
 }
 
 // Caller-owned loop context (include/raft_hip.h): the four cross-stream events of the three-stream schedule, created
-// ONCE by raft_loop_ctx_create (the only allocating entry point), plus a small cache of instantiated hipGraphs of whole
-// prediction loops keyed by every argument of the call.
-struct LoopKey {
-    raft_basic_update_weights wts;
-    LookupSource src;
-    raft_state st;
-    int64_t offs[RAFT_MAX_LEVELS + 1];   // VALUES of level_offsets (the pointer is host memory of the caller)
-    const float *flow_up;
-    void *stream, *aux0, *aux1;
-    int B, h, w, iters, final_only, opt_stamp;
-};
-struct LoopGraph {
-    LoopKey key;
-    hipGraphExec_t exec;
-    uint64_t last_use;
-};
+// ONCE by raft_loop_ctx_create (the only allocating entry point).
 struct raft_loop_ctx {
     hipEvent_t ev[4];
-    LoopGraph graphs[4];
-    int n_graphs;
-    uint64_t clock;
     int device;
 };
 
@@ -871,7 +853,6 @@ extern "C" int raft_loop_ctx_create(raft_loop_ctx **out) {
 
 extern "C" int raft_loop_ctx_destroy(raft_loop_ctx *c) {
     if (!c) return RAFT_OK;
-    for (int k = 0; k < c->n_graphs; ++k) (void)hipGraphExecDestroy(c->graphs[k].exec);
     for (int k = 0; k < 4; ++k) (void)hipEventDestroy(c->ev[k]);
     free(c);
     return RAFT_OK;
@@ -917,7 +898,7 @@ extern "C" int raft_iterate_basic_final_f32(const raft_basic_update_weights *wts
     return iterate_basic_overlap_impl(wts, src, B, h, w, iters, st, flow_up_last, stream, aux0, aux1, ctx, true);
 }
 
-// Enqueue the whole loop on `stream` + the two side streams (also the body of a stream capture).
+// Enqueue the whole loop on `stream` + the two side streams.
 static int enqueue_loop(const raft_basic_update_weights *wts, const LookupSource &src, int B, int h, int w, int iters,
                         const raft_state *st, float *flow_up, void *stream, void *aux0, void *aux1, raft_loop_ctx *ctx,
                         bool final_only) {
@@ -976,27 +957,6 @@ static int enqueue_loop(const raft_basic_update_weights *wts, const LookupSource
     return rc;
 }
 
-// Padding-free copy of the weight table (it is an array of raft_conv_weights): the key is compared with memcmp.
-static void copy_weights_clean(raft_basic_update_weights *dst, const raft_basic_update_weights *src) {
-    static_assert(sizeof(raft_basic_update_weights) % sizeof(raft_conv_weights) == 0, "weight table = array of raft_conv_weights");
-    memset(dst, 0, sizeof(*dst));
-    const raft_conv_weights *sw = (const raft_conv_weights *)src;
-    raft_conv_weights *dw = (raft_conv_weights *)dst;
-    for (size_t i = 0; i < sizeof(*src) / sizeof(raft_conv_weights); ++i) {
-        dw[i].wp = sw[i].wp;
-        dw[i].bias = sw[i].bias;
-        dw[i].npad = sw[i].npad;
-    }
-}
-
-// RAFT_LOOP_GRAPH (raft_set_option): 1 = replay the loop as ONE hipGraph launch (captured from the same enqueue code the
-// first time a given set of arguments is seen, then cached in the caller's raft_loop_ctx), 0 = enqueue the ~350 kernels
-// and ~100 event operations from the host every call.  Default 0: measured on MI355X / ROCm 7.2 the replay is SLOWER
-// than the stream launches at every batch size (B = 1: 8.44 vs 7.94 ms, B = 4: 15.9 vs 15.4 ms,
-// profiles/r05a_batch_sweep.txt) -- the host is not the limiter of the small-batch loop, the dependent chain of short
-// kernels on the GPU is (docs/NOTEBOOK.md section 4.2).  Kept as a switch: bit-identical results, one launch per forward.
-static bool use_loop_graph(int, int, int) { return raft_opt(RAFT_OPT_LOOP_GRAPH, 0) != 0; }
-
 static int iterate_basic_overlap_impl(const raft_basic_update_weights *wts, const LookupSource &src, int B, int h, int w,
                                       int iters, const raft_state *st, float *flow_up, void *stream, void *aux0, void *aux1,
                                       raft_loop_ctx *ctx, bool final_only) {
@@ -1009,63 +969,12 @@ static int iterate_basic_overlap_impl(const raft_basic_update_weights *wts, cons
     RAFT_REQUIRE(B > 0 && h > 0 && w > 0 && iters > 0, RAFT_E_SHAPE);
     // three distinct streams, or all three the same one (the single-stream schedule)
     RAFT_REQUIRE((aux0 != stream && aux1 != stream && aux0 != aux1) || (aux0 == stream && aux1 == stream), RAFT_E_UNSUPPORTED);
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if (!use_loop_graph(B, h, w) || s == nullptr) {   // the legacy NULL stream cannot be captured
-        rc = enqueue_loop(wts, src, B, h, w, iters, st, flow_up, stream, aux0, aux1, ctx, final_only);
-        if (rc != RAFT_OK) {   // never leave side streams running behind an error return
-            (void)hipStreamSynchronize((hipStream_t)aux0);
-            (void)hipStreamSynchronize((hipStream_t)aux1);
-        }
-        return rc;
+    const int rc = enqueue_loop(wts, src, B, h, w, iters, st, flow_up, stream, aux0, aux1, ctx, final_only);
+    if (rc != RAFT_OK) {   // never leave side streams running behind an error return
+        (void)hipStreamSynchronize((hipStream_t)aux0);
+        (void)hipStreamSynchronize((hipStream_t)aux1);
     }
-    LoopKey key;
-    memset(&key, 0, sizeof(key));   // padding bytes take part in the memcmp below
-    copy_weights_clean(&key.wts, wts);
-    key.src.pyr = src.pyr;
-    key.src.fmap1 = src.fmap1;
-    key.src.fmap2_pyr = src.fmap2_pyr;
-    key.src.C = src.C;
-    if (src.level_offsets)
-        for (int l = 0; l <= RAFT_MAX_LEVELS; ++l) key.offs[l] = src.level_offsets[l];
-    key.st = *st;   // nine pointers, no padding
-    key.flow_up = flow_up;
-    key.stream = stream;
-    key.aux0 = aux0;
-    key.aux1 = aux1;
-    key.B = B; key.h = h; key.w = w; key.iters = iters;
-    key.final_only = final_only ? 1 : 0;
-    key.opt_stamp = raft_opt_generation();   // any raft_set_option call may change which kernels the loop launches
-    ++ctx->clock;
-    for (int k = 0; k < ctx->n_graphs; ++k)
-        if (memcmp(&ctx->graphs[k].key, &key, sizeof(key)) == 0) {
-            ctx->graphs[k].last_use = ctx->clock;
-            return (int)hipGraphLaunch(ctx->graphs[k].exec, s);
-        }
-    // capture the enqueue code: the event record / wait pairs pull the two side streams into the capture
-    rc = (int)hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-    if (rc != RAFT_OK) return rc;
-    rc = enqueue_loop(wts, src, B, h, w, iters, st, flow_up, stream, aux0, aux1, ctx, final_only);
-    hipGraph_t graph = nullptr;
-    const int rc_end = (int)hipStreamEndCapture(s, &graph);
-    if (rc == RAFT_OK) rc = rc_end;
-    hipGraphExec_t exec = nullptr;
-    if (rc == RAFT_OK) rc = (int)hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    if (graph) (void)hipGraphDestroy(graph);
-    if (rc != RAFT_OK) return rc;
-    int slot = ctx->n_graphs;
-    if (slot == 4) {   // evict the least recently used graph
-        slot = 0;
-        for (int k = 1; k < 4; ++k)
-            if (ctx->graphs[k].last_use < ctx->graphs[slot].last_use) slot = k;
-        (void)hipGraphExecDestroy(ctx->graphs[slot].exec);
-    } else {
-        ++ctx->n_graphs;
-    }
-    ctx->graphs[slot].key = key;
-    ctx->graphs[slot].exec = exec;
-    ctx->graphs[slot].last_use = ctx->clock;
-    return (int)hipGraphLaunch(exec, s);
+    return rc;
 }
 
 // Profiling twin of raft_iterate_basic_f32: identical launches, plus a HIP event after every kernel

@@ -56,7 +56,7 @@ namespace {
 const char *const kOptNames[RAFT_OPT_COUNT] = {
     "RAFT_CONV_WINO", "RAFT_SMALL_WINO", "RAFT_GRU_WINO", "RAFT_GRU_WINO4", "RAFT_WINO_TNW", "RAFT_WINO_SB",
     "RAFT_WINO_CK", "RAFT_WINO1D_TM",
-    "RAFT_LOOKUP_FUSED", "RAFT_ONDEMAND_BLOCK", "RAFT_ENC_WINO", "RAFT_LOOP_GRAPH",
+    "RAFT_LOOKUP_FUSED", "RAFT_ONDEMAND_BLOCK", "RAFT_ENC_WINO",
     "RAFT_WINO_KS", "RAFT_CONV_WINO4", "RAFT_WINO4_KS", "RAFT_MASK_FUSED", "RAFT_ENC_WINO4", "RAFT_CONVC2_KS", "RAFT_CONVF2_KS",
     "RAFT_EVENT_FENCE", "RAFT_CORR_XCD", "RAFT_CORR_POOL",
 };
@@ -69,7 +69,6 @@ struct Options {
     std::atomic<bool> set[RAFT_OPT_COUNT];
     int env_val[RAFT_OPT_COUNT];     // the load-time (environment) state: raft_set_option(name, NULL) returns to it
     bool env_set[RAFT_OPT_COUNT];
-    std::atomic<int> generation{0};
     std::mutex tile_mu;
     char tile_text[256], tile_env[256];
     TileRule tile_rules[kTileEntries];
@@ -132,7 +131,6 @@ int raft_opt(int id, int dflt) {
     return o.set[id].load(std::memory_order_relaxed) ? o.val[id].load(std::memory_order_relaxed) : dflt;
 }
 bool raft_opt_is_set(int id) { return opts().set[id].load(std::memory_order_relaxed); }
-int raft_opt_generation() { return opts().generation.load(std::memory_order_relaxed); }
 
 int raft_opt_conv_tile(int npad, int taps, bool (*valid)(int, int)) {
     Options &o = opts();
@@ -151,12 +149,10 @@ extern "C" int raft_set_option(const char *name, const char *value) {
     if (strcmp(name, "RAFT_CONV_TILE") == 0) {
         std::lock_guard<std::mutex> g(o.tile_mu);
         o.parse_tiles(value ? value : o.tile_env);
-        o.generation.fetch_add(1);
         return RAFT_OK;
     }
     const int i = opt_index(name);
     if (i < 0) return RAFT_E_UNSUPPORTED;
-    o.generation.fetch_add(1);
     if (value == nullptr) {   // back to the load-time state
         o.val[i].store(o.env_val[i]);
         o.set[i].store(o.env_set[i]);

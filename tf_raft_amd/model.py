@@ -27,7 +27,7 @@ import contextlib
 import ctypes as C
 import os
 from collections import OrderedDict
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -63,8 +63,20 @@ def _dropout_seed(model_seed: int, rank: int, step: int) -> int:
 DEFAULT_LANES = 3          # profiles/r12b_lanes_ab_per_process.txt: 1 / 2 / 3 / 4 / 6 lanes = 332 / 352 / 362 / 347-352 / 353-362 pairs/s at 4 pairs
 
 
+class _LoopPlan(NamedTuple):
+    """How one forward call schedules its recurrent loop, fixed when the call starts and passed down to the launchers."""
+    lane: int                   # whose flow / mask streams and raft_loop_ctx the loop uses
+    three_stream: bool          # flow / mask branches on side streams; False = the single-stream schedule
+    pre_hint: Optional[int]     # launch-shape hint of the encoders and volume build; None = the calling thread's own
+    loop_hint: int              # launch-shape hint of the loop
+
+
+def _hinted(hint):
+    return _ffi.thread_concurrency(hint) if hint is not None else contextlib.nullcontext()
+
+
 class RAFT:
-    """reference model.py:10-109."""
+    """reference model.py:10-109.  A model object is driven by one host thread at a time."""
 
     variant = 'raft'
 
@@ -102,8 +114,6 @@ class RAFT:
         self._state = None
         self._ring = []                          # pipelined forward: [UpdateState, loop-done event] per slot (lanes + 1 slots)
         self._calls = 0
-        self._lane = 0                           # the lane whose streams / loop context the loop launchers use
-        self._lane_mode = False                  # inside a pipelined call with several lanes and single-stream loops
         # which launches of a multi-lane call get the library's concurrency hint (launch shapes of a lanes-times larger batch):
         # 'loop' = the recurrent loop, 'all' = encoders and volume build as well, 'none'
         self._shape_hint = os.environ.get('RAFT_LANE_SHAPES', 'all')      # profiles/r12e_hint_ab.txt: 361 / 374 / 375 pairs/s with none / loop / all at 4 pairs
@@ -111,7 +121,6 @@ class RAFT:
         # pipelined one to obtain the same kernels, hence the same bits)
         self.loop_concurrency = 1 if loop_concurrency is None else max(1, int(loop_concurrency))
         self._lane_res = {}                      # lane -> (device, (flow stream, mask stream), raft_loop_ctx handle)
-        self._loop_stream = None
         _dev.reserve_streams(_dev.require_gpu())
         _dev.lib()
         if weights is None:
@@ -207,49 +216,23 @@ class RAFT:
     def _lane_role(role, lane):
         return role if lane == 0 else f'{role}{lane}'
 
-    def _loop_priority(self):
-        """Stream priority of the loop lanes.  RAFT_LOOP_PRIORITY=1 (high) is worth +0.7 % in a process that creates nothing but one
-        multi-lane model (379.4 / 380.0 against 376.9 / 377.0 pairs/s, A/B/A/B, profiles/r12n_steps_and_priority.txt) and costs 10 - 70 %
-        in a process that also holds a serial model: priority streams come from a pool of their own, and the two pools' streams then
-        collide on HIP's four hardware queues (profiles/r12t_config_bench.txt: SmallRAFT 747 -> 597, a serial model after a multi-lane one
-        328 -> 187 pairs/s).  Not the default."""
-        return -1 if os.environ.get('RAFT_LOOP_PRIORITY', '0') == '1' else _dev.STREAM_PRIORITY
-
-    def _lane_entry(self, dev):
-        """(device, (flow stream, mask stream), loop-context handle or None) of the current lane."""
-        ent = self._lane_res.get(self._lane)
+    def _lane_entry(self, dev, lane):
+        """(device, (flow stream, mask stream), loop-context handle or None) of ``lane``."""
+        ent = self._lane_res.get(lane)
         if ent is None or ent[0] != dev:
             if ent is not None:
-                self._free_lane(self._lane)
-            prio = self._loop_priority()
-            aux = (_dev.side_stream(dev, self._lane_role('flow', self._lane), prio),
-                   _dev.side_stream(dev, self._lane_role('mask', self._lane), prio))
-            ent = self._lane_res[self._lane] = [dev, aux, None]
+                self._free_lane(lane)
+            aux = (_dev.side_stream(dev, self._lane_role('flow', lane)), _dev.side_stream(dev, self._lane_role('mask', lane)))
+            ent = self._lane_res[lane] = [dev, aux, None]
         return ent
 
-    def _aux_streams(self, dev):
-        return self._lane_entry(dev)[1]
+    def _aux_streams(self, dev, lane):
+        return self._lane_entry(dev, lane)[1]
 
-    @contextlib.contextmanager
-    def _capturable_stream(self, dev):
-        """The three-stream loops replay a captured hipGraph for small batches (include/raft_hip.h, RAFT_LOOP_GRAPH); the
-        legacy default stream (handle 0, torch's default) cannot be captured, so when the caller is on it the loop is
-        enqueued on a private stream ordered after / before the current one."""
-        cur = torch.cuda.current_stream(dev)
-        if cur.cuda_stream != 0 or _ffi.get_option('RAFT_LOOP_GRAPH') != '1':    # replay is opt-in (measured slower)
-            yield
-            return
-        if self._loop_stream is None or self._loop_stream.device != dev:
-            self._loop_stream = _dev.side_stream(dev, 'loop')
-        self._loop_stream.wait_stream(cur)
-        with torch.cuda.stream(self._loop_stream):
-            yield
-        cur.wait_stream(self._loop_stream)   # joined: buffers allocated on `cur` are safe to reuse after this point
-
-    def _loop_context(self, dev):
-        """The caller-owned ``raft_loop_ctx`` (cross-stream events + hipGraph cache) of the three-stream loops: one per lane
-        (loops of different lanes run concurrently; loops of one lane follow each other in stream order and share it)."""
-        ent = self._lane_entry(dev)
+    def _loop_context(self, dev, lane):
+        """The caller-owned ``raft_loop_ctx`` (cross-stream events) of the three-stream loops: one per lane (loops of different
+        lanes run concurrently; loops of one lane follow each other in stream order and share it)."""
+        ent = self._lane_entry(dev, lane)
         if ent[2] is None:
             handle = C.c_void_p()
             with torch.cuda.device(dev):
@@ -273,33 +256,33 @@ class RAFT:
     def __del__(self):
         self._free_loop_context()
 
-    def _iterate(self, corr: CorrBlock, st, iters, flow_up):
-        if self.overlap:
+    def _iterate(self, corr: CorrBlock, st, iters, flow_up, plan=None):
+        if plan is None:                            # called on its own: lane 0 of the serial schedule
+            plan = self._plan(0, self.overlap, 1)
+        if plan.three_stream:
             # flow branch and mask branch of every iteration on two side streams (events inside the library)
             dev = flow_up.device
-            aux = self._aux_streams(dev)
-            with self._capturable_stream(dev):
-                check(_dev.lib().raft_iterate_basic_overlap_f32(
-                    C.byref(self.update_block.c), _dev.ptr(corr._pyr), corr._off, st.B, st.h, st.w, iters, C.byref(st.c),
-                    _dev.ptr(flow_up), _dev.stream_ptr(), aux[0].cuda_stream, aux[1].cuda_stream,
-                    self._loop_context(dev)), 'iterate_basic_overlap')
+            aux = self._aux_streams(dev, plan.lane)
+            check(_dev.lib().raft_iterate_basic_overlap_f32(
+                C.byref(self.update_block.c), _dev.ptr(corr._pyr), corr._off, st.B, st.h, st.w, iters, C.byref(st.c),
+                _dev.ptr(flow_up), _dev.stream_ptr(), aux[0].cuda_stream, aux[1].cuda_stream,
+                self._loop_context(dev, plan.lane)), 'iterate_basic_overlap')
             return
         check(_dev.lib().raft_iterate_basic_f32(C.byref(self.update_block.c), _dev.ptr(corr._pyr), corr._off,
                                                 st.B, st.h, st.w, iters, C.byref(st.c), _dev.ptr(flow_up),
                                                 _dev.stream_ptr()), 'iterate_basic')
 
-    def _iterate_alternate(self, corr: CorrBlock, st, iters, flow_up):
-        if self.variant == 'raft' and (self.overlap or self._lane_mode):
+    def _iterate_alternate(self, corr: CorrBlock, st, iters, flow_up, plan):
+        if self.variant == 'raft' and self.overlap:
             # the same C loop (three streams, or the loop's own stream three times = the single-stream schedule of a lane),
-            # lookups computed on demand from fmap1 and the pooled fmap2 pyramid
+            # lookups computed on demand from fmap1 and the pooled fmap2 pyramid; overlap=False keeps the loop below
             dev = flow_up.device
-            with self._capturable_stream(dev):
-                s0 = _dev.stream_ptr()
-                s1, s2 = ((a.cuda_stream for a in self._aux_streams(dev)) if self.overlap else (s0, s0))
-                check(_dev.lib().raft_iterate_basic_ondemand_f32(
-                    C.byref(self.update_block.c), _dev.ptr(corr.fmap1), _dev.ptr(corr._f2pyr), corr.fmap1.shape[-1],
-                    st.B, st.h, st.w, iters, C.byref(st.c), _dev.ptr(flow_up), s0, s1, s2, self._loop_context(dev)),
-                    'iterate_basic_ondemand')
+            s0 = _dev.stream_ptr()
+            s1, s2 = ((a.cuda_stream for a in self._aux_streams(dev, plan.lane)) if plan.three_stream else (s0, s0))
+            check(_dev.lib().raft_iterate_basic_ondemand_f32(
+                C.byref(self.update_block.c), _dev.ptr(corr.fmap1), _dev.ptr(corr._f2pyr), corr.fmap1.shape[-1],
+                st.B, st.h, st.w, iters, C.byref(st.c), _dev.ptr(flow_up), s0, s1, s2, self._loop_context(dev, plan.lane)),
+                'iterate_basic_ondemand')
             return
         g = st.g
         for i in range(iters):
@@ -340,15 +323,26 @@ class RAFT:
         if (self.pipeline if pipelined is None else pipelined) and not training:
             # several lanes (and their launch shapes) only for a model that asked for the pipelined schedule: predict() on a serial
             # model overlaps its calls on ONE lane with the serial schedule's kernels, so predict() == predict_step() bit for bit
-            return self._forward_pipelined(image1, image2, final_only, self.lanes if self.pipeline else 1)
+            lanes = self.lanes if self.pipeline else 1
+            n = self._calls
+            self._calls += 1
+            # with several lanes the loops are single-stream unless overlap was asked for: the lanes are each other's side branches
+            plan = self._plan(n % lanes, self.overlap and not (lanes > 1 and not self._overlap_given), lanes)
+            with _hinted(plan.pre_hint):
+                return self._forward_lane(image1, image2, final_only, n, lanes, plan)
         self._join_pipeline()                       # (a training-mode or serial call after pipelined ones)
-        self._lane = 0
-        if self.loop_concurrency > 1 and self._shape_hint == 'all' and not training:
-            with _ffi.thread_concurrency(self.loop_concurrency):        # the whole call with a multi-lane call's launch shapes
-                return self._forward_serial(image1, image2, training, final_only)
-        return self._forward_serial(image1, image2, training, final_only)
+        plan = self._plan(0, self.overlap, 1 if training else self.loop_concurrency)
+        with _hinted(plan.pre_hint):
+            return self._forward_serial(image1, image2, training, final_only, plan)
 
-    def _forward_serial(self, image1, image2, training, final_only):
+    def _plan(self, lane, three_stream, hint):
+        """The loop plan of one call.  ``hint`` is the number of loops that share the chip: the lanes of a pipelined call,
+        loop_concurrency of a serial inference call, 1 in training.  RAFT_LANE_SHAPES says whether the loop ('loop', 'all') and the
+        pre-loop work ('all') are launched with it; with a hint of 1 the pre-loop work keeps the calling thread's own."""
+        return _LoopPlan(lane, three_stream, hint if (hint > 1 and self._shape_hint == 'all') else None,
+                         hint if self._shape_hint in ('loop', 'all') else 1)
+
+    def _forward_serial(self, image1, image2, training, final_only, plan):
         B, H, W, _ = image1.shape
         if self.overlap and not training:
             # the context encoder does not depend on the feature encoder or the volume: it runs on a side stream
@@ -375,33 +369,32 @@ class RAFT:
             st = self._get_state(B, h, w, image1.device)
             self._prepare(cnet, st)                                             # model.py:84-89
         iters = self.iters if training else self.iters_pred
-        with _ffi.thread_concurrency(self.loop_concurrency if (not training and self._shape_hint in ('loop', 'all')) else 1):
-            out = self._run_loop(correlation, st, iters, self._alloc_out(iters, B, H, W, image1.device, final_only), final_only)
+        with _ffi.thread_concurrency(plan.loop_hint):
+            out = self._run_loop(correlation, st, iters, self._alloc_out(iters, B, H, W, image1.device, final_only), final_only, plan)
         return _dev.wrap(out) if final_only else [_dev.wrap(out[i]) for i in range(iters)]   # model.py:109
 
     @staticmethod
     def _alloc_out(iters, B, H, W, dev, final_only):
         return torch.empty((B, H, W, 2) if final_only else (iters, B, H, W, 2), device=dev, dtype=torch.float32)
 
-    def _run_loop(self, correlation, st, iters, out, final_only):
+    def _run_loop(self, correlation, st, iters, out, final_only, plan):
         """model.py:93-109 on the CURRENT stream (+ the two aux streams of the three-stream schedule) into ``out``."""
         B, h, w = st.B, st.h, st.w
         if final_only:
             last = out
-            with self._capturable_stream(last.device):
-                # single-stream schedule (several lanes): the flow / mask "branches" are the loop's own stream
-                s0 = _dev.stream_ptr()
-                s1, s2 = ((a.cuda_stream for a in self._aux_streams(last.device)) if self.overlap else (s0, s0))
-                check(_dev.lib().raft_iterate_basic_final_f32(
-                    C.byref(self.update_block.c), _dev.ptr(correlation._pyr), correlation._off, B, h, w, iters, C.byref(st.c),
-                    _dev.ptr(last), s0, s1, s2, self._loop_context(last.device)), 'iterate_basic_final')
+            # single-stream schedule (several lanes): the flow / mask "branches" are the loop's own stream
+            s0 = _dev.stream_ptr()
+            s1, s2 = ((a.cuda_stream for a in self._aux_streams(last.device, plan.lane)) if plan.three_stream else (s0, s0))
+            check(_dev.lib().raft_iterate_basic_final_f32(
+                C.byref(self.update_block.c), _dev.ptr(correlation._pyr), correlation._off, B, h, w, iters, C.byref(st.c),
+                _dev.ptr(last), s0, s1, s2, self._loop_context(last.device, plan.lane)), 'iterate_basic_final')
             self._last_correlation = correlation
             return last
         flow_up = out
         if self.alternate_corr:
-            self._iterate_alternate(correlation, st, iters, flow_up)
+            self._iterate_alternate(correlation, st, iters, flow_up, plan)
         else:
-            self._iterate(correlation, st, iters, flow_up)                      # model.py:93-106
+            self._iterate(correlation, st, iters, flow_up, plan)                # model.py:93-106
         self._last_correlation = correlation                                    # keep buffers alive until the stream drains
         return flow_up
 
@@ -442,36 +435,12 @@ class RAFT:
     # raft_loop_ctx of its own), so up to D loops of consecutive calls are resident together and each fills the other's gaps and
     # idle CUs; the UpdateState ring has D + 1 slots (call n + D + 1's pre-loop waits for loop n).  Each call still runs exactly
     # the kernels of the serial schedule in the same order on its own buffers: results stay bit-identical per call.
-    def _forward_pipelined(self, image1, image2, final_only, lanes):
+    def _forward_lane(self, image1, image2, final_only, n, lanes, plan):
         B, H, W, _ = image1.shape
         h, w = H // 8, W // 8
         dev = image1.device
         cur = torch.cuda.current_stream(dev)
-        n = self._calls
-        self._calls += 1
-        self._lane = lane = n % lanes
-        keep_overlap = self.overlap
-        if lanes > 1 and not self._overlap_given:
-            self.overlap = False                         # single-stream loops: the lanes are each other's side branches
-            self._lane_mode = True
-        try:
-            if lanes > 1 and self._shape_hint == 'all':
-                with _ffi.thread_concurrency(self._hint_value(lanes)):
-                    return self._forward_lane(image1, image2, final_only, n, lane, lanes, cur, dev, B, H, W, h, w)
-            return self._forward_lane(image1, image2, final_only, n, lane, lanes, cur, dev, B, H, W, h, w)
-        finally:
-            self.overlap = keep_overlap
-            self._lane = 0
-            self._lane_mode = False
-
-    @staticmethod
-    def _hint_value(lanes):
-        """The launch-shape hint of a multi-lane call: the number of loops that share the chip (RAFT_LANE_HINT overrides, for A/B runs)."""
-        v = os.environ.get('RAFT_LANE_HINT')
-        return max(1, int(v)) if v else lanes
-
-    def _forward_lane(self, image1, image2, final_only, n, lane, lanes, cur, dev, B, H, W, h, w):
-        loop = _dev.side_stream(dev, self._lane_role('loop', lane), priority=self._loop_priority())
+        loop = _dev.side_stream(dev, self._lane_role('loop', plan.lane))
         ent = self._ring_state(n % (lanes + 1), B, h, w, dev)
         st = ent[0]
         if ent[1] is not None:
@@ -485,8 +454,8 @@ class RAFT:
         ready = torch.cuda.Event()
         ready.record(cur)
         loop.wait_event(ready)
-        with torch.cuda.stream(loop), _ffi.thread_concurrency(self._hint_value(lanes) if self._shape_hint in ('loop', 'all') else 1):
-            self._run_loop(correlation, st, self.iters_pred, out, final_only)
+        with torch.cuda.stream(loop), _ffi.thread_concurrency(plan.loop_hint):
+            self._run_loop(correlation, st, self.iters_pred, out, final_only, plan)
             done = torch.cuda.Event()
             done.record(loop)
         for t in (out, getattr(correlation, '_pyr', None), getattr(correlation, '_f2pyr', None), correlation.fmap1, correlation.fmap2):
@@ -758,7 +727,7 @@ class SmallRAFT(RAFT):
         check(_dev.lib().raft_prepare_state_small_f32(_dev.ptr(cnet), st.B, st.h, st.w, C.byref(st.c),
                                                       _dev.stream_ptr()), 'prepare_state_small')
 
-    def _iterate(self, corr, st, iters, flow_up):
+    def _iterate(self, corr, st, iters, flow_up, plan=None):
         check(_dev.lib().raft_iterate_small_f32(C.byref(self.update_block.c), _dev.ptr(corr._pyr), corr._off,
                                                 st.B, st.h, st.w, iters, C.byref(st.c), _dev.ptr(flow_up),
                                                 _dev.stream_ptr()), 'iterate_small')

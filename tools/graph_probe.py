@@ -1,4 +1,4 @@
-"""One RAFT forward loop at batch B, a few calls, under whatever RAFT_LOOP_GRAPH says (run it under rocprofv3 --kernel-trace:
+"""One RAFT forward loop at batch B, a few calls (run it under rocprofv3 --kernel-trace:
 tools/graph_trace.py reads the start / end timestamps of the kernels of the LAST call and says where the time goes).
 usage: python tools/graph_probe.py <batch> [calls]"""
 import os
@@ -28,4 +28,4 @@ for _ in range(calls):
     model([i1, i2])
     torch.cuda.synchronize()
     t.append((time.perf_counter() - t0) * 1e3)
-print(f'B={B} RAFT_LOOP_GRAPH={os.environ.get("RAFT_LOOP_GRAPH", "unset")}: ms per call {[round(x, 3) for x in t]}')
+print(f'B={B}: ms per call {[round(x, 3) for x in t]}')

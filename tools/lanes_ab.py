@@ -53,7 +53,7 @@ for r in range(args.rounds):
             m([i1, i2])
         torch.cuda.synchronize()
         rates[s].append(B * args.steps / (time.perf_counter() - t0))
-tag = ' '.join(f'{k}={os.environ[k]}' for k in ('GPU_MAX_HW_QUEUES', 'RAFT_LOOP_PRIORITY', 'RAFT_EVENT_FENCE') if k in os.environ) or 'defaults'
+tag = ' '.join(f'{k}={os.environ[k]}' for k in ('GPU_MAX_HW_QUEUES', 'RAFT_EVENT_FENCE') if k in os.environ) or 'defaults'
 for s in args.settings:
     v = rates[s]
     print(f'[{tag}] B={B} steps={args.steps} {s:>7}: median {np.median(v):7.1f} pairs/s  (rounds {[round(x, 1) for x in v]})', flush=True)

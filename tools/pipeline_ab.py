@@ -13,7 +13,7 @@ from tf_raft_amd import weights as wm  # noqa: E402
 
 dev = torch.device('cuda', 0)
 batches = [int(a) for a in sys.argv[1:]] or [4, 8]
-tag = ' '.join(f'{k}={os.environ[k]}' for k in ('RAFT_PIPELINE', 'RAFT_LOOP_PRIORITY', 'GPU_MAX_HW_QUEUES') if k in os.environ) or 'defaults'
+tag = ' '.join(f'{k}={os.environ[k]}' for k in ('RAFT_PIPELINE', 'GPU_MAX_HW_QUEUES') if k in os.environ) or 'defaults'
 model = tf_raft_amd.RAFT(weights=wm.init_weights('raft', seed=0), iters_pred=24)
 for B in batches:
     g = torch.Generator(device=dev).manual_seed(B)
