@@ -3,18 +3,21 @@
 // build_sanitizer_library): no device code, no GPU -- what runs here is everything an entry point does BEFORE it launches:
 // argument validation, geometry / workspace arithmetic, the option table, error strings.  Every launching entry point is
 // called with arguments it must reject (null pointers, bad shapes, misaligned buffers) and has to return an error code
-// without touching memory; the pure-host helpers are called with valid arguments; four threads then hammer the option table
-// and the helpers concurrently (the only process-global state of the library).
+// without touching memory; the pure-host helpers are called with valid arguments; the launch plans (which kernel family and
+// workgroup shape every update-block layer and encoder stage runs) are checked against a table; four threads then hammer the
+// option table, the helpers and the plans concurrently (the only process-global state of the library).
 // Test infrastructure: built and run by tests/test_abi_sanitizers.py, never shipped.
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <thread>
 #include <vector>
 
 #include "raft_hip.h"
+#include "../../tf_raft_amd/csrc/launch_plan.h"
 
 static int failures = 0;
 #define EXPECT(cond)                                                        \
@@ -112,7 +115,173 @@ static void rejects() {
     EXPECT(raft_loop_ctx_destroy(nullptr) == 0 || true);
 }
 
+// ---- launch plans (tf_raft_amd/csrc/launch_plan.h) at 448 x 512 (56 x 64 features), every weight copy supplied
+static std::string plan_str(const ConvChoice &c) {
+    char b[48];
+    switch (c.family) {
+        case RAFT_FAM_HALO: std::snprintf(b, sizeof b, "halo th%d tn%d", c.halo.th, c.halo.tn); break;
+        case RAFT_FAM_WINO: std::snprintf(b, sizeof b, "F2x2 tnw%d sb%d ck%d ks%d", c.wino.tnw, c.wino.sb, c.wino.ck, c.wino.ks); break;
+        case RAFT_FAM_WINO1D:
+            if (c.wino1d.mo == 4) std::snprintf(b, sizeof b, "F4,5 tnw%d", c.wino1d.tnw);
+            else std::snprintf(b, sizeof b, "F2,5 tnw%d tm%d ck%d", c.wino1d.tnw, c.wino1d.tm, c.wino1d.ck);
+            break;
+        case RAFT_FAM_WINO4: std::snprintf(b, sizeof b, "F4x4 ks%d", c.wino4.ks); break;
+        default: std::snprintf(b, sizeof b, "family %d", c.family);
+    }
+    return b;
+}
+#define EXPECT_PLAN(choice, want)                                                                            \
+    do {                                                                                                     \
+        const std::string got__ = plan_str(choice);                                                          \
+        if (got__ != (want)) {                                                                               \
+            std::fprintf(stderr, "FAILED %s:%d: %s is \"%s\", expected \"%s\"\n", __FILE__, __LINE__, #choice, got__.c_str(), want); \
+            ++failures;                                                                                      \
+        }                                                                                                    \
+    } while (0)
+
+static float plan_dummy[4];
+static raft_conv_weights cw(int npad) { return {plan_dummy, plan_dummy, npad}; }
+
+struct BasicRow {
+    int B, hint;
+    const char *convc2, *convf2, *conv, *fh1_mask0, *fh1, *gru[4];   // fh1: final-only flow head; gru: zr1, q1, zr2, q2
+    bool lookup_fused, mask_fused;
+};
+static const BasicRow kBasic[] = {
+    {1, 1, "F2x2 tnw1 sb1 ck4 ks2", "halo th4 tn1", "F2x2 tnw1 sb1 ck4 ks2", "F2x2 tnw1 sb1 ck2 ks1", "F2x2 tnw1 sb1 ck2 ks1", {"F2,5 tnw1 tm1 ck2", "F2,5 tnw1 tm1 ck2", "F2,5 tnw1 tm1 ck2", "F2,5 tnw1 tm1 ck2"}, 1, 0},
+    {1, 3, "F4x4 ks2", "F4x4 ks2", "F2x2 tnw1 sb1 ck2 ks1", "F4x4 ks1", "F4x4 ks1", {"F4,5 tnw1", "F4,5 tnw1", "F4,5 tnw1", "F4,5 tnw1"}, 1, 1},
+    {2, 1, "F2x2 tnw1 sb1 ck2 ks1", "halo th4 tn1", "F2x2 tnw1 sb1 ck4 ks2", "F4x4 ks2", "F4x4 ks2", {"F4,5 tnw1", "F4,5 tnw1", "F4,5 tnw1", "F4,5 tnw1"}, 1, 1},
+    {2, 3, "F4x4 ks2", "F4x4 ks2", "F2x2 tnw1 sb1 ck2 ks1", "F4x4 ks1", "F4x4 ks1", {"F4,5 tnw2", "F4,5 tnw1", "F4,5 tnw2", "F4,5 tnw1"}, 1, 1},
+    {3, 1, "F4x4 ks2", "F4x4 ks2", "F2x2 tnw1 sb1 ck2 ks1", "F4x4 ks1", "F4x4 ks1", {"F4,5 tnw1", "F4,5 tnw1", "F4,5 tnw1", "F4,5 tnw1"}, 1, 1},
+    {3, 3, "F4x4 ks1", "F4x4 ks1", "F4x4 ks2", "F4x4 ks1", "F4x4 ks1", {"F4,5 tnw2", "F4,5 tnw2", "F4,5 tnw2", "F4,5 tnw2"}, 1, 1},
+    {4, 1, "F4x4 ks2", "F4x4 ks2", "F2x2 tnw1 sb1 ck2 ks1", "F4x4 ks1", "F4x4 ks1", {"F4,5 tnw2", "F4,5 tnw1", "F4,5 tnw2", "F4,5 tnw1"}, 1, 1},
+    {4, 3, "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", {"F4,5 tnw2", "F4,5 tnw2", "F4,5 tnw2", "F4,5 tnw2"}, 1, 1},
+    {8, 1, "F4x4 ks1", "F4x4 ks1", "F4x4 ks2", "F4x4 ks1", "F4x4 ks1", {"F4,5 tnw2", "F4,5 tnw2", "F4,5 tnw2", "F4,5 tnw2"}, 1, 1},
+    {8, 3, "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", {"F4,5 tnw2", "F4,5 tnw2", "F4,5 tnw2", "F4,5 tnw2"}, 1, 1},
+    {16, 1, "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", {"F4,5 tnw2", "F4,5 tnw2", "F4,5 tnw2", "F4,5 tnw2"}, 1, 1},
+    {16, 3, "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", {"F4,5 tnw2", "F4,5 tnw2", "F4,5 tnw2", "F4,5 tnw2"}, 1, 1},
+};
+struct SmallRow {
+    int B, hint;
+    const char *convc1, *convf2, *conv, *gru_zr, *gru_q, *fh1;
+};
+static const SmallRow kSmall[] = {
+    {4, 1, "halo th7 tn1", "halo th4 tn1", "F2x2 tnw1 sb1 ck2 ks1", "F2x2 tnw1 sb0 ck1 ks1", "F2x2 tnw1 sb1 ck2 ks1", "F2x2 tnw1 sb1 ck2 ks1"},
+    {4, 3, "halo th7 tn1", "halo th4 tn1", "F2x2 tnw2 sb1 ck1 ks1", "F2x2 tnw2 sb1 ck1 ks1", "F2x2 tnw2 sb1 ck1 ks1", "F2x2 tnw2 sb1 ck1 ks1"},
+};
+// the stride-1 3x3 layers of BasicEncoder stages layer1..3 (224 x 256 x 64, 112 x 128 x 96, 56 x 64 x 128); fnet: 2B images,
+// instance norm (moments in the epilogue); cnet: B images, folded batch norm
+struct EncRow {
+    int B, hint, cnet;
+    const char *stage[3];
+};
+static const EncRow kEnc[] = {
+    {1, 1, 0, {"F2x2 tnw2 sb1 ck1 ks1", "F2x2 tnw1 sb0 ck1 ks1", "F2x2 tnw1 sb1 ck2 ks1"}},
+    {1, 1, 1, {"F2x2 tnw1 sb0 ck1 ks1", "F2x2 tnw1 sb1 ck2 ks1", "F2x2 tnw1 sb1 ck4 ks2"}},
+    {1, 3, 0, {"F4x4 ks1", "F4x4 ks1", "F2x2 tnw1 sb1 ck2 ks1"}},
+    {1, 3, 1, {"F4x4 ks1", "F2x2 tnw2 sb1 ck1 ks1", "F2x2 tnw1 sb1 ck2 ks1"}},
+    {4, 1, 0, {"F4x4 ks1", "F4x4 ks1", "F2x2 tnw1 sb0 ck1 ks1"}},
+    {4, 1, 1, {"F4x4 ks1", "F2x2 tnw2 sb1 ck1 ks1", "F2x2 tnw1 sb1 ck2 ks1"}},
+    {4, 3, 0, {"F4x4 ks1", "F4x4 ks1", "F4x4 ks1"}},
+    {4, 3, 1, {"F4x4 ks1", "F4x4 ks1", "F2x2 tnw2 sb1 ck1 ks1"}},
+};
+// forced switches (raft_set_option); rows as above
+struct SwitchRows {
+    const char *name, *value;
+    BasicRow basic[2];
+    EncRow enc[2];
+};
+static const SwitchRows kSwitched[] = {
+    {"RAFT_WINO4_KS", "1",
+     {{4, 1, "F4x4 ks1", "F4x4 ks1", "F2x2 tnw1 sb1 ck2 ks1", "F4x4 ks1", "F4x4 ks1", {"F4,5 tnw2", "F4,5 tnw1", "F4,5 tnw2", "F4,5 tnw1"}, 1, 1},
+      {4, 3, "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", {"F4,5 tnw2", "F4,5 tnw2", "F4,5 tnw2", "F4,5 tnw2"}, 1, 1}},
+     {{1, 3, 1, {"F4x4 ks1", "F2x2 tnw2 sb1 ck1 ks1", "F2x2 tnw1 sb1 ck2 ks1"}}, {4, 3, 1, {"F4x4 ks1", "F4x4 ks1", "F2x2 tnw2 sb1 ck1 ks1"}}}},
+    {"RAFT_CONVC2_KS", "2",
+     {{4, 1, "F4x4 ks2", "F4x4 ks2", "F2x2 tnw1 sb1 ck2 ks1", "F4x4 ks1", "F4x4 ks1", {"F4,5 tnw2", "F4,5 tnw1", "F4,5 tnw2", "F4,5 tnw1"}, 1, 1},
+      {4, 3, "F4x4 ks2", "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", {"F4,5 tnw2", "F4,5 tnw2", "F4,5 tnw2", "F4,5 tnw2"}, 1, 1}},
+     {{1, 1, 1, {"F2x2 tnw1 sb0 ck1 ks1", "F2x2 tnw1 sb1 ck2 ks1", "F2x2 tnw1 sb1 ck4 ks2"}}, {4, 3, 0, {"F4x4 ks1", "F4x4 ks1", "F4x4 ks1"}}}},
+    {"RAFT_GRU_WINO4", "0",
+     {{4, 1, "F4x4 ks2", "F4x4 ks2", "F2x2 tnw1 sb1 ck2 ks1", "F4x4 ks1", "F4x4 ks1", {"F2,5 tnw2 tm2 ck2", "F2,5 tnw1 tm2 ck2", "F2,5 tnw2 tm2 ck2", "F2,5 tnw1 tm2 ck2"}, 1, 1},
+      {4, 3, "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", {"F2,5 tnw2 tm2 ck2", "F2,5 tnw2 tm2 ck2", "F2,5 tnw2 tm2 ck2", "F2,5 tnw2 tm2 ck2"}, 1, 1}},
+     {{1, 1, 0, {"F2x2 tnw2 sb1 ck1 ks1", "F2x2 tnw1 sb0 ck1 ks1", "F2x2 tnw1 sb1 ck2 ks1"}}, {1, 3, 0, {"F4x4 ks1", "F4x4 ks1", "F2x2 tnw1 sb1 ck2 ks1"}}}},
+    {"RAFT_ENC_WINO4", "7",   // explicit: every stage, no grid test
+     {{4, 1, "F4x4 ks2", "F4x4 ks2", "F2x2 tnw1 sb1 ck2 ks1", "F4x4 ks1", "F4x4 ks1", {"F4,5 tnw2", "F4,5 tnw1", "F4,5 tnw2", "F4,5 tnw1"}, 1, 1},
+      {4, 3, "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", "F4x4 ks1", {"F4,5 tnw2", "F4,5 tnw2", "F4,5 tnw2", "F4,5 tnw2"}, 1, 1}},
+     {{1, 1, 0, {"F4x4 ks1", "F4x4 ks1", "F4x4 ks1"}}, {1, 1, 1, {"F4x4 ks2", "F4x4 ks2", "F4x4 ks2"}}}},
+};
+
+static raft_basic_update_weights basic_weights() {
+    raft_basic_update_weights w = {};
+    w.convc1 = cw(256); w.convc2 = cw(192); w.convf2 = cw(64); w.conv = cw(128);
+    w.gru_zr1 = w.gru_zr2 = cw(256); w.gru_q1 = w.gru_q2 = cw(128); w.fh1_mask0 = cw(512); w.mask2 = cw(576);
+    w.convc2_w = cw(192); w.convf2_w = cw(64); w.conv_w = cw(128); w.fh1_mask0_w = cw(512);
+    w.gru_zr1_w = w.gru_zr2_w = cw(256); w.gru_q1_w = w.gru_q2_w = cw(128); w.fh1_w = cw(256);
+    w.gru_zr1_w4 = w.gru_zr2_w4 = cw(256); w.gru_q1_w4 = w.gru_q2_w4 = cw(128);
+    w.convc2_w44 = cw(192); w.conv_w44 = cw(128); w.fh1_mask0_w44 = cw(512); w.fh1_w44 = cw(256); w.convf2_w44 = cw(64);
+    w.convc1_f = cw(256);
+    return w;
+}
+
+// check_fused: false while other threads flip RAFT_LOOKUP_FUSED (options_once)
+static void check_basic(const BasicRow &r, bool check_fused) {
+    static const raft_basic_update_weights w = basic_weights();
+    const BasicLoopPlan p = raft_basic_loop_plan(w, r.B, 56, 64, true, r.hint);
+    EXPECT_PLAN(p.convc2, r.convc2);
+    EXPECT_PLAN(p.convf2, r.convf2);
+    EXPECT_PLAN(p.conv, r.conv);
+    EXPECT_PLAN(p.fh1_mask0, r.fh1_mask0);
+    EXPECT_PLAN(p.fh1, r.fh1);
+    for (int l = 0; l < 4; ++l) EXPECT_PLAN(p.gru[l], r.gru[l]);
+    EXPECT(!check_fused || p.lookup_fused == r.lookup_fused);
+    EXPECT(p.mask_fused == r.mask_fused);
+}
+
+static void check_enc(const EncRow &r) {
+    const int Ho[3] = {224, 112, 56}, Wo[3] = {256, 128, 64}, F[3] = {64, 96, 128};
+    const int n = r.cnet ? r.B : 2 * r.B;
+    for (int st = 0; st < 3; ++st) {
+        const int npad = (F[st] + 63) / 64 * 64;
+        EXPECT_PLAN(raft_enc_stage_wino4(st, n, Ho[st], Wo[st], F[st], r.hint)
+                        ? raft_choice(raft_wino4_plan(n, Ho[st], Wo[st], F[st], 0, npad, r.cnet, r.hint))
+                        : raft_choice(raft_wino_plan(n, Ho[st], Wo[st], F[st], 0, npad, r.cnet, r.hint)),
+                    r.stage[st]);
+    }
+}
+
+static void plans_once(bool check_fused) {
+    for (const BasicRow &r : kBasic) check_basic(r, check_fused);
+    raft_small_update_weights sw = {};
+    sw.convc1 = cw(128); sw.convf2 = cw(64); sw.conv = cw(128); sw.gru_zr = cw(192); sw.gru_q = cw(128); sw.fh1 = cw(128);
+    sw.conv_w = cw(128); sw.gru_zr_w = cw(192); sw.gru_q_w = cw(128); sw.fh1_w = cw(128);
+    for (const SmallRow &r : kSmall) {
+        const SmallLoopPlan p = raft_small_loop_plan(sw, r.B, 56, 64, r.hint);
+        EXPECT_PLAN(p.convc1, r.convc1);
+        EXPECT_PLAN(p.convf2, r.convf2);
+        EXPECT_PLAN(p.conv, r.conv);
+        EXPECT_PLAN(p.gru_zr, r.gru_zr);
+        EXPECT_PLAN(p.gru_q, r.gru_q);
+        EXPECT_PLAN(p.fh1, r.fh1);
+    }
+    for (const EncRow &r : kEnc) check_enc(r);
+}
+
+static void switched_plans() {   // single-threaded: the switches are process-global
+    for (const SwitchRows &sr : kSwitched) {
+        EXPECT(raft_set_option(sr.name, sr.value) == 0);
+        for (const BasicRow &r : sr.basic) check_basic(r, true);
+        for (const EncRow &r : sr.enc) check_enc(r);
+        EXPECT(raft_set_option(sr.name, "") == 0);
+    }
+}
+
 int main() {
+    // the plan table describes the built-in defaults: no tuning switch from the environment
+    const char *plan_switches[] = {"RAFT_CONV_WINO", "RAFT_SMALL_WINO", "RAFT_GRU_WINO", "RAFT_GRU_WINO4", "RAFT_WINO_TNW", "RAFT_WINO_SB",
+                                   "RAFT_WINO_CK", "RAFT_WINO1D_TM", "RAFT_LOOKUP_FUSED", "RAFT_ENC_WINO", "RAFT_WINO_KS", "RAFT_CONV_WINO4",
+                                   "RAFT_WINO4_KS", "RAFT_MASK_FUSED", "RAFT_ENC_WINO4", "RAFT_CONVC2_KS", "RAFT_CONVF2_KS", "RAFT_CONV_TILE"};
+    for (const char *name : plan_switches) EXPECT(raft_set_option(name, "") == 0);
+    plans_once(true);
+    switched_plans();
     helpers_once(0);
     options_once(0);
     rejects();
@@ -127,6 +296,12 @@ int main() {
                 helpers_once(t * 1000 + i);
                 options_once(t + i);
                 if ((i & 63) == 0) rejects();
+                if ((i & 15) == 0) plans_once(false);
+                if (i == 200) {   // the plan functions take the hint as an argument: the thread's own hint changes nothing
+                    raft_set_thread_concurrency(5 - t);
+                    plans_once(false);
+                    raft_set_thread_concurrency(t + 2);
+                }
                 EXPECT(raft_set_thread_concurrency(t + 2) == t + 2);
             }
             EXPECT(raft_set_thread_concurrency(0) == t + 2);       // n < 1 restores the default ...

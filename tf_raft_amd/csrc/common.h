@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/raft_hip.h"
+#include "launch_plan.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -61,24 +62,10 @@ __host__ __device__ inline void raft_untiled_yx(int n, int tiles_x, int *y, int 
     *x = (t % tiles_x) * RAFT_TILE_W + (n & (RAFT_TILE_W - 1));
 }
 
-// Tuning switches (include/raft_hip.h: raft_set_option).  Process-global, initialised ONCE from the environment when the
-// library is loaded and changed only through raft_set_option afterwards: the launch path reads an atomic int, it never
-// calls getenv.  raft_opt(id, dflt) = the switch's value, or dflt while it is unset.
-enum RaftOptionId {
-    RAFT_OPT_CONV_WINO, RAFT_OPT_SMALL_WINO, RAFT_OPT_GRU_WINO, RAFT_OPT_GRU_WINO4, RAFT_OPT_WINO_TNW, RAFT_OPT_WINO_SB,
-    RAFT_OPT_WINO_CK, RAFT_OPT_WINO1D_TM,
-    RAFT_OPT_LOOKUP_FUSED, RAFT_OPT_ONDEMAND_BLOCK, RAFT_OPT_ENC_WINO,
-    RAFT_OPT_WINO_KS, RAFT_OPT_CONV_WINO4, RAFT_OPT_WINO4_KS, RAFT_OPT_MASK_FUSED, RAFT_OPT_ENC_WINO4, RAFT_OPT_CONVC2_KS, RAFT_OPT_CONVF2_KS,
-    RAFT_OPT_EVENT_FENCE, RAFT_OPT_CORR_XCD, RAFT_OPT_CORR_POOL,
-    RAFT_OPT_COUNT
-};
-int raft_opt(int id, int dflt);
 // raft_set_thread_concurrency (include/raft_hip.h): how many independent launch sequences of about this size share the device
-// with the calling thread's launches (>= 1).  The launchers' "does this grid fill the chip?" rules count a grid n times.
+// with the calling thread's launches (>= 1).  Read only by the extern "C" entry points, once per call: the launch plans
+// (launch_plan.h) count a grid that many times in their "does this grid fill the chip?" rules.
 int raft_concurrency();
-bool raft_opt_is_set(int id);
-// RAFT_CONV_TILE ("<code>" or "<npad>:<taps>:<code>,..."): the tile code forced for a convolution, or -1
-int raft_opt_conv_tile(int npad, int taps, bool (*valid)(int code, int npad));
 
 struct PyramidGeom {
     int64_t off[RAFT_MAX_LEVELS];   // float offset of each level of the corr pyramid

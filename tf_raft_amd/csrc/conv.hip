@@ -12,64 +12,10 @@
 // mask.2 + RAFT.upsample_flow in one kernel (mask_upsample.hip)
 int raft_launch_mask_upsample(const float *a, int lda, const float *wp, const float *bias, int npad, const float *flow, int B,
                               int h, int w, float scale, float *out, hipStream_t s, int max_wgs = 0);
-// RAFT_MASK_FUSED: the prediction loops run mask.2 and the convex upsampling as one kernel.  Default: from 2 pairs (2 x 3584
-// feature pixels) on.  Launched one workgroup per tile the fused kernel only pays from 4 pairs (single pair 152.7 pairs/s with two
-// kernels, 137.8 - 142.0 fused; two pairs 210.7 / 205.4; four 282.7 / 288.4: profiles/r08k_round3_options.txt, r07q); as the
-// 32-workgroup background branch of the three-stream loop (struct Overlap) it pays from 2 pairs: 225.5 -> 244.1 pairs/s at two,
-// 246.3 -> 256.3 at three (profiles/r09e_small_batch_mask.txt); a single pair stays on the two-kernel path (152 - 153 against
-// 148 - 155).
-static bool mask_is_fused(const raft_basic_update_weights *wts, int64_t pixels) {
-    return raft_opt(RAFT_OPT_MASK_FUSED, pixels * raft_concurrency() >= 2 * 3584 ? 1 : 0) != 0 && wts->mask2.wp != nullptr && wts->mask2.npad == 576;
-}
-
 // ------------------------------------------------------------------------------------------------
-// tile selection + dispatch of the direct (halo-tiled) convolution kernel
+// dispatch of the direct (halo-tiled) convolution kernel (tile: launch_plan.h raft_halo_plan)
 // ------------------------------------------------------------------------------------------------
-// Tuning / test override: RAFT_CONV_TILE is either one code (applies to every convolution whose npad
-// it divides) or a comma-separated list of `npad:taps:code` entries, e.g. "256:5:171,128:5:141".
-// code = 100 + 10*TH + TN: TH x 16-pixel x 64*TN-channel workgroups of the halo-tiled kernel.
-static bool code_valid(int code, int npad) {
-    if (code >= 100) {
-        const int th = (code - 100) / 10, tn = (code - 100) % 10;
-        return (th == 4 || th == 7 || th == 8) && (tn == 1 || tn == 2) && npad % (64 * tn) == 0;
-    }
-    return false;
-}
-static int forced_code(int npad, int taps) { return raft_opt_conv_tile(npad, taps, code_valid); }
-
-// Pick the halo tile (TH x 16 pixels, 64*TN channels) by a small cost model of MI355X (256 CUs):
-//   time ~ (workgroups per CU, rounded up) x (MFMA work of one tile) x (latency-hiding penalty),
-// where the penalty reflects how many workgroups (= waves per SIMD) are co-resident on a CU: one wave
-// per SIMD exposes prologue / barrier / epilogue latency, three or more hide it (docs/NOTEBOOK.md section 4.1).
-static int pick_code(const ConvArgs &a, int kh, int kw) {
-    const int f = forced_code(a.npad, kh * kw);
-    if (f >= 100) return f;
-    static const int ths[3] = {4, 7, 8};
-    double best = 1e30;
-    int best_code = 141;
-    for (int ti = 0; ti < 3; ++ti)
-        for (int tn = 1; tn <= 2; ++tn) {
-            const int th = ths[ti];
-            if (a.npad % (64 * tn)) continue;
-            const int64_t blocks = (int64_t)a.B * ((a.H + th - 1) / th) * ((a.W + 15) / 16) * (a.npad / (64 * tn)) * raft_concurrency();
-            const int64_t per_cu = (blocks + 255) / 256;
-            const int lds = 2 * ((th + kh - 1) * (16 + kw - 1) * 40 + 8) * 4;
-            int resident = 160 * 1024 / lds;
-            const int reg_limit = (tn == 2 && th >= 7) ? 1 : (th >= 7 ? 2 : 3);   // VGPR + AGPR budget per SIMD
-            if (resident > reg_limit) resident = reg_limit;
-            const int64_t conc = per_cu < resident ? per_cu : resident;
-            const double pen = conc >= 3 ? 1.0 : (conc == 2 ? 1.05 : 1.15);
-            const double eff = (th == 4 && kh * kw > 1) ? 0.88 : 1.0;   // short tiles: more halo traffic per MFMA (measured; a 1x1 kernel has no halo)
-            const double cost = (double)per_cu * th * 16 * 64 * tn * pen / eff;
-            if (cost < best) {
-                best = cost;
-                best_code = 100 + th * 10 + tn;
-            }
-        }
-    return best_code;
-}
-
-int raft_launch_conv(const ConvArgs &a_in, int kh, int kw, int epi, hipStream_t s) {
+int raft_launch_conv(const ConvArgs &a_in, int kh, int kw, int epi, hipStream_t s, HaloPlan p) {
     ConvArgs a = a_in;
     if (a.Hi == 0) {   // plain stride-1 'same' convolution
         a.Hi = a.H;
@@ -78,197 +24,88 @@ int raft_launch_conv(const ConvArgs &a_in, int kh, int kw, int epi, hipStream_t 
         a.pl = (kw - 1) / 2;
     }
     if (a.c0 <= 0 || a.c0 % 32 || a.c1 < 0 || a.c1 % 32 || a.npad <= 0 || a.npad % 64) return RAFT_E_UNSUPPORTED;
-    if (a.lda0 % 4 || (a.c1 && a.lda1 % 4)) return RAFT_E_ALIGN;
-    if (!raft_aligned16(a.a0) || !raft_aligned16(a.wp) || (a.c1 && !raft_aligned16(a.a1))) return RAFT_E_ALIGN;
-    {   // every operand is addressed through 32-bit buffer offsets: each must span < 2 GiB
-        const int64_t M = (int64_t)a.B * a.H * a.W;
-        const int64_t lim = (int64_t)1 << 31;
-        const int64_t e0 = ((M - 1) * a.lda0 + a.c0) * 4, e1 = a.c1 ? ((M - 1) * a.lda1 + a.c1) * 4 : 0;
-        if (e0 >= lim || e1 >= lim) return RAFT_E_UNSUPPORTED;
-        if (M * a.ldo0 * 4 >= lim || (a.o1 && M * a.ldo1 * 4 >= lim) || (a.e0 && M * a.lde0 * 4 >= lim) ||
-            (a.e1 && M * a.lde1 * 4 >= lim))
-            return RAFT_E_UNSUPPORTED;
-        if ((int64_t)kh * kw * (a.c0 + a.c1) * a.npad * 4 >= lim) return RAFT_E_UNSUPPORTED;
-    }
-    const bool known = (kh == 1 && kw == 1) || (kh == 3 && kw == 3) || (kh == 1 && kw == 5) || (kh == 5 && kw == 1);
-    if (!known) return RAFT_E_UNSUPPORTED;
-    const int code = pick_code(a, kh, kw);
-    if (a.init) {
-        const int64_t M = (int64_t)a.B * a.H * a.W;
-        if (M * a.ldi * 4 >= ((int64_t)1 << 31)) return RAFT_E_UNSUPPORTED;
-    }
-    if (code >= 100) {
-        const int th = (code - 100) / 10, tn = (code - 100) % 10;
-        if (kh == 1 && kw == 1) return raft_launch_conv_halo_1x1(a, th, tn, epi, s);
-        if (kh == 3 && kw == 3) return raft_launch_conv_halo_3x3(a, th, tn, epi, s);
-        if (kh == 1 && kw == 5) return raft_launch_conv_halo_1x5(a, th, tn, epi, s);
-        return raft_launch_conv_halo_5x1(a, th, tn, epi, s);
-    }
+    RAFT_TRY(raft_check_operands(a, kh * kw, RAFT_CHECK_ALL));
+    if (!raft_halo_code_valid(100 + 10 * p.th + p.tn, a.npad)) return RAFT_E_UNSUPPORTED;
+    if (kh == 1 && kw == 1) return raft_launch_conv_halo_1x1(a, p.th, p.tn, epi, s);
+    if (kh == 3 && kw == 3) return raft_launch_conv_halo_3x3(a, p.th, p.tn, epi, s);
+    if (kh == 1 && kw == 5) return raft_launch_conv_halo_1x5(a, p.th, p.tn, epi, s);
+    if (kh == 5 && kw == 1) return raft_launch_conv_halo_5x1(a, p.th, p.tn, epi, s);
     return RAFT_E_UNSUPPORTED;
+}
+
+// The single-convolution entry points: one validation, one argument block, the family's default plan under the caller's hint.
+static int single_conv(int family, int kh, int kw, int mo, const float *a0, int lda0, int c0, const float *a1, int lda1, int c1,
+                       const float *wp, const float *bias, int B, int H, int W, int npad, int nvalid, int act, float scale,
+                       float *out, int ldo, void *stream, int hint) {
+    RAFT_REQUIRE_PTR(a0);
+    RAFT_REQUIRE_PTR(wp);
+    RAFT_REQUIRE_PTR(bias);
+    RAFT_REQUIRE_PTR(out);
+    RAFT_REQUIRE(c1 == 0 || a1 != nullptr, RAFT_E_NULL);
+    RAFT_REQUIRE(B > 0 && H > 0 && W > 0 && nvalid > 0 && nvalid <= npad && ldo >= nvalid, RAFT_E_SHAPE);
+    RAFT_REQUIRE(lda0 >= c0 && (c1 == 0 || lda1 >= c1), RAFT_E_SHAPE);
+    RAFT_REQUIRE(act == RAFT_ACT_NONE || act == RAFT_ACT_RELU, RAFT_E_UNSUPPORTED);
+    ConvArgs a = {};
+    a.a0 = a0; a.a1 = a1; a.lda0 = lda0; a.lda1 = lda1; a.c0 = c0; a.c1 = c1;
+    a.wp = wp; a.bias = bias; a.B = B; a.H = H; a.W = W;
+    a.npad = npad; a.nvalid = nvalid; a.hid = 0; a.scale = scale;
+    a.o0 = out; a.ldo0 = ldo;
+    const int epi = act == RAFT_ACT_RELU ? EPI_RELU : EPI_LINEAR;
+    hipStream_t s = (hipStream_t)stream;
+    switch (family) {
+        case RAFT_FAM_WINO: return raft_launch_conv_wino(a, epi, s, raft_wino_plan(B, H, W, c0, c1, npad, true, hint));
+        case RAFT_FAM_WINO4: return raft_launch_conv_wino4(a, epi, s, raft_wino4_plan(B, H, W, c0, c1, npad, true, hint));
+        case RAFT_FAM_WINO1D: return raft_launch_conv_wino1d(a, kh, kw, epi, s, raft_wino1d_plan(B, H, W, c0, c1, npad, kh, mo, hint));
+    }
+    return raft_launch_conv(a, kh, kw, epi, s, raft_halo_plan(B, H, W, npad, kh, kw, hint));
 }
 
 extern "C" int raft_conv2d_f32(const float *a0, int lda0, int c0, const float *a1, int lda1, int c1,
                                const float *wp, const float *bias, int B, int H, int W, int kh, int kw, int npad,
                                int nvalid, int act, float scale, float *out, int ldo, void *stream) {
-    RAFT_REQUIRE_PTR(a0);
-    RAFT_REQUIRE_PTR(wp);
-    RAFT_REQUIRE_PTR(bias);
-    RAFT_REQUIRE_PTR(out);
-    RAFT_REQUIRE(c1 == 0 || a1 != nullptr, RAFT_E_NULL);
-    RAFT_REQUIRE(B > 0 && H > 0 && W > 0 && nvalid > 0 && nvalid <= npad && ldo >= nvalid, RAFT_E_SHAPE);
-    RAFT_REQUIRE(lda0 >= c0 && (c1 == 0 || lda1 >= c1), RAFT_E_SHAPE);
-    RAFT_REQUIRE(act == RAFT_ACT_NONE || act == RAFT_ACT_RELU, RAFT_E_UNSUPPORTED);
-    ConvArgs a = {};
-    a.a0 = a0; a.a1 = a1; a.lda0 = lda0; a.lda1 = lda1; a.c0 = c0; a.c1 = c1;
-    a.wp = wp; a.bias = bias; a.B = B; a.H = H; a.W = W;
-    a.npad = npad; a.nvalid = nvalid; a.hid = 0; a.scale = scale;
-    a.o0 = out; a.ldo0 = ldo;
-    return raft_launch_conv(a, kh, kw, act == RAFT_ACT_RELU ? EPI_RELU : EPI_LINEAR, (hipStream_t)stream);
+    return single_conv(RAFT_FAM_HALO, kh, kw, 0, a0, lda0, c0, a1, lda1, c1, wp, bias, B, H, W, npad, nvalid, act, scale, out, ldo,
+                       stream, raft_concurrency());
 }
 
 extern "C" int raft_conv2d_winograd_f32(const float *a0, int lda0, int c0, const float *a1, int lda1, int c1,
                                         const float *wp, const float *bias, int B, int H, int W, int npad, int nvalid,
                                         int act, float scale, float *out, int ldo, void *stream) {
-    RAFT_REQUIRE_PTR(a0);
-    RAFT_REQUIRE_PTR(wp);
-    RAFT_REQUIRE_PTR(bias);
-    RAFT_REQUIRE_PTR(out);
-    RAFT_REQUIRE(c1 == 0 || a1 != nullptr, RAFT_E_NULL);
-    RAFT_REQUIRE(B > 0 && H > 0 && W > 0 && nvalid > 0 && nvalid <= npad && ldo >= nvalid, RAFT_E_SHAPE);
-    RAFT_REQUIRE(lda0 >= c0 && (c1 == 0 || lda1 >= c1), RAFT_E_SHAPE);
-    RAFT_REQUIRE(act == RAFT_ACT_NONE || act == RAFT_ACT_RELU, RAFT_E_UNSUPPORTED);
-    ConvArgs a = {};
-    a.a0 = a0; a.a1 = a1; a.lda0 = lda0; a.lda1 = lda1; a.c0 = c0; a.c1 = c1;
-    a.wp = wp; a.bias = bias; a.B = B; a.H = H; a.W = W;
-    a.npad = npad; a.nvalid = nvalid; a.hid = 0; a.scale = scale;
-    a.o0 = out; a.ldo0 = ldo;
-    return raft_launch_conv_wino(a, act == RAFT_ACT_RELU ? EPI_RELU : EPI_LINEAR, (hipStream_t)stream);
+    return single_conv(RAFT_FAM_WINO, 3, 3, 0, a0, lda0, c0, a1, lda1, c1, wp, bias, B, H, W, npad, nvalid, act, scale, out, ldo,
+                       stream, raft_concurrency());
 }
 
 extern "C" int raft_conv2d_winograd4_f32(const float *a0, int lda0, int c0, const float *a1, int lda1, int c1,
                                          const float *wp, const float *bias, int B, int H, int W, int npad, int nvalid,
                                          int act, float scale, float *out, int ldo, void *stream) {
-    RAFT_REQUIRE_PTR(a0);
-    RAFT_REQUIRE_PTR(wp);
-    RAFT_REQUIRE_PTR(bias);
-    RAFT_REQUIRE_PTR(out);
-    RAFT_REQUIRE(c1 == 0 || a1 != nullptr, RAFT_E_NULL);
-    RAFT_REQUIRE(B > 0 && H > 0 && W > 0 && nvalid > 0 && nvalid <= npad && ldo >= nvalid, RAFT_E_SHAPE);
-    RAFT_REQUIRE(lda0 >= c0 && (c1 == 0 || lda1 >= c1), RAFT_E_SHAPE);
-    RAFT_REQUIRE(act == RAFT_ACT_NONE || act == RAFT_ACT_RELU, RAFT_E_UNSUPPORTED);
-    ConvArgs a = {};
-    a.a0 = a0; a.a1 = a1; a.lda0 = lda0; a.lda1 = lda1; a.c0 = c0; a.c1 = c1;
-    a.wp = wp; a.bias = bias; a.B = B; a.H = H; a.W = W;
-    a.npad = npad; a.nvalid = nvalid; a.hid = 0; a.scale = scale;
-    a.o0 = out; a.ldo0 = ldo;
-    return raft_launch_conv_wino4(a, act == RAFT_ACT_RELU ? EPI_RELU : EPI_LINEAR, (hipStream_t)stream);
-}
-
-static int conv1d_winograd(int mo, const float *a0, int lda0, int c0, const float *a1, int lda1, int c1,
-                           const float *wp, const float *bias, int B, int H, int W, int kh, int kw,
-                           int npad, int nvalid, int act, float scale, float *out, int ldo, void *stream) {
-    RAFT_REQUIRE_PTR(a0);
-    RAFT_REQUIRE_PTR(wp);
-    RAFT_REQUIRE_PTR(bias);
-    RAFT_REQUIRE_PTR(out);
-    RAFT_REQUIRE(c1 == 0 || a1 != nullptr, RAFT_E_NULL);
-    RAFT_REQUIRE(B > 0 && H > 0 && W > 0 && nvalid > 0 && nvalid <= npad && ldo >= nvalid, RAFT_E_SHAPE);
-    RAFT_REQUIRE(lda0 >= c0 && (c1 == 0 || lda1 >= c1), RAFT_E_SHAPE);
-    RAFT_REQUIRE(act == RAFT_ACT_NONE || act == RAFT_ACT_RELU, RAFT_E_UNSUPPORTED);
-    ConvArgs a = {};
-    a.a0 = a0; a.a1 = a1; a.lda0 = lda0; a.lda1 = lda1; a.c0 = c0; a.c1 = c1;
-    a.wp = wp; a.bias = bias; a.B = B; a.H = H; a.W = W;
-    a.npad = npad; a.nvalid = nvalid; a.hid = 0; a.scale = scale;
-    a.o0 = out; a.ldo0 = ldo;
-    return raft_launch_conv_wino1d(a, kh, kw, act == RAFT_ACT_RELU ? EPI_RELU : EPI_LINEAR, (hipStream_t)stream, mo);
+    return single_conv(RAFT_FAM_WINO4, 3, 3, 0, a0, lda0, c0, a1, lda1, c1, wp, bias, B, H, W, npad, nvalid, act, scale, out, ldo,
+                       stream, raft_concurrency());
 }
 
 extern "C" int raft_conv1d_winograd_f32(const float *a0, int lda0, int c0, const float *a1, int lda1, int c1,
                                         const float *wp, const float *bias, int B, int H, int W, int kh, int kw,
                                         int npad, int nvalid, int act, float scale, float *out, int ldo, void *stream) {
-    return conv1d_winograd(2, a0, lda0, c0, a1, lda1, c1, wp, bias, B, H, W, kh, kw, npad, nvalid, act, scale, out, ldo, stream);
+    return single_conv(RAFT_FAM_WINO1D, kh, kw, 2, a0, lda0, c0, a1, lda1, c1, wp, bias, B, H, W, npad, nvalid, act, scale, out, ldo,
+                       stream, raft_concurrency());
 }
 
 extern "C" int raft_conv1d_winograd4_f32(const float *a0, int lda0, int c0, const float *a1, int lda1, int c1,
                                          const float *wp, const float *bias, int B, int H, int W, int kh, int kw,
                                          int npad, int nvalid, int act, float scale, float *out, int ldo, void *stream) {
-    return conv1d_winograd(4, a0, lda0, c0, a1, lda1, c1, wp, bias, B, H, W, kh, kw, npad, nvalid, act, scale, out, ldo, stream);
+    return single_conv(RAFT_FAM_WINO1D, kh, kw, 4, a0, lda0, c0, a1, lda1, c1, wp, bias, B, H, W, npad, nvalid, act, scale, out, ldo,
+                       stream, raft_concurrency());
 }
 
-// The per-iteration SepConvGRU convolutions: direct halo kernel or 1-D Winograd F(2, 5) / F(4, 5) (conv_wino1d.h).
-// RAFT_GRU_WINO and RAFT_GRU_WINO4 are bit masks over {1: gru_zr1, 2: gru_q1, 4: gru_zr2, 8: gru_q2}; a layer runs
-// F(4, 5) if its WINO4 bit is set and the 8-tap weights were supplied, else F(2, 5) if its WINO bit is set and the
-// 6-tap weights were supplied, else the direct kernel.  Unset = the defaults below.
-constexpr int RAFT_GRU_WINO_DEFAULT = 15;
-constexpr int RAFT_GRU_WINO4_DEFAULT = 15;
-static int launch_gru_conv(const raft_conv_weights &direct, const raft_conv_weights &wino, const raft_conv_weights &wino4,
-                           int bit, ConvArgs a, int kh, int kw, int epi, hipStream_t s) {
-    const int mask = raft_opt(RAFT_OPT_GRU_WINO, RAFT_GRU_WINO_DEFAULT);
-    // F(4, 5) wins where the launch fills the chip; below ~2 x 3584 pixels (the reference's single 448 x 512 pair) every
-    // kernel is one under-filled round of workgroups and the F(2, 5) kernel's smaller workgroups finish sooner
-    // (B = 1: 8.69 -> 8.40 ms per forward, profiles/r05d_b1_probe.txt)
-    const int mask4 = raft_opt(RAFT_OPT_GRU_WINO4, (int64_t)a.B * a.H * a.W * raft_concurrency() < 2 * 3584 ? 0 : RAFT_GRU_WINO4_DEFAULT);
-    if ((mask4 & bit) && wino4.wp != nullptr && a.c0 % 32 == 0 && a.c1 % 32 == 0) {
-        a.wp = wino4.wp;
-        a.bias = wino4.bias;
-        a.npad = wino4.npad;
-        return raft_launch_conv_wino1d(a, kh, kw, epi, s, 4, 0);   // workgroup width by grid size (a forced 32- / 64-channel width for gru_q lost to it: profiles/r09q_gru_q_tnw.txt)
+// One layer of a loop plan: the weight copy of the chosen family, its launcher.
+static int launch_layer(const ConvChoice &c, ConvArgs a, int kh, int kw, int epi, hipStream_t s) {
+    a.wp = c.wt->wp;
+    a.bias = c.wt->bias;
+    a.npad = c.wt->npad;
+    switch (c.family) {
+        case RAFT_FAM_WINO: return raft_launch_conv_wino(a, epi, s, c.wino);
+        case RAFT_FAM_WINO1D: return raft_launch_conv_wino1d(a, kh, kw, epi, s, c.wino1d);
+        case RAFT_FAM_WINO4: return raft_launch_conv_wino4(a, epi, s, c.wino4);
     }
-    if ((mask & bit) && wino.wp != nullptr) {
-        a.wp = wino.wp;
-        a.bias = wino.bias;
-        a.npad = wino.npad;
-        return raft_launch_conv_wino1d(a, kh, kw, epi, s);
-    }
-    a.wp = direct.wp;
-    a.bias = direct.bias;
-    a.npad = direct.npad;
-    return raft_launch_conv(a, kh, kw, epi, s);
-}
-
-// The 3x3 layers of the update block run either on the direct halo kernel or on the Winograd F(2x2, 3x3) kernel
-// (conv_wino.h) when the caller supplied transformed weights.  RAFT_CONV_WINO is a bit mask over
-// {1: convc2, 2: convf2, 4: conv, 8: fh1_mask0}; unset = RAFT_WINO_DEFAULT (the layers where it measured faster at
-// B = 4, docs/NOTEBOOK.md section 4.4).  Read per call so that tests can switch it.
-constexpr int RAFT_WINO_DEFAULT = 13;
-constexpr int RAFT_SMALL_WINO_DEFAULT = 15;   // SmallRAFT: {1: conv, 2: gru_zr, 4: gru_q, 8: fh1}, switch RAFT_SMALL_WINO
-// F(4x4, 3x3) (conv_wino4.h), switch RAFT_CONV_WINO4 = bit mask {1: convc2, 4: conv, 8: fh1_mask0 / fh1}.  Default (us alone,
-// F(4x4) against F(2x2), profiles/r07i_wino4_bench.txt): from 4 pairs on the flow / mask head (63 vs 91 at 4 pairs, 128 vs 169 at
-// 8) and convc2 (61 vs 76 with the K-split workgroups, 107 vs 132); conv (N = 128) from 8 pairs on (65 vs 114; at 4 pairs its
-// 112 K-split workgroups lose to F(2x2): 59 vs 49).  A single pair nothing: a launch is then one round of workgroups whose
-// duration is one workgroup's K loop, and the one-wave-per-SIMD F(4x4) workgroup is the longer one (single pair: 151 pairs/s
-// without, 133 with -- same-box A/B with bench.py, profiles/r07p_bench_mask_ab.txt: 4 pairs 270 -> 282, 8 pairs 285 -> 296);
-// at two pairs the flow / mask head alone gains (206 -> 221 pairs/s with mask 8 on two boxes; with convc2 as well 214 and one
-// outlier of 235: profiles/r08k_round3_options.txt, r08z_b2_options.txt).
-// Bit 2 = convf2 (3x3, 128 -> 64), with convc2 from 3 pairs on: alone its 56 K-split workgroups (4 pairs) are slower than the direct kernel's
-// 224 (42 against 27 us), but they take a quarter of the CU-time and, with 108 KB of LDS each, settle on CUs of their own: in the
-// three-stream loop convc2's 168 K-split workgroups + these 56 + the 32 of the background mask branch are exactly 256 -- the flow
-// branch no longer competes with convc2, which can have its faster shape back (one process, profiles/r09i_b4_options3.txt:
-// 303.1 pairs/s -> 325.9 at 4 pairs; with convc2 on 8-row workgroups 303.3; 8 pairs 345.0 -> 353.3).
-static int wino4_default_mask(const ConvArgs &a) {
-    const int64_t m = (int64_t)a.B * a.H * a.W * raft_concurrency();   // loops sharing the chip fill it like one loop of n times the batch
-    return m < 2 * 3584 ? 0 : (8 | (m >= 3 * 3584 ? 1 | 2 : 0) | (m >= 8 * 3584 ? 4 : 0));   // three pairs: 250 -> 262 pairs/s with 11, two: 237 -> 231
-}
-static int launch_conv3x3(const raft_conv_weights &direct, const raft_conv_weights &wino, int bit, ConvArgs a, int epi,
-                          hipStream_t s, bool small = false, const raft_conv_weights *wino44 = nullptr, int w4_ks_hint = 0) {
-    const int mask = small ? raft_opt(RAFT_OPT_SMALL_WINO, RAFT_SMALL_WINO_DEFAULT) : raft_opt(RAFT_OPT_CONV_WINO, RAFT_WINO_DEFAULT);
-    if (wino44 != nullptr && wino44->wp != nullptr && (raft_opt(RAFT_OPT_CONV_WINO4, wino4_default_mask(a)) & bit) &&
-        (epi == EPI_LINEAR || epi == EPI_RELU || epi == EPI_RES)) {
-        a.wp = wino44->wp;
-        a.bias = wino44->bias;
-        a.npad = wino44->npad;
-        return raft_launch_conv_wino4(a, epi, s, 0, w4_ks_hint);
-    }
-    if ((mask & bit) && wino.wp != nullptr) {
-        a.wp = wino.wp;
-        a.bias = wino.bias;
-        a.npad = wino.npad;
-        return raft_launch_conv_wino(a, epi, s);
-    }
-    a.wp = direct.wp;
-    a.bias = direct.bias;
-    a.npad = direct.npad;
-    return raft_launch_conv(a, 3, 3, epi, s);
+    return raft_launch_conv(a, kh, kw, epi, s, c.halo);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -539,7 +376,8 @@ extern "C" int64_t raft_update_workspace_floats(int B, int h, int w) {
     return (int64_t)B * h * w * WS_PER_PIX;
 }
 
-static int check_state(const raft_state *st) {
+// small = true: the SmallUpdateBlock's state (no mask, no GRU context)
+static int check_state(const raft_state *st, bool small = false) {
     RAFT_REQUIRE_PTR(st);
     RAFT_REQUIRE_PTR(st->net);
     RAFT_REQUIRE_PTR(st->x);
@@ -547,9 +385,8 @@ static int check_state(const raft_state *st) {
     RAFT_REQUIRE_PTR(st->coords1);
     RAFT_REQUIRE_PTR(st->flow);
     RAFT_REQUIRE_PTR(st->delta);
-    RAFT_REQUIRE_PTR(st->mask);
     RAFT_REQUIRE_PTR(st->ws);
-    RAFT_REQUIRE_PTR(st->ctx);
+    RAFT_REQUIRE(small || (st->mask != nullptr && st->ctx != nullptr), RAFT_E_NULL);
     return RAFT_OK;
 }
 
@@ -584,17 +421,12 @@ extern "C" int raft_gru_context_f32(const raft_basic_update_weights *wts, int B,
     RAFT_REQUIRE_PTR(wts);
     RAFT_TRY(check_state(st));
     RAFT_REQUIRE(B > 0 && h > 0 && w > 0, RAFT_E_SHAPE);
+    const int hint = raft_concurrency();
     for (int pass = 0; pass < 2; ++pass) {
-        const raft_conv_weights &wc = pass == 0 ? wts->gru_ctx1 : wts->gru_ctx2;
-        const raft_conv_weights &w4 = pass == 0 ? wts->gru_ctx1_w4 : wts->gru_ctx2_w4;
         const int kh = pass == 0 ? 1 : 5, kw = pass == 0 ? 5 : 1;
-        // F(4, 5) like the per-iteration GRU convolutions (same switch: bit 1 / 4 of RAFT_GRU_WINO4 = the pass)
-        const bool wino = w4.wp != nullptr && (raft_opt(RAFT_OPT_GRU_WINO4, RAFT_GRU_WINO4_DEFAULT) & (pass == 0 ? 1 : 4));
-        ConvArgs a = conv_args(wino ? w4 : wc, st->x, XDIM, CDIM, nullptr, 0, 0, B, h, w, 3 * HDIM, st->ctx + pass * 3 * HDIM, CTX_LD);
-        if (wino)
-            RAFT_TRY(raft_launch_conv_wino1d(a, kh, kw, EPI_LINEAR, (hipStream_t)stream, 4));
-        else
-            RAFT_TRY(raft_launch_conv(a, kh, kw, EPI_LINEAR, (hipStream_t)stream));
+        const raft_conv_weights &wc = pass == 0 ? wts->gru_ctx1 : wts->gru_ctx2;
+        ConvArgs a = conv_args(wc, st->x, XDIM, CDIM, nullptr, 0, 0, B, h, w, 3 * HDIM, st->ctx + pass * 3 * HDIM, CTX_LD);
+        RAFT_TRY(launch_layer(raft_gru_ctx_plan(*wts, pass, B, h, w, hint), a, kh, kw, EPI_LINEAR, (hipStream_t)stream));
     }
     return RAFT_OK;
 }
@@ -654,15 +486,9 @@ struct Overlap {
     } while (0)
 
 // with_mask = false (final-only prediction, every iteration but the last): the mask branch -- mask.0 (the second half of
-// fh1_mask0) and mask.2 -- is skipped; flow_head.conv1 alone runs from wts->fh1_w.
-// The loops run the lookup fused into convc1 (raft_lookup_convc1_f32) when they read a stored volume, the repacked
-// kernel was supplied and RAFT_LOOKUP_FUSED is not switched off.
-static bool lookup_is_fused(const raft_basic_update_weights *wts, const LookupSource *src) {
-    return src && src->pyr && wts->convc1_f.wp != nullptr && raft_opt(RAFT_OPT_LOOKUP_FUSED, 1) != 0;
-}
-
+// fh1_mask0) and mask.2 -- is skipped; flow_head.conv1 alone runs from wts->fh1_w / fh1_w44 (plan.fh1).
 // fused_src != NULL: st->corr is NOT read; cor1 comes from the volume through the fused kernel
-static int update_basic_impl(const raft_basic_update_weights *wts, int B, int h, int w, const raft_state *st,
+static int update_basic_impl(const raft_basic_update_weights *wts, const BasicLoopPlan &plan, int B, int h, int w, const raft_state *st,
                              void *stream, StageTimer *tm, Overlap *ov = nullptr, bool with_mask = true,
                              const LookupSource *fused_src = nullptr, float *flow_up_fused = nullptr) {
     RAFT_REQUIRE_PTR(wts);
@@ -685,17 +511,12 @@ static int update_basic_impl(const raft_basic_update_weights *wts, int B, int h,
         RAFT_MARK();
     } else {   // cor = relu(convc1(corr))            1x1, 324(+28 zero pad) -> 256
         ConvArgs a = conv_args(wts->convc1, st->corr, CORR_LD, CORR_LD, nullptr, 0, 0, B, h, w, 256, cor1, 256);
-        RAFT_TRY(raft_launch_conv(a, 1, 1, EPI_RELU, s));
+        RAFT_TRY(launch_layer(plan.convc1, a, 1, 1, EPI_RELU, s));
         RAFT_MARK();
     }
     {   // cor = relu(convc2(cor))             3x3, 256 -> 192   -> corflo[:, 0:192]
         ConvArgs a = conv_args(wts->convc2, cor1, 256, 256, nullptr, 0, 0, B, h, w, 192, corflo, 256);
-        // F(4x4) workgroup shape: the launcher's grid rule (K-split 4-row workgroups while 8-row ones would be fewer than 128: 168
-        // instead of 84 at 4 pairs).  While the flow branch ran the direct convf2 (224 workgroups competing for the same CUs) the
-        // 8-row shape was the better one in the loop (288.7 -> 293.7 pairs/s: less CU-time, room for the side branches,
-        // profiles/r08n_b4_options.txt); with convf2 on its own 56 CUs (wino4_default_mask) the K-split shape wins by 7 %.
-        // RAFT_CONVC2_KS = 1 / 2 forces either; every loop uses the same shape (the loops stay bit-identical to each other).
-        RAFT_TRY(launch_conv3x3(wts->convc2, wts->convc2_w, 1, a, EPI_RELU, s, false, &wts->convc2_w44, raft_opt(RAFT_OPT_CONVC2_KS, 0)));
+        RAFT_TRY(launch_layer(plan.convc2, a, 3, 3, EPI_RELU, s));
         RAFT_MARK();
     }
     if (ov) RAFT_HIP(hipStreamWaitEvent(sf, ov->e_fh, 0));   // flow of the previous iteration is final
@@ -707,11 +528,7 @@ static int update_basic_impl(const raft_basic_update_weights *wts, int B, int h,
     }
     {   // flo = relu(convf2(flo))             3x3, 128 -> 64    -> corflo[:, 192:256]
         ConvArgs a = conv_args(wts->convf2, flo1, 128, 128, nullptr, 0, 0, B, h, w, 64, corflo + 192, 256);
-        // F(4x4) shape: K-split workgroups up to 4 pairs (28 eight-row workgroups -> 56), eight-row ones from 56 on (8 pairs:
-        // 56 of them beside convc2's 168 and the mask branch's 32: 353.4 -> 356.1 pairs/s, profiles/r09k_b8_options.txt)
-        const int f2_grid1 = B * ((h + 7) / 8) * ((w + 63) / 64);
-        RAFT_TRY(launch_conv3x3(wts->convf2, wts->convf2_w, 2, a, EPI_RELU, sf, false, &wts->convf2_w44,
-                                raft_opt(RAFT_OPT_CONVF2_KS, f2_grid1 * raft_concurrency() >= 56 ? 1 : 0)));
+        RAFT_TRY(launch_layer(plan.convf2, a, 3, 3, EPI_RELU, sf));
         RAFT_MARK();
     }
     if (ov) {
@@ -720,44 +537,37 @@ static int update_basic_impl(const raft_basic_update_weights *wts, int B, int h,
     }
     {   // out = relu(conv(cat[cor, flo]))     3x3, 256 -> 126   -> x[:, 128:254]; x[:, 254:256] = flow (kept by flowhead2)
         ConvArgs a = conv_args(wts->conv, corflo, 256, 256, nullptr, 0, 0, B, h, w, 126, st->x + 128, XDIM);
-        RAFT_TRY(launch_conv3x3(wts->conv, wts->conv_w, 4, a, EPI_RELU, s, false, &wts->conv_w44));
+        RAFT_TRY(launch_layer(plan.conv, a, 3, 3, EPI_RELU, s));
         RAFT_MARK();
     }
     // ---- SepConvGRU (update.py:51-67): hx = [h | x]; [r*h | x]
     for (int pass = 0; pass < 2; ++pass) {
-        const raft_conv_weights &wzr = pass == 0 ? wts->gru_zr1 : wts->gru_zr2;
-        const raft_conv_weights &wq = pass == 0 ? wts->gru_q1 : wts->gru_q2;
-        const raft_conv_weights &wzr_w = pass == 0 ? wts->gru_zr1_w : wts->gru_zr2_w;
-        const raft_conv_weights &wq_w = pass == 0 ? wts->gru_q1_w : wts->gru_q2_w;
-        const raft_conv_weights &wzr_w4 = pass == 0 ? wts->gru_zr1_w4 : wts->gru_zr2_w4;
-        const raft_conv_weights &wq_w4 = pass == 0 ? wts->gru_q1_w4 : wts->gru_q2_w4;
         const int kh = pass == 0 ? 1 : 5, kw = pass == 0 ? 5 : 1;
         const float *xm = st->x + CDIM;                      // [motion | flow]; the inp rows live in st->ctx
         const float *ctx = st->ctx + pass * 3 * HDIM;        // [z | r | q] context of this pass
         {
-            ConvArgs a = conv_args(wzr, st->net, HDIM, HDIM, xm, XDIM, XDIM - CDIM, B, h, w, 2 * HDIM, zb, HDIM);
+            ConvArgs a = conv_args(*plan.gru[2 * pass].wt, st->net, HDIM, HDIM, xm, XDIM, XDIM - CDIM, B, h, w, 2 * HDIM, zb, HDIM);
             a.hid = HDIM; a.o1 = rh; a.ldo1 = HDIM; a.e0 = st->net; a.lde0 = HDIM;
             a.init = ctx; a.ldi = CTX_LD;
-            RAFT_TRY(launch_gru_conv(wzr, wzr_w, wzr_w4, pass == 0 ? 1 : 4, a, kh, kw, EPI_GRU_ZR, s));
+            RAFT_TRY(launch_layer(plan.gru[2 * pass], a, kh, kw, EPI_GRU_ZR, s));
             RAFT_MARK();
         }
         {
-            ConvArgs a = conv_args(wq, rh, HDIM, HDIM, xm, XDIM, XDIM - CDIM, B, h, w, HDIM, st->net, HDIM);
+            ConvArgs a = conv_args(*plan.gru[2 * pass + 1].wt, rh, HDIM, HDIM, xm, XDIM, XDIM - CDIM, B, h, w, HDIM, st->net, HDIM);
             a.e0 = st->net; a.lde0 = HDIM; a.e1 = zb; a.lde1 = HDIM;
             a.init = ctx + 2 * HDIM; a.ldi = CTX_LD;
-            RAFT_TRY(launch_gru_conv(wq, wq_w, wq_w4, pass == 0 ? 2 : 8, a, kh, kw, EPI_GRU_Q, s));
+            RAFT_TRY(launch_layer(plan.gru[2 * pass + 1], a, kh, kw, EPI_GRU_Q, s));
             RAFT_MARK();
         }
     }
     if (ov && ov->have_up && !rot) RAFT_HIP(hipStreamWaitEvent(s, ov->e_up, 0));   // mask2 / upsample of the previous iteration
     if (with_mask) {   // relu(flow_head.conv1(net)) | relu(mask.0(net))   3x3, 128 -> 256 + 256
         ConvArgs a = conv_args(wts->fh1_mask0, st->net, HDIM, HDIM, nullptr, 0, 0, B, h, w, 512, fm, 512);
-        RAFT_TRY(launch_conv3x3(wts->fh1_mask0, wts->fh1_mask0_w, 8, a, EPI_RELU, s, false, &wts->fh1_mask0_w44));
+        RAFT_TRY(launch_layer(plan.fh1_mask0, a, 3, 3, EPI_RELU, s));
         RAFT_MARK();
     } else {           // relu(flow_head.conv1(net)) only            3x3, 128 -> 256        -> fm[:, 0:256]
-        const bool w44 = wts->fh1_w44.wp != nullptr && (raft_opt(RAFT_OPT_CONV_WINO4, (int64_t)B * h * w * raft_concurrency() < 2 * 3584 ? 0 : 8) & 8);
-        ConvArgs a = conv_args(w44 ? wts->fh1_w44 : wts->fh1_w, st->net, HDIM, HDIM, nullptr, 0, 0, B, h, w, 256, fm, 512);
-        RAFT_TRY(w44 ? raft_launch_conv_wino4(a, EPI_RELU, s, wts->fh1_mask0_w44.npad) : raft_launch_conv_wino(a, EPI_RELU, s, wts->fh1_mask0_w.npad));
+        ConvArgs a = conv_args(wts->fh1_w, st->net, HDIM, HDIM, nullptr, 0, 0, B, h, w, 256, fm, 512);
+        RAFT_TRY(launch_layer(plan.fh1, a, 3, 3, EPI_RELU, s));
     }
     if (ov && with_mask && flow_up_fused == nullptr) {   // two-kernel mask branch: mask.2 may start before fh2
         RAFT_HIP(hipEventRecord(ov->e_fm, s));
@@ -780,7 +590,7 @@ static int update_basic_impl(const raft_basic_update_weights *wts, int B, int h,
     } else if (with_mask) {   // mask = 0.25 * mask.2(.)             1x1, 256 -> 576
         ConvArgs a = conv_args(wts->mask2, fm + 256, 512, 256, nullptr, 0, 0, B, h, w, 576, st->mask, 576);
         a.scale = 0.25f;
-        RAFT_TRY(raft_launch_conv(a, 1, 1, EPI_LINEAR, sm));
+        RAFT_TRY(launch_layer(plan.mask2, a, 1, 1, EPI_LINEAR, sm));
         RAFT_MARK();
     }
     return RAFT_OK;
@@ -788,7 +598,8 @@ static int update_basic_impl(const raft_basic_update_weights *wts, int B, int h,
 
 extern "C" int raft_update_basic_f32(const raft_basic_update_weights *wts, int B, int h, int w,
                                      const raft_state *st, void *stream) {
-    return update_basic_impl(wts, B, h, w, st, stream, nullptr);
+    RAFT_REQUIRE_PTR(wts);
+    return update_basic_impl(wts, raft_basic_loop_plan(*wts, B, h, w, false, raft_concurrency()), B, h, w, st, stream, nullptr);
 }
 
 extern "C" int raft_iterate_basic_f32(const raft_basic_update_weights *wts, const float *pyr,
@@ -802,11 +613,11 @@ extern "C" int raft_iterate_basic_f32(const raft_basic_update_weights *wts, cons
     RAFT_REQUIRE(B > 0 && h > 0 && w > 0 && iters > 0, RAFT_E_SHAPE);
     const int64_t up = (int64_t)B * 64 * h * w * 2;
     const LookupSource src = {pyr, level_offsets, nullptr, nullptr, 0};
-    const bool fused = lookup_is_fused(wts, &src);
+    const BasicLoopPlan plan = raft_basic_loop_plan(*wts, B, h, w, true, raft_concurrency());
+    const bool fused = plan.lookup_fused, mf = plan.mask_fused;
     for (int i = 0; i < iters; ++i) {
         if (!fused) RAFT_TRY(raft_corr_lookup_f32(pyr, level_offsets, st->coords1, B, h, w, 4, 4, st->corr, CORR_LD, stream));
-        const bool mf = mask_is_fused(wts, (int64_t)B * h * w);
-        RAFT_TRY(update_basic_impl(wts, B, h, w, st, stream, nullptr, nullptr, true, fused ? &src : nullptr, mf ? flow_up + i * up : nullptr));
+        RAFT_TRY(update_basic_impl(wts, plan, B, h, w, st, stream, nullptr, nullptr, true, fused ? &src : nullptr, mf ? flow_up + i * up : nullptr));
         if (!mf) RAFT_TRY(raft_upsample_convex_f32(st->flow, st->mask, B, h, w, flow_up + i * up, stream));
     }
     return RAFT_OK;
@@ -826,7 +637,7 @@ struct raft_loop_ctx {
 
 static int iterate_basic_overlap_impl(const raft_basic_update_weights *wts, const LookupSource &src, int B, int h, int w,
                                       int iters, const raft_state *st, float *flow_up, void *stream, void *aux0, void *aux1,
-                                      raft_loop_ctx *ctx, bool final_only = false);
+                                      raft_loop_ctx *ctx, int hint, bool final_only = false);
 
 extern "C" int raft_loop_ctx_create(raft_loop_ctx **out) {
     RAFT_REQUIRE_PTR(out);
@@ -867,7 +678,7 @@ extern "C" int raft_iterate_basic_overlap_f32(const raft_basic_update_weights *w
     RAFT_REQUIRE_PTR(pyr);
     RAFT_REQUIRE_PTR(level_offsets);
     const LookupSource src = {pyr, level_offsets, nullptr, nullptr, 0};
-    return iterate_basic_overlap_impl(wts, src, B, h, w, iters, st, flow_up, stream, aux0, aux1, ctx);
+    return iterate_basic_overlap_impl(wts, src, B, h, w, iters, st, flow_up, stream, aux0, aux1, ctx, raft_concurrency());
 }
 
 // The same three-stream loop with the volume-free ("alternate") correlation: every iteration's lookup computes its
@@ -879,7 +690,7 @@ extern "C" int raft_iterate_basic_ondemand_f32(const raft_basic_update_weights *
     RAFT_REQUIRE_PTR(fmap1);
     RAFT_REQUIRE_PTR(fmap2_pyr);
     const LookupSource src = {nullptr, nullptr, fmap1, fmap2_pyr, C};
-    return iterate_basic_overlap_impl(wts, src, B, h, w, iters, st, flow_up, stream, aux0, aux1, ctx);
+    return iterate_basic_overlap_impl(wts, src, B, h, w, iters, st, flow_up, stream, aux0, aux1, ctx, raft_concurrency());
 }
 
 // The prediction loop for callers that only want flow_predictions[-1] (reference model.py:160-166, predict_step): the
@@ -895,13 +706,14 @@ extern "C" int raft_iterate_basic_final_f32(const raft_basic_update_weights *wts
     RAFT_REQUIRE_PTR(level_offsets);
     RAFT_REQUIRE(wts->fh1_w.wp != nullptr, RAFT_E_NULL);
     const LookupSource src = {pyr, level_offsets, nullptr, nullptr, 0};
-    return iterate_basic_overlap_impl(wts, src, B, h, w, iters, st, flow_up_last, stream, aux0, aux1, ctx, true);
+    return iterate_basic_overlap_impl(wts, src, B, h, w, iters, st, flow_up_last, stream, aux0, aux1, ctx, raft_concurrency(), true);
 }
 
 // Enqueue the whole loop on `stream` + the two side streams.
-static int enqueue_loop(const raft_basic_update_weights *wts, const LookupSource &src, int B, int h, int w, int iters,
-                        const raft_state *st, float *flow_up, void *stream, void *aux0, void *aux1, raft_loop_ctx *ctx,
-                        bool final_only) {
+static int enqueue_loop(const raft_basic_update_weights *wts, const BasicLoopPlan &plan, const LookupSource &src, int B, int h,
+                        int w, int iters, const raft_state *st, float *flow_up, void *stream, void *aux0, void *aux1,
+                        raft_loop_ctx *ctx, bool final_only) {
+    const bool fused = plan.lookup_fused;
     hipStream_t s = (hipStream_t)stream;
     if (aux0 == stream) {
         // single-stream schedule (aux0 == aux1 == stream): the launches of raft_iterate_basic_f32, for every lookup source and
@@ -909,11 +721,10 @@ static int enqueue_loop(const raft_basic_update_weights *wts, const LookupSource
         const int64_t up1 = (int64_t)B * 64 * h * w * 2;
         for (int i = 0; i < iters; ++i) {
             const bool with_mask = !final_only || i == iters - 1;
-            const bool fused = lookup_is_fused(wts, &src);
             if (!fused) RAFT_TRY(loop_lookup(src, st, B, h, w, stream));
             float *up_i = flow_up + (final_only ? 0 : i * up1);
-            const bool mf = with_mask && mask_is_fused(wts, (int64_t)B * h * w);
-            RAFT_TRY(update_basic_impl(wts, B, h, w, st, stream, nullptr, nullptr, with_mask, fused ? &src : nullptr, mf ? up_i : nullptr));
+            const bool mf = with_mask && plan.mask_fused;
+            RAFT_TRY(update_basic_impl(wts, plan, B, h, w, st, stream, nullptr, nullptr, with_mask, fused ? &src : nullptr, mf ? up_i : nullptr));
             if (with_mask && !mf) RAFT_TRY(raft_upsample_convex_f32(st->flow, st->mask, B, h, w, up_i, stream));
         }
         return RAFT_OK;
@@ -927,22 +738,21 @@ static int enqueue_loop(const raft_basic_update_weights *wts, const LookupSource
     ov.e_up = ctx->ev[3];
     ov.e_rot[0] = ctx->ev[2];   // e_fm is not used in that mode
     ov.e_rot[1] = ctx->ev[3];
-    ov.rot = !final_only && mask_is_fused(wts, (int64_t)B * h * w);
+    ov.rot = !final_only && plan.mask_fused;
     const int64_t up = (int64_t)B * 64 * h * w * 2;
     int rc = (int)hipEventRecord(ov.e_fh, s);   // state prepared on `stream`: the flow branch may start
     for (int i = 0; i < iters && rc == RAFT_OK; ++i) {
         const bool with_mask = !final_only || i == iters - 1;
-        const bool fused = lookup_is_fused(wts, &src);
         rc = fused ? RAFT_OK : loop_lookup(src, st, B, h, w, stream);
         float *up_i = flow_up + (final_only ? 0 : i * up);
-        const bool mf = with_mask && mask_is_fused(wts, (int64_t)B * h * w);
+        const bool mf = with_mask && plan.mask_fused;
         ov.iter = i;
         // default 32, except where the chain's launches cover the chip exactly (the flow / mask head's F(4x4) grid a multiple of
         // 256: a single 1024 x 1024 pair loses 6 % to a background branch); one process, profiles/r09d_mask_bg_shapes.txt:
         // 448 x 512 at 4 / 5 / 6 / 8 / 12 / 16 pairs +2.7 / +7.9 / +4.5 / +6.1 / +2.5 / +1.6 %, 16 or 40+ workgroups lose
         const int head_grid = B * ((h + 7) / 8) * ((w + 63) / 64) * 8;
         ov.mask_bg_wgs = (ov.rot && i + 1 < iters) ? (head_grid % 256 ? 32 : 0) : 0;
-        if (rc == RAFT_OK) rc = update_basic_impl(wts, B, h, w, st, stream, nullptr, &ov, with_mask, fused ? &src : nullptr, mf ? up_i : nullptr);
+        if (rc == RAFT_OK) rc = update_basic_impl(wts, plan, B, h, w, st, stream, nullptr, &ov, with_mask, fused ? &src : nullptr, mf ? up_i : nullptr);
         if (!with_mask) continue;
         if (!mf) {
             // upsample on the mask branch: needs mask2 (same stream) and the flow written by fh2
@@ -959,7 +769,7 @@ static int enqueue_loop(const raft_basic_update_weights *wts, const LookupSource
 
 static int iterate_basic_overlap_impl(const raft_basic_update_weights *wts, const LookupSource &src, int B, int h, int w,
                                       int iters, const raft_state *st, float *flow_up, void *stream, void *aux0, void *aux1,
-                                      raft_loop_ctx *ctx, bool final_only) {
+                                      raft_loop_ctx *ctx, int hint, bool final_only) {
     RAFT_REQUIRE_PTR(wts);
     RAFT_REQUIRE_PTR(flow_up);
     RAFT_REQUIRE_PTR(aux0);
@@ -969,7 +779,8 @@ static int iterate_basic_overlap_impl(const raft_basic_update_weights *wts, cons
     RAFT_REQUIRE(B > 0 && h > 0 && w > 0 && iters > 0, RAFT_E_SHAPE);
     // three distinct streams, or all three the same one (the single-stream schedule)
     RAFT_REQUIRE((aux0 != stream && aux1 != stream && aux0 != aux1) || (aux0 == stream && aux1 == stream), RAFT_E_UNSUPPORTED);
-    const int rc = enqueue_loop(wts, src, B, h, w, iters, st, flow_up, stream, aux0, aux1, ctx, final_only);
+    const BasicLoopPlan plan = raft_basic_loop_plan(*wts, B, h, w, src.pyr != nullptr, hint);
+    const int rc = enqueue_loop(wts, plan, src, B, h, w, iters, st, flow_up, stream, aux0, aux1, ctx, final_only);
     if (rc != RAFT_OK) {   // never leave side streams running behind an error return
         (void)hipStreamSynchronize((hipStream_t)aux0);
         (void)hipStreamSynchronize((hipStream_t)aux1);
@@ -1001,15 +812,15 @@ extern "C" int raft_iterate_basic_timed_f32(const raft_basic_update_weights *wts
     const int64_t up = (int64_t)B * 64 * h * w * 2;
     int rc = RAFT_OK;
     const LookupSource src = {pyr, level_offsets, nullptr, nullptr, 0};
-    const bool fused = lookup_is_fused(wts, &src);
+    const BasicLoopPlan plan = raft_basic_loop_plan(*wts, B, h, w, true, raft_concurrency());
+    const bool fused = plan.lookup_fused, mf = plan.mask_fused;
     tm.mark(s);
     for (int i = 0; i < iters && rc == RAFT_OK; ++i) {
         // RAFT_LOOKUP_FUSED as in the product loops: fused, the lookup stage is empty and the convc1 stage is the fused kernel
         if (!fused) rc = raft_corr_lookup_f32(pyr, level_offsets, st->coords1, B, h, w, 4, 4, st->corr, CORR_LD, stream);
         tm.mark(s);
         // RAFT_MASK_FUSED likewise: fused, the mask2 stage is the fused kernel and the upsampling stage is empty
-        const bool mf = mask_is_fused(wts, (int64_t)B * h * w);
-        if (rc == RAFT_OK) rc = update_basic_impl(wts, B, h, w, st, stream, &tm, nullptr, true, fused ? &src : nullptr, mf ? flow_up + i * up : nullptr);
+        if (rc == RAFT_OK) rc = update_basic_impl(wts, plan, B, h, w, st, stream, &tm, nullptr, true, fused ? &src : nullptr, mf ? flow_up + i * up : nullptr);
         if (rc == RAFT_OK && !mf) rc = raft_upsample_convex_f32(st->flow, st->mask, B, h, w, flow_up + i * up, stream);
         tm.mark(s);
     }
@@ -1043,22 +854,10 @@ extern "C" int64_t raft_small_update_workspace_floats(int B, int h, int w) {
     return (int64_t)B * h * w * SW_PER_PIX;
 }
 
-static int check_state_small(const raft_state *st) {
-    RAFT_REQUIRE_PTR(st);
-    RAFT_REQUIRE_PTR(st->net);
-    RAFT_REQUIRE_PTR(st->x);
-    RAFT_REQUIRE_PTR(st->corr);
-    RAFT_REQUIRE_PTR(st->coords1);
-    RAFT_REQUIRE_PTR(st->flow);
-    RAFT_REQUIRE_PTR(st->delta);
-    RAFT_REQUIRE_PTR(st->ws);
-    return RAFT_OK;
-}
-
 extern "C" int raft_prepare_state_small_f32(const float *cnet, int B, int h, int w, const raft_state *st,
                                             void *stream) {
     RAFT_REQUIRE_PTR(cnet);
-    RAFT_TRY(check_state_small(st));
+    RAFT_TRY(check_state(st, true));
     RAFT_REQUIRE(B > 0 && h > 0 && w > 0, RAFT_E_SHAPE);
     const int64_t total = (int64_t)B * h * w * (S_HDIM + S_CDIM);
     prepare_state_kernel<<<raft_ceil_div(total, 256), 256, 0, (hipStream_t)stream>>>(
@@ -1067,10 +866,9 @@ extern "C" int raft_prepare_state_small_f32(const float *cnet, int B, int h, int
     return raft_launch_status();
 }
 
-extern "C" int raft_update_small_f32(const raft_small_update_weights *wts, int B, int h, int w,
-                                     const raft_state *st, void *stream) {
-    RAFT_REQUIRE_PTR(wts);
-    RAFT_TRY(check_state_small(st));
+static int update_small_impl(const raft_small_update_weights *wts, const SmallLoopPlan &plan, int B, int h, int w,
+                             const raft_state *st, void *stream) {
+    RAFT_TRY(check_state(st, true));
     RAFT_REQUIRE(B > 0 && h > 0 && w > 0, RAFT_E_SHAPE);
     hipStream_t s = (hipStream_t)stream;
     const int64_t M = (int64_t)B * h * w;
@@ -1079,7 +877,7 @@ extern "C" int raft_update_small_f32(const raft_small_update_weights *wts, int B
     float *fh = ws + M * SW_FH;
     {   // cor = relu(convc1(corr))      1x1, 196(+28) -> 96     -> corflo[:, 0:96]
         ConvArgs a = conv_args(wts->convc1, st->corr, S_CORR_LD, S_CORR_LD, nullptr, 0, 0, B, h, w, 96, corflo, 128);
-        RAFT_TRY(raft_launch_conv(a, 1, 1, EPI_RELU, s));
+        RAFT_TRY(launch_layer(plan.convc1, a, 1, 1, EPI_RELU, s));
     }
     {   // flo = relu(convf1(flow))      7x7, 2 -> 64
         conv7x7_c2_kernel<64><<<B * ((h + 3) / 4) * ((w + 15) / 16), 256, 0, s>>>(st->flow, wts->convf1.wp, wts->convf1.bias, B, h, w, flo1, 64);
@@ -1087,26 +885,26 @@ extern "C" int raft_update_small_f32(const raft_small_update_weights *wts, int B
     }
     {   // flo = relu(convf2(flo))       3x3, 64 -> 32           -> corflo[:, 96:128]
         ConvArgs a = conv_args(wts->convf2, flo1, 64, 64, nullptr, 0, 0, B, h, w, 32, corflo + 96, 128);
-        RAFT_TRY(raft_launch_conv(a, 3, 3, EPI_RELU, s));
+        RAFT_TRY(launch_layer(plan.convf2, a, 3, 3, EPI_RELU, s));
     }
     {   // out = relu(conv(cat[cor, flo])) 3x3, 128 -> 80        -> x[:, 64:144]
         ConvArgs a = conv_args(wts->conv, corflo, 128, 128, nullptr, 0, 0, B, h, w, 80, st->x + 64, S_XLD);
-        RAFT_TRY(launch_conv3x3(wts->conv, wts->conv_w, 1, a, EPI_RELU, s, true));
+        RAFT_TRY(launch_layer(plan.conv, a, 3, 3, EPI_RELU, s));
     }
     {   // ConvGRU (update.py:26-35), 3x3: z | r
         ConvArgs a = conv_args(wts->gru_zr, st->net, S_HDIM, S_HDIM, st->x, S_XLD, S_XLD, B, h, w, 2 * S_HDIM, zb,
                                S_HDIM);
         a.hid = S_HDIM; a.o1 = rh; a.ldo1 = S_HDIM; a.e0 = st->net; a.lde0 = S_HDIM;
-        RAFT_TRY(launch_conv3x3(wts->gru_zr, wts->gru_zr_w, 2, a, EPI_GRU_ZR, s, true));
+        RAFT_TRY(launch_layer(plan.gru_zr, a, 3, 3, EPI_GRU_ZR, s));
     }
     {
         ConvArgs a = conv_args(wts->gru_q, rh, S_HDIM, S_HDIM, st->x, S_XLD, S_XLD, B, h, w, S_HDIM, st->net, S_HDIM);
         a.e0 = st->net; a.lde0 = S_HDIM; a.e1 = zb; a.lde1 = S_HDIM;
-        RAFT_TRY(launch_conv3x3(wts->gru_q, wts->gru_q_w, 4, a, EPI_GRU_Q, s, true));
+        RAFT_TRY(launch_layer(plan.gru_q, a, 3, 3, EPI_GRU_Q, s));
     }
     {   // relu(flow_head.conv1(net))    3x3, 96 -> 128
         ConvArgs a = conv_args(wts->fh1, st->net, S_HDIM, S_HDIM, nullptr, 0, 0, B, h, w, 128, fh, 128);
-        RAFT_TRY(launch_conv3x3(wts->fh1, wts->fh1_w, 8, a, EPI_RELU, s, true));
+        RAFT_TRY(launch_layer(plan.fh1, a, 3, 3, EPI_RELU, s));
     }
     {   // delta = flow_head.conv2(.), coords1 += delta, flow = coords1 - coords0
         flowhead2_kernel<128><<<raft_ceil_div((int64_t)B * ((h + 1) / 2) * ((w + 3) / 4), 4), 256, 0, s>>>(fh, 128, wts->fh2.wp, wts->fh2.bias, B, h, w,
@@ -1117,6 +915,12 @@ extern "C" int raft_update_small_f32(const raft_small_update_weights *wts, int B
     return RAFT_OK;
 }
 
+extern "C" int raft_update_small_f32(const raft_small_update_weights *wts, int B, int h, int w,
+                                     const raft_state *st, void *stream) {
+    RAFT_REQUIRE_PTR(wts);
+    return update_small_impl(wts, raft_small_loop_plan(*wts, B, h, w, raft_concurrency()), B, h, w, st, stream);
+}
+
 extern "C" int raft_iterate_small_f32(const raft_small_update_weights *wts, const float *pyr,
                                       const int64_t *level_offsets, int B, int h, int w, int iters,
                                       const raft_state *st, float *flow_up, void *stream) {
@@ -1124,12 +928,13 @@ extern "C" int raft_iterate_small_f32(const raft_small_update_weights *wts, cons
     RAFT_REQUIRE_PTR(pyr);
     RAFT_REQUIRE_PTR(level_offsets);
     RAFT_REQUIRE_PTR(flow_up);
-    RAFT_TRY(check_state_small(st));
+    RAFT_TRY(check_state(st, true));
     RAFT_REQUIRE(B > 0 && h > 0 && w > 0 && iters > 0, RAFT_E_SHAPE);
     const int64_t up = (int64_t)B * 64 * h * w * 2;
+    const SmallLoopPlan plan = raft_small_loop_plan(*wts, B, h, w, raft_concurrency());
     for (int i = 0; i < iters; ++i) {
         RAFT_TRY(raft_corr_lookup_f32(pyr, level_offsets, st->coords1, B, h, w, 4, 3, st->corr, S_CORR_LD, stream));
-        RAFT_TRY(raft_update_small_f32(wts, B, h, w, st, stream));
+        RAFT_TRY(update_small_impl(wts, plan, B, h, w, st, stream));
         RAFT_TRY(raft_upflow8_f32(st->flow, B, h, w, flow_up + i * up, stream));
     }
     return RAFT_OK;

@@ -425,11 +425,6 @@ static int raft_launch_conv_halo_tile(const ConvArgs &a, int th, int tn, hipStre
 
 template <int KH, int KW>
 static int raft_launch_conv_halo_epi(const ConvArgs &a, int th, int tn, int epi, hipStream_t s) {
-    switch (epi) {
-        case EPI_LINEAR: return raft_launch_conv_halo_tile<KH, KW, EPI_LINEAR>(a, th, tn, s);
-        case EPI_RELU: return raft_launch_conv_halo_tile<KH, KW, EPI_RELU>(a, th, tn, s);
-        case EPI_GRU_ZR: return raft_launch_conv_halo_tile<KH, KW, EPI_GRU_ZR>(a, th, tn, s);
-        case EPI_GRU_Q: return raft_launch_conv_halo_tile<KH, KW, EPI_GRU_Q>(a, th, tn, s);
-    }
-    return RAFT_E_UNSUPPORTED;
+    return raft_dispatch_epi<EPI_LINEAR, EPI_RELU, EPI_GRU_ZR, EPI_GRU_Q>(
+        epi, [&](auto e) { return raft_launch_conv_halo_tile<KH, KW, decltype(e)::value>(a, th, tn, s); });
 }

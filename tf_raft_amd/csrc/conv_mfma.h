@@ -9,6 +9,8 @@
 //   * the same for the epilogues: the GRU gates read h / z with unconditional (clamped) loads issued as one batch per
 //     accumulator tile before any arithmetic.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 enum ConvEpilogue {
@@ -64,5 +66,31 @@ constexpr unsigned RAFT_OOB = 0x80000000u;   // >= any buffer extent we accept (
 // RAFT_CONV_TILE -- was kept for A/B through round 3 and removed in round 4: the halo-tiled kernel of conv_halo.h replaced it
 // everywhere in round 1; its measurements stay in profiles/r01*.)
 
-// Host-side launch with tile selection.  Returns RAFT_E_UNSUPPORTED for an un-instantiated shape.
-int raft_launch_conv(const ConvArgs &a, int kh, int kw, int epi, hipStream_t stream);
+// ---- launchers: validate, then dispatch a plan (launch_plan.h); RAFT_E_UNSUPPORTED for a shape or plan not instantiated
+int raft_launch_conv(const ConvArgs &a, int kh, int kw, int epi, hipStream_t s, HaloPlan p);            // conv.hip
+int raft_launch_conv_wino(const ConvArgs &a, int epi, hipStream_t s, WinoPlan p);                      // conv_wino.hip
+int raft_launch_conv_wino1d(const ConvArgs &a, int kh, int kw, int epi, hipStream_t s, Wino1dPlan p);   // conv_wino1d.hip
+int raft_launch_conv_wino4(const ConvArgs &a, int epi, hipStream_t s, Wino4Plan p);                    // conv_wino4.hip
+
+// Operand checks of every launcher: 16-byte aligned sources and weights (RAFT_E_ALIGN); each operand spans < 2 GiB (32-bit buffer
+// offsets, RAFT_E_UNSUPPORTED).  wtaps: weight taps (kernel or Winograd transform); opt: optional operands checked where present.
+enum { RAFT_CHECK_O1 = 1, RAFT_CHECK_E0 = 2, RAFT_CHECK_E1 = 4, RAFT_CHECK_INIT = 8, RAFT_CHECK_ALL = 15 };
+static inline int raft_check_operands(const ConvArgs &a, int64_t wtaps, int opt) {
+    if (a.lda0 % 4 || (a.c1 && a.lda1 % 4)) return RAFT_E_ALIGN;
+    if (!raft_aligned16(a.a0) || !raft_aligned16(a.wp) || (a.c1 && !raft_aligned16(a.a1))) return RAFT_E_ALIGN;
+    const int64_t M = (int64_t)a.B * a.H * a.W, lim = (int64_t)1 << 31;
+    if (((M - 1) * a.lda0 + a.c0) * 4 >= lim || (a.c1 && ((M - 1) * a.lda1 + a.c1) * 4 >= lim)) return RAFT_E_UNSUPPORTED;
+    if (M * a.ldo0 * 4 >= lim || wtaps * (a.c0 + a.c1) * a.npad * 4 >= lim) return RAFT_E_UNSUPPORTED;
+    if (((opt & RAFT_CHECK_O1) && a.o1 && M * a.ldo1 * 4 >= lim) || ((opt & RAFT_CHECK_E0) && a.e0 && M * a.lde0 * 4 >= lim) ||
+        ((opt & RAFT_CHECK_E1) && a.e1 && M * a.lde1 * 4 >= lim) || ((opt & RAFT_CHECK_INIT) && a.init && M * a.ldi * 4 >= lim))
+        return RAFT_E_UNSUPPORTED;
+    return RAFT_OK;
+}
+
+// Epilogue dispatch: launch(std::integral_constant<int, EPI>()) if epi is one of EPIS (a family's instantiated epilogues), else RAFT_E_UNSUPPORTED.
+template <int... EPIS, class Launch>
+static int raft_dispatch_epi(int epi, Launch &&launch) {
+    int rc = RAFT_E_UNSUPPORTED;
+    (void)((epi == EPIS && ((rc = launch(std::integral_constant<int, EPIS>())), true)) || ...);
+    return rc;
+}

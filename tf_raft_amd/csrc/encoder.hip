@@ -16,9 +16,6 @@
 #include "conv_halo.h"
 #include "conv_wino.h"
 
-// F(4x4, 3x3) launcher (conv_wino4.hip; the kernel header is not needed here)
-int raft_launch_conv_wino4(const ConvArgs &a, int epi, hipStream_t s, int decide_npad = 0, int ks_hint = 0);
-
 namespace {
 
 // ---------------------------------------------------------------- small kernels
@@ -202,22 +199,22 @@ extern "C" int64_t raft_encoder_workspace_floats(const raft_encoder_weights *w, 
 }
 
 static int encoder_impl(const raft_encoder_weights *w, const float *images, const float *images_b, int n_a, int n, int H, int W,
-                        int input_affine, float *out, float *workspace, void *stream);
+                        int input_affine, float *out, float *workspace, void *stream, int hint);
 
 extern "C" int raft_encoder_f32(const raft_encoder_weights *w, const float *images, int n, int H, int W,
                                 int input_affine, float *out, float *workspace, void *stream) {
-    return encoder_impl(w, images, images, n, n, H, W, input_affine, out, workspace, stream);
+    return encoder_impl(w, images, images, n, n, H, W, input_affine, out, workspace, stream, raft_concurrency());
 }
 
 extern "C" int raft_encoder_pair_f32(const raft_encoder_weights *w, const float *images_a, const float *images_b, int n_each,
                                      int H, int W, int input_affine, float *out, float *workspace, void *stream) {
     RAFT_REQUIRE_PTR(images_b);
     RAFT_REQUIRE(n_each > 0, RAFT_E_SHAPE);
-    return encoder_impl(w, images_a, images_b, n_each, 2 * n_each, H, W, input_affine, out, workspace, stream);
+    return encoder_impl(w, images_a, images_b, n_each, 2 * n_each, H, W, input_affine, out, workspace, stream, raft_concurrency());
 }
 
 static int encoder_impl(const raft_encoder_weights *w, const float *images, const float *images_b, int n_a, int n, int H, int W,
-                        int input_affine, float *out, float *workspace, void *stream) {
+                        int input_affine, float *out, float *workspace, void *stream, int hint) {
     RAFT_REQUIRE_PTR(w);
     RAFT_REQUIRE_PTR(images);
     RAFT_REQUIRE_PTR(out);
@@ -242,17 +239,8 @@ static int encoder_impl(const raft_encoder_weights *w, const float *images, cons
         const int64_t tiles_w = (int64_t)n * 2 * ((h1 + 3) / 4) * ((w1 + 31) / 32);
         if (tiles_w > tiles_max) tiles_max = tiles_w;
     }
-    const bool use_wino = raft_opt(RAFT_OPT_ENC_WINO, 1) != 0;   // 0: direct 3x3 kernels everywhere (A/B timing, parity tests)
-    // stages whose stride-1 3x3 layers run the F(4x4, 3x3) kernel (bit 0 = layer1 ...).  Default: every layer whose launch is
-    // MORE than one round of the kernel's 8 x 64-pixel x 64-channel workgroups on the chip (> 256) -- at 4 pairs fnet's layer1 / layer2
-    // (896 / 448) and cnet's layer1 (448).  Per kernel at 4 pairs (profiles/r07u_encoder_kernels_b4.txt): fnet's ten layers
-    // 1308 -> 1120 us, the 64-channel half-resolution layers ~190 -> ~150 us each (K = 64 is only four 16-channel chunks:
-    // prologue and output transform are 40 % of a workgroup); a layer3 launch with the K-split variant is slower than F(2x2)
-    // (41 against 28 us).  Launches of a single round gain nothing measurable (one / two pairs: 137.2 / 203.8 pairs/s without,
-    // 137.2 / 204.5 with every stage on it, profiles/r08k_round3_options.txt) and F(4x4) is the noisier algorithm (3.3e-6 against
-    // 1.9e-6 of the output scale), so they stay on F(2x2).  An explicit RAFT_ENC_WINO4 is taken as given.
-    const int wino4_mask = use_wino ? raft_opt(RAFT_OPT_ENC_WINO4, 7) : 0;
-    const bool wino4_forced = raft_opt_is_set(RAFT_OPT_ENC_WINO4);
+    // stride-1 3x3 layers: F(4x4) on the stages of raft_enc_stage_wino4 (launch_plan.h), else F(2x2) unless RAFT_ENC_WINO = 0
+    const bool use_wino = raft_enc_wino();
     EncBufs b;
     float *p = workspace;
     b.img4 = p; p += align4((int64_t)n * H * W * 4);
@@ -293,7 +281,10 @@ static int encoder_impl(const raft_encoder_weights *w, const float *images, cons
         a.stats = (inorm && slot >= 0) ? b.part : nullptr;
         int th, tn;
         enc_pick(Ho, cw.npad, &th, &tn);
-        int rc = wino4 ? raft_launch_conv_wino4(a, epi, s) : (wino ? raft_launch_conv_wino(a, epi, s) : enc_conv(a, kind, epi, th, tn, s));
+        const bool plain = pre_sc == nullptr && a.stats == nullptr;
+        int rc = wino4  ? raft_launch_conv_wino4(a, epi, s, raft_wino4_plan(n, Ho, Wo, a.c0, a.c1, a.npad, plain, hint))
+                 : wino ? raft_launch_conv_wino(a, epi, s, raft_wino_plan(n, Ho, Wo, a.c0, a.c1, a.npad, plain, hint))
+                        : enc_conv(a, kind, epi, th, tn, s);
         if (rc != RAFT_OK) return rc;
         if (a.stats) {
             const int tiles = wino4  ? 2 * ((Ho + 7) / 8) * ((Wo + 63) / 64)
@@ -342,8 +333,7 @@ static int encoder_impl(const raft_encoder_weights *w, const float *images, cons
         }
         const EncKind k1 = stride == 2 ? ENC_3x3_S2 : ENC_3x3_S1;
         const int ni = 1 + blk * 3;   // index of this block's norm1 in in_gamma / in_beta
-        const bool w4 = ((wino4_mask >> (blk / 2)) & 1) &&
-                        (wino4_forced || (int64_t)n * ((Ho + 7) / 8) * ((Wo + 63) / 64) * ((F + 63) / 64) * raft_concurrency() > 256);   // loops sharing the chip: the launch counts raft_concurrency() times (378.7 against 375.6 pairs/s with every stage on F(4x4) under three lanes, profiles/r12l_*)
+        const bool w4 = raft_enc_stage_wino4(blk / 2, n, Ho, Wo, F, hint);
         const raft_conv_weights *w44a = w4 ? &w->block_w44[blk][0] : nullptr, *w44b = w4 ? &w->block_w44[blk][1] : nullptr;
         if (inorm) {
             RAFT_TRY(conv(k1, c1, x, C, Hc, Wc, Ho, Wo, p1t, p1l, F, EPI_LINEAR, b.r1, nullptr, nullptr, nullptr, 0,

@@ -34,7 +34,7 @@ int main(int argc, char **argv) {
     a.o0 = o0; a.ldo0 = 128; a.e0 = h; a.lde0 = 128; a.init = ctx; a.ldi = 768;
     if (zr) { a.hid = hid; a.o1 = o1; a.ldo1 = 128; } else { a.e1 = z; a.lde1 = 128; }
     const int kh = axis ? 5 : 1, kw = axis ? 1 : 5;
-    auto go = [&]() { return raft_launch_conv_wino1d(a, kh, kw, zr ? EPI_GRU_ZR : EPI_GRU_Q, 0, mo); };
+    auto go = [&]() { return raft_launch_conv_wino1d(a, kh, kw, zr ? EPI_GRU_ZR : EPI_GRU_Q, 0, raft_wino1d_plan(a.B, a.H, a.W, a.c0, a.c1, a.npad, kh, mo, 1)); };
     for (int i = 0; i < 3; ++i) if (go() != 0) { printf("launch failed\n"); return 1; }
     hipDeviceSynchronize();
     hipEvent_t e0, e1;

@@ -24,7 +24,7 @@ int main(int argc, char **argv) {
     ConvArgs a = {};
     a.a0 = x; a.lda0 = cin; a.c0 = cin; a.wp = w; a.bias = bias; a.B = B; a.H = H; a.W = W;
     a.npad = npad; a.nvalid = npad; a.scale = 1.f; a.o0 = out; a.ldo0 = npad;
-    auto go = [&]() { raft_launch_conv_wino4(a, EPI_RELU, 0); };
+    auto go = [&]() { raft_launch_conv_wino4(a, EPI_RELU, 0, raft_wino4_plan(a.B, a.H, a.W, a.c0, a.c1, a.npad, true, 1)); };
     for (int i = 0; i < 3; ++i) go();
     hipDeviceSynchronize();
     hipEvent_t e0, e1;
