@@ -9,7 +9,8 @@
  *
  * Conventions
  *   - plain C: raw DEVICE pointers, explicit sizes, no torch / C++ types;
- *   - all tensors are fp32, NHWC (channels contiguous), exactly the reference's layouts;
+ *   - all tensors are fp32, NHWC (channels contiguous), exactly the reference's layouts (the one exception: the
+ *     raft_crop_or_pad_u8* entries take or return bytes, the type frames and validity masks arrive in);
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream); calls only
  *     enqueue work, they never synchronise and never allocate.  Two documented exceptions:
  *     raft_loop_ctx_create / _destroy, which create and destroy the four cross-stream HIP events of
@@ -68,7 +69,7 @@
 extern "C" {
 #endif
 
-#define RAFT_HIP_VERSION 220          /* 0.2.0: ABI stamp, checked by the Python binding -- bump on ANY struct / signature change */
+#define RAFT_HIP_VERSION 221          /* 0.2.1: ABI stamp, checked by the Python binding -- bump on ANY struct / signature change */
 #define RAFT_MAX_LEVELS 4
 
 enum {
@@ -178,6 +179,20 @@ int raft_upflow8_f32(const float *flow, int B, int h, int w, float *out, void *s
  * the box it runs on -- the "measured roofline" the lookup / build / upsample kernels are quoted
  * against next to the 8 TB/s datasheet figure. */
 int raft_stream_copy_f32(const float *src, float *dst, int64_t n, void *stream);
+
+/* tf.image.resize_with_crop_or_pad on NHWC images (reference tf_raft/datasets/dataset.py:323-334 CropOrPadder,
+ * tf_raft/training.py:72-84 VisFlowCallback): src (N, Hs, Ws, C) -> dst (N, Ht, Wt, C), both contiguous.  Per axis, with
+ * d = target - source (floor division): the source window starts at max(-d // 2, 0), lands at max(d // 2, 0) in the target
+ * and is min(source, target) long, so an odd surplus goes to the bottom / right; everything outside it is zero in the
+ * input's own scale.  Every element of dst is written exactly once (no memset needed).  Any sizes >= 1, any C >= 1 and any
+ * alignment are accepted; destination rows that are whole 16-byte chunks of a 16-byte aligned dst (the model's targets
+ * always are) take the vectorised path.  W * C of either side must fit an int.
+ *   _f32    : float -> float (float images, ground-truth flow, predictions: N = iterations x batch in one launch)
+ *   _u8_f32 : uint8 -> float (uint8 frames: the cast and the window in one pass)
+ *   _u8     : uint8 -> uint8 (validity masks; bool tensors are bytes) */
+int raft_crop_or_pad_f32(const float *src, float *dst, int N, int Hs, int Ws, int Ht, int Wt, int C, void *stream);
+int raft_crop_or_pad_u8_f32(const uint8_t *src, float *dst, int N, int Hs, int Ws, int Ht, int Wt, int C, void *stream);
+int raft_crop_or_pad_u8(const uint8_t *src, uint8_t *dst, int N, int Hs, int Ws, int Ht, int Wt, int C, void *stream);
 
 /* Measurement utility (no reference counterpart): `blocks` workgroups of 256 threads, every wave issuing `iters` x 8
  * independent v_mfma_f32_16x16x4_f32 (nothing else in the loop; non-zero lane-varying operands); out: blocks * 256

@@ -1,0 +1,3 @@
+"""Import-path shim for reference ``tf_raft/datasets/__init__.py`` (train_sintel.py:9: ``from tf_raft.datasets import MpiSintel,
+ShapeSetter, CropOrPadder``): the batch-shaping stages; the data-set readers are out of scope."""
+from tf_raft_amd.datasets import CropOrPadder, ShapeSetter  # noqa: F401

@@ -1,0 +1,41 @@
+"""Mirror of the batch-shaping stages of reference ``tf_raft/datasets/dataset.py`` that sit between a data set and the model:
+``CropOrPadder`` (dataset.py:323-334) and ``ShapeSetter`` (dataset.py:309-316), as used by train_sintel.py:52-56, 72-75.
+The data-set readers and the augmentation are out of scope.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _dev
+from .image_ops import _on_device, resize_with_crop_or_pad
+
+
+def CropOrPadder(target_size):
+    """reference dataset.py:323-334: ``f(image1, image2, flow, valid) -> (image1, image2, flow, valid)`` at ``target_size``
+    (centred crop / zero padding, ``tf_raft_amd.image_ops``).  ``valid`` is ``(N, H, W)`` (or ``(H, W)``) without a channel axis
+    and comes back that way.  Every array keeps its type; the results are device tensors."""
+    th, tw = (int(v) for v in target_size)
+
+    def f(image1, image2, flow, valid):
+        image1 = resize_with_crop_or_pad(image1, th, tw)
+        image2 = resize_with_crop_or_pad(image2, th, tw)
+        flow = resize_with_crop_or_pad(flow, th, tw)
+        valid = _on_device(valid)
+        valid = resize_with_crop_or_pad(valid[..., None], th, tw).as_subclass(torch.Tensor)[..., 0]
+        return image1, image2, flow, _dev.wrap(valid)
+    return f
+
+
+def ShapeSetter(batch_size, image_size):
+    """reference dataset.py:309-316 sets the static shapes of a ``tf.data`` element; tensors here carry their shapes, so this
+    CHECKS them: ``ValueError`` when one of the four is not ``(batch_size, *image_size[, channels])``."""
+    image_size = tuple(int(v) for v in image_size)
+
+    def f(image1, image2, flow, valid):
+        want = {'image1': (batch_size, *image_size, 3), 'image2': (batch_size, *image_size, 3),
+                'flow': (batch_size, *image_size, 2), 'valid': (batch_size, *image_size)}
+        for (name, shape), a in zip(want.items(), (image1, image2, flow, valid)):
+            if tuple(a.shape) != shape:
+                raise ValueError(f'{name} has shape {tuple(a.shape)}, expected {shape}')
+        return image1, image2, flow, valid
+    return f

@@ -1,4 +1,4 @@
-"""Output-side helpers of the prediction path: Middlebury ``.flo`` files and the flow colour coding.
+"""Output-side helpers of the prediction path: Middlebury ``.flo`` files, the flow colour coding and a PNG writer.
 
 Mirrors what a user of the reference calls right after ``model([image1, image2])``:
 ``tf_raft/datasets/frame_utils.py:12-31`` (readFlow), ``70-99`` (writeFlow) and
@@ -7,6 +7,9 @@ colour wheel of Baker et al., ICCV 2007).  NumPy on the host: these touch one (H
 are not on the device path.  Accepts NumPy arrays, torch tensors (any device) and the model's output tensors.
 """
 from __future__ import annotations
+
+import struct
+import zlib
 
 import numpy as np
 
@@ -102,3 +105,23 @@ def flow_to_image(flow_uv, clip_flow=None, convert_to_bgr=False) -> np.ndarray:
     rad_max = np.max(np.sqrt(np.square(u) + np.square(v)))
     eps = 1e-5
     return flow_uv_to_colors(u / (rad_max + eps), v / (rad_max + eps), convert_to_bgr)
+
+
+def write_png(path, image) -> None:
+    """``imageio.imwrite(path, image)`` for what ``VisFlowCallback`` writes (reference training.py:88): uint8 ``(H, W, 3)`` as an
+    8-bit RGB PNG, every scanline with filter type 0, one IDAT chunk.  Standard library only."""
+    image = _to_numpy(image)
+    if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or 0 in image.shape:
+        raise ValueError(f'image must be uint8 (H, W, 3), got {image.dtype} {image.shape}')
+    h, w = image.shape[:2]
+    rows = np.zeros((h, 1 + 3 * w), np.uint8)                 # leading byte of a scanline: filter type 0 (none)
+    rows[:, 1:] = image.reshape(h, 3 * w)
+
+    def chunk(kind, data):
+        return struct.pack('>I', len(data)) + kind + data + struct.pack('>I', zlib.crc32(kind + data) & 0xffffffff)
+
+    with open(path, 'wb') as f:
+        f.write(b'\x89PNG\r\n\x1a\n')
+        f.write(chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 2, 0, 0, 0)))      # 8 bits, colour type 2 (RGB), no interlace
+        f.write(chunk(b'IDAT', zlib.compress(rows.tobytes(), 6)))
+        f.write(chunk(b'IEND', b''))

@@ -33,6 +33,7 @@ import numpy as np
 import torch
 
 from . import _dev
+from . import image_ops
 from . import weights as weights_mod
 from . import _ffi
 from ._ffi import check
@@ -81,7 +82,8 @@ class RAFT:
     variant = 'raft'
 
     def __init__(self, drop_rate=0, iters=12, iters_pred=24, weights: Optional[Dict[str, np.ndarray]] = None,
-                 seed=0, alternate_corr=False, overlap=None, pipeline=None, lanes=None, loop_concurrency=None, **kwargs):
+                 seed=0, alternate_corr=False, overlap=None, pipeline=None, lanes=None, loop_concurrency=None, target_size=None,
+                 **kwargs):
         # reference model.py:11-12 forwards **kwargs to tf.keras.Model, whose constructor takes `name` (and nothing a
         # forward pass depends on): accept it, reject the rest
         self.name = kwargs.pop('name', type(self).__name__.lower())
@@ -96,6 +98,11 @@ class RAFT:
         self.iters = iters
         self.iters_pred = iters_pred
         self.alternate_corr = alternate_corr
+        # Inference on frames of any size (reference train_sintel.py:72-75 CropOrPadder, training.py:72-84 VisFlowCallback): None =
+        # frames must already be multiples of 8; 'auto' = every inference call zero-pads its frames to the next multiples of 8, at
+        # least MIN_SIDE per axis; (Ht, Wt) = the reference's fixed target, larger frames are centre-cropped.  The returned flow
+        # is cropped / zero-padded back to the frames' own size.  Training-mode calls and train_step are not affected.
+        self.target_size = self._check_target_size(target_size)
         # three-stream schedule of the loop (RAFT only); RAFT_OVERLAP=0 forces the single-stream loop.  With several lanes
         # (below) the loops of a pipelined call default to the single-stream schedule: the other lanes fill the chain's idle CUs
         # and gaps better than a loop's own side branches do (profiles/r12b_lanes_ab_per_process.txt).
@@ -129,6 +136,50 @@ class RAFT:
         self._weights = dict(weights)
         self._dw, self._host_stale, self._train_vars = None, False, None     # device master copies of train_step
         self._build(weights)
+
+    MIN_SIDE = 64      # the four-level pyramid pools an H/8 x W/8 map three times: below 8 rows or columns its last level is empty
+
+    @classmethod
+    def _check_target_size(cls, target_size):
+        if target_size is None or target_size == 'auto':
+            return target_size
+        try:
+            th, tw = (int(v) for v in target_size)
+        except (TypeError, ValueError):
+            raise ValueError(f"target_size must be None, 'auto' or (height, width), got {target_size!r}") from None
+        if th % 8 or tw % 8 or th < cls.MIN_SIDE or tw < cls.MIN_SIDE:
+            raise ValueError(f'target_size must be multiples of 8 and at least {cls.MIN_SIDE} per axis, got {th} x {tw}')
+        return (th, tw)
+
+    def _model_size(self, H, W):
+        """The size the model runs at for frames of H x W under ``target_size``."""
+        if self.target_size == 'auto':
+            return max(self.MIN_SIDE, -(-H // 8) * 8), max(self.MIN_SIDE, -(-W // 8) * 8)
+        return self.target_size
+
+    def _fit_frames(self, image1, image2):
+        """``target_size`` set: both frames as float32 device tensors of the model's size, and the frames' own (H, W) when that
+        differs (None: nothing was launched).  uint8 frames are cast and windowed in one pass."""
+        image1, image2 = image_ops._on_device(image1), image_ops._on_device(image2)
+        if image1.dim() != 4 or image1.shape[-1] != 3 or image1.shape != image2.shape or image1.dtype != image2.dtype or 0 in image1.shape:
+            raise ValueError(f'images must both be (bs, H, W, 3) of one type, got {tuple(image1.shape)} {image1.dtype} / '
+                             f'{tuple(image2.shape)} {image2.dtype}')
+        H, W = image1.shape[1:3]
+        th, tw = self._model_size(H, W)
+        if (H, W) == (th, tw):
+            return _dev.to_device(image1), _dev.to_device(image2), None
+        if image1.dtype not in (torch.uint8, torch.float32):
+            image1, image2 = image1.to(torch.float32), image2.to(torch.float32)
+        return (image_ops.window_copy(image1, th, tw, torch.float32), image_ops.window_copy(image2, th, tw, torch.float32), (H, W))
+
+    @staticmethod
+    def _fit_flow(out, window, into=None):
+        """Predictions (..., Ht, Wt, 2) of the model's size -> the frames' own size, ONE launch over all leading axes, on the
+        current stream."""
+        lead = tuple(out.shape[:-3])
+        res = image_ops.window_copy(out.view((-1,) + tuple(out.shape[-3:])), window[0], window[1],
+                                    out=None if into is None else into.view((-1,) + tuple(into.shape[-3:])))
+        return res.view(lead + tuple(res.shape[-3:]))
 
     def _build(self, weights):
         self.fnet = BasicEncoder(output_dim=256, norm_type='instance', drop_rate=self.drop_rate,
@@ -312,6 +363,9 @@ class RAFT:
     def _forward(self, inputs, training=False, final_only=False, pipelined=None):
         self._sync_inference_weights()
         image1, image2 = inputs
+        window = None
+        if self.target_size is not None and not training:
+            image1, image2, window = self._fit_frames(image1, image2)
         image1 = _dev.to_device(image1)
         image2 = _dev.to_device(image2)
         if image1.dim() != 4 or image1.shape[-1] != 3 or image1.shape != image2.shape:
@@ -329,11 +383,11 @@ class RAFT:
             # with several lanes the loops are single-stream unless overlap was asked for: the lanes are each other's side branches
             plan = self._plan(n % lanes, self.overlap and not (lanes > 1 and not self._overlap_given), lanes)
             with _hinted(plan.pre_hint):
-                return self._forward_lane(image1, image2, final_only, n, lanes, plan)
+                return self._forward_lane(image1, image2, final_only, n, lanes, plan, window)
         self._join_pipeline()                       # (a training-mode or serial call after pipelined ones)
         plan = self._plan(0, self.overlap, 1 if training else self.loop_concurrency)
         with _hinted(plan.pre_hint):
-            return self._forward_serial(image1, image2, training, final_only, plan)
+            return self._forward_serial(image1, image2, training, final_only, plan, window)
 
     def _plan(self, lane, three_stream, hint):
         """The loop plan of one call.  ``hint`` is the number of loops that share the chip: the lanes of a pipelined call,
@@ -342,7 +396,7 @@ class RAFT:
         return _LoopPlan(lane, three_stream, hint if (hint > 1 and self._shape_hint == 'all') else None,
                          hint if self._shape_hint in ('loop', 'all') else 1)
 
-    def _forward_serial(self, image1, image2, training, final_only, plan):
+    def _forward_serial(self, image1, image2, training, final_only, plan, window=None):
         B, H, W, _ = image1.shape
         if self.overlap and not training:
             # the context encoder does not depend on the feature encoder or the volume: it runs on a side stream
@@ -371,6 +425,8 @@ class RAFT:
         iters = self.iters if training else self.iters_pred
         with _ffi.thread_concurrency(plan.loop_hint):
             out = self._run_loop(correlation, st, iters, self._alloc_out(iters, B, H, W, image1.device, final_only), final_only, plan)
+        if window is not None:
+            out = self._fit_flow(out, window)       # follows the loop on the current stream
         return _dev.wrap(out) if final_only else [_dev.wrap(out[i]) for i in range(iters)]   # model.py:109
 
     @staticmethod
@@ -435,7 +491,7 @@ class RAFT:
     # raft_loop_ctx of its own), so up to D loops of consecutive calls are resident together and each fills the other's gaps and
     # idle CUs; the UpdateState ring has D + 1 slots (call n + D + 1's pre-loop waits for loop n).  Each call still runs exactly
     # the kernels of the serial schedule in the same order on its own buffers: results stay bit-identical per call.
-    def _forward_lane(self, image1, image2, final_only, n, lanes, plan):
+    def _forward_lane(self, image1, image2, final_only, n, lanes, plan, window=None):
         B, H, W, _ = image1.shape
         h, w = H // 8, W // 8
         dev = image1.device
@@ -451,21 +507,25 @@ class RAFT:
         correlation = CorrBlock(fmap1, fmap2, num_levels=self.corr_levels, radius=self.corr_radius,
                                 alternate=self.alternate_corr)                           # model.py:77
         out = self._alloc_out(self.iters_pred, B, H, W, dev, final_only)      # from the caller's stream's pool, like every other buffer
+        res = out if window is None else self._alloc_out(self.iters_pred, B, window[0], window[1], dev, final_only)
         ready = torch.cuda.Event()
         ready.record(cur)
         loop.wait_event(ready)
         with torch.cuda.stream(loop), _ffi.thread_concurrency(plan.loop_hint):
             self._run_loop(correlation, st, self.iters_pred, out, final_only, plan)
+            if window is not None:
+                # back to the frames' own size on the LOOP's stream, in front of `done`: the caller's stream never waits for the loop
+                self._fit_flow(out, window, into=res)
             done = torch.cuda.Event()
             done.record(loop)
-        for t in (out, getattr(correlation, '_pyr', None), getattr(correlation, '_f2pyr', None), correlation.fmap1, correlation.fmap2):
+        for t in (out, res, getattr(correlation, '_pyr', None), getattr(correlation, '_f2pyr', None), correlation.fmap1, correlation.fmap2):
             if isinstance(t, torch.Tensor) and t.is_cuda:
                 t.as_subclass(torch.Tensor).record_stream(loop)      # allocated under `cur`, in use on `loop`
         ent[1] = done
         pending = _dev.Pending(done, dev)
         if final_only:
-            return _dev.wrap(out, pending)
-        return [_dev.wrap(out[i], pending) for i in range(self.iters_pred)]             # model.py:109
+            return _dev.wrap(res, pending)
+        return [_dev.wrap(res[i], pending) for i in range(self.iters_pred)]             # model.py:109
 
     def predict_step(self, data, _pipelined=None):
         """reference model.py:160-166: ``flow_predictions[-1]`` of the forward pass.  RAFT computes it with the mask head

@@ -1,14 +1,15 @@
 """Mirror of reference ``tf_raft/training.py`` (learning-rate scale functions) and of the optimizer objects the reference's
 training scripts build (train_sintel.py:83-93): ``tfa.optimizers.CyclicalLearningRate`` and ``tfa.optimizers.AdamW``
 (tensorflow-addons 0.11.1 / Keras Adam of TF 2.3 semantics), with the update itself a HIP kernel (``raft_adamw_step_f32``)
-and ``tf.clip_by_global_norm`` reduced on the device (``raft_sumsq_f32``).  ``VisFlowCallback`` (Keras callback plumbing) is
-out of scope.
+and ``tf.clip_by_global_norm`` reduced on the device (``raft_sumsq_f32``), and of ``VisFlowCallback`` (training.py:43-88).
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 
+import numpy as np
 import torch
 
 from . import _dev
@@ -107,3 +108,45 @@ class AdamW:
         _grad.bump_pack_version()      # the variables changed in place through raw pointers: packed copies of them are stale
         self.iterations += 1
         return gn
+
+
+class VisFlowCallback:
+    """reference training.py:43-88 (a ``tf.keras.callbacks.Callback``): at the end of an epoch, predict the flow of the first
+    (or of randomly chosen) samples of ``dataset`` and write ``[image1, image2, colour-coded flow]`` stacked vertically to
+    ``logdir/epoch{NNN}_{iii}.png``.  Each frame is padded (or cropped) to ``target_size`` for the model and the final flow is
+    cropped (or padded) back to the frame's own size, both on the device (``tf_raft_amd.image_ops``).  ``dataset[i]`` yields
+    ``(image1, image2, ...)`` of shape ``(H, W, 3)``, values 0..255."""
+
+    def __init__(self, dataset, target_size=(448, 1024), num_visualize=1, choose_random=False, logdir='predicted_flows'):
+        self.dataset = dataset
+        self.target_size = tuple(int(v) for v in target_size)
+        self.num_visualize = num_visualize
+        self.choose_random = choose_random
+        self.logdir = logdir
+        self.model = None
+        os.makedirs(logdir, exist_ok=True)
+
+    def set_model(self, model):
+        self.model = model
+
+    def on_epoch_end(self, epoch, logs=None):
+        from . import io
+        from .image_ops import resize_with_crop_or_pad
+        if self.model is None:
+            raise RuntimeError('VisFlowCallback has no model: call set_model(model) first')
+        if self.choose_random:
+            vis_ids = np.random.choice(len(self.dataset), size=self.num_visualize, replace=False)
+        else:
+            vis_ids = range(self.num_visualize)
+        for i in vis_ids:
+            image1, image2, *_ = self.dataset[int(i)]
+            if len(image1.shape) > 3:
+                raise ValueError('target dataset must not be batched')
+            h_origin, w_origin, _ = image1.shape
+            padded = [resize_with_crop_or_pad(im, *self.target_size, dtype=torch.float32)[None] for im in (image1, image2)]
+            flow_pred = self.model(padded, training=False)[-1][0]
+            flow_pred = resize_with_crop_or_pad(flow_pred, h_origin, w_origin)
+            flow_img = io.flow_to_image(flow_pred.numpy()).astype(np.uint8)
+            frames = [np.clip(io._to_numpy(im), 0, 255).astype(np.uint8) for im in (image1, image2)]
+            contents = np.concatenate(frames + [flow_img], axis=0)
+            io.write_png(os.path.join(self.logdir, f'epoch{str(epoch + 1).zfill(3)}_{str(int(i) + 1).zfill(3)}.png'), contents)
