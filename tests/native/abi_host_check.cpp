@@ -72,8 +72,137 @@ static void options_once(int salt) {
     EXPECT(raft_set_option("RAFT_LOOKUP_FUSED", "not a number") != 0 || true);
 }
 
+static raft_basic_update_weights basic_weights();
+
+// The update-block and loop entry points with invalid calls that reach validation (non-NULL dummy weights and state) and the
+// exact code each returns: NULL pointers first, then dimensions, then the stream rule.  Every row is rejected before any HIP call.
+static void loop_rejects() {
+    static float f[64] = {0};
+    static const int64_t off[RAFT_MAX_LEVELS + 1] = {0, 32, 64, 96, 128};
+    static const raft_basic_update_weights W = basic_weights();
+    static const raft_small_update_weights SW = {};
+    const raft_state ok = {f, f, f, f, f, f, f, f, f};
+    raft_state no_net = ok, no_mask = ok, no_ctx = ok, no_ws = ok;
+    no_net.net = nullptr; no_mask.mask = nullptr; no_ctx.ctx = nullptr; no_ws.ws = nullptr;
+    raft_basic_update_weights no_fh1 = W;
+    no_fh1.fh1_w = {nullptr, nullptr, 0};
+    // never dereferenced: validation fails first
+    void *s = (void *)f, *a0 = (void *)(f + 4), *a1 = (void *)(f + 8);
+    raft_loop_ctx *ctx = (raft_loop_ctx *)(f + 12);
+    float ms[RAFT_BASIC_STAGES];
+#define EXPECT_RC(call, want)                                                                                          \
+    do {                                                                                                               \
+        const int got__ = (call);                                                                                      \
+        if (got__ != (want)) {                                                                                         \
+            std::fprintf(stderr, "FAILED %s:%d: %s returned %d, expected %s\n", __FILE__, __LINE__, #call, got__, #want); \
+            ++failures;                                                                                                \
+        }                                                                                                              \
+    } while (0)
+    // ---- raft_update_basic_f32
+    EXPECT_RC(raft_update_basic_f32(nullptr, 1, 8, 8, &ok, s), RAFT_E_NULL);
+    EXPECT_RC(raft_update_basic_f32(&W, 1, 8, 8, nullptr, s), RAFT_E_NULL);
+    EXPECT_RC(raft_update_basic_f32(&W, 1, 8, 8, &no_net, s), RAFT_E_NULL);
+    EXPECT_RC(raft_update_basic_f32(&W, 1, 8, 8, &no_mask, s), RAFT_E_NULL);
+    EXPECT_RC(raft_update_basic_f32(&W, 1, 8, 8, &no_ctx, s), RAFT_E_NULL);
+    EXPECT_RC(raft_update_basic_f32(&W, 0, 8, 8, &ok, s), RAFT_E_SHAPE);
+    EXPECT_RC(raft_update_basic_f32(&W, 1, 8, -1, &ok, s), RAFT_E_SHAPE);
+    EXPECT_RC(raft_update_basic_f32(&W, 0, 8, 8, &no_ws, s), RAFT_E_NULL);            // pointers before dimensions
+    // ---- raft_iterate_basic_f32
+    EXPECT_RC(raft_iterate_basic_f32(nullptr, f, off, 1, 8, 8, 2, &ok, f, s), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_f32(&W, nullptr, off, 1, 8, 8, 2, &ok, f, s), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_f32(&W, f, nullptr, 1, 8, 8, 2, &ok, f, s), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_f32(&W, f, off, 1, 8, 8, 2, &ok, nullptr, s), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_f32(&W, f, off, 1, 8, 8, 2, nullptr, f, s), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_f32(&W, f, off, 1, 8, 8, 2, &no_net, f, s), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_f32(&W, f, off, 1, 8, 8, 2, &no_mask, f, s), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_f32(&W, f, off, 1, 8, 8, 0, &ok, f, s), RAFT_E_SHAPE);
+    EXPECT_RC(raft_iterate_basic_f32(&W, f, off, 1, 8, 8, -3, &ok, f, s), RAFT_E_SHAPE);
+    EXPECT_RC(raft_iterate_basic_f32(&W, f, off, 1, 0, 8, 2, &ok, f, s), RAFT_E_SHAPE);
+    EXPECT_RC(raft_iterate_basic_f32(&W, f, off, 1, 8, 8, 0, &ok, nullptr, s), RAFT_E_NULL);
+    // ---- raft_iterate_basic_timed_f32
+    EXPECT_RC(raft_iterate_basic_timed_f32(nullptr, f, off, 1, 8, 8, 2, &ok, f, s, ms), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_timed_f32(&W, nullptr, off, 1, 8, 8, 2, &ok, f, s, ms), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_timed_f32(&W, f, nullptr, 1, 8, 8, 2, &ok, f, s, ms), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_timed_f32(&W, f, off, 1, 8, 8, 2, &ok, nullptr, s, ms), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_timed_f32(&W, f, off, 1, 8, 8, 2, &ok, f, s, nullptr), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_timed_f32(&W, f, off, 1, 8, 8, 2, nullptr, f, s, ms), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_timed_f32(&W, f, off, 1, 8, 8, 2, &no_mask, f, s, ms), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_timed_f32(&W, f, off, 1, 8, 8, 0, &ok, f, s, ms), RAFT_E_SHAPE);
+    EXPECT_RC(raft_iterate_basic_timed_f32(&W, f, off, 1, 8, 8, 65, &ok, f, s, ms), RAFT_E_SHAPE);
+    EXPECT_RC(raft_iterate_basic_timed_f32(&W, f, off, -1, 8, 8, 2, &ok, f, s, ms), RAFT_E_SHAPE);
+    EXPECT_RC(raft_iterate_basic_timed_f32(&W, f, off, 1, 8, 8, 65, &ok, f, s, nullptr), RAFT_E_NULL);
+    // ---- raft_iterate_basic_overlap_f32
+    EXPECT_RC(raft_iterate_basic_overlap_f32(nullptr, f, off, 1, 8, 8, 2, &ok, f, s, a0, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_overlap_f32(&W, nullptr, off, 1, 8, 8, 2, &ok, f, s, a0, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_overlap_f32(&W, f, nullptr, 1, 8, 8, 2, &ok, f, s, a0, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_overlap_f32(&W, f, off, 1, 8, 8, 2, &ok, nullptr, s, a0, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_overlap_f32(&W, f, off, 1, 8, 8, 2, &ok, f, s, nullptr, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_overlap_f32(&W, f, off, 1, 8, 8, 2, &ok, f, s, a0, nullptr, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_overlap_f32(&W, f, off, 1, 8, 8, 2, &ok, f, s, a0, a1, nullptr), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_overlap_f32(&W, f, off, 1, 8, 8, 2, &ok, f, s, s, s, nullptr), RAFT_E_NULL);   // one stream still needs a context
+    EXPECT_RC(raft_iterate_basic_overlap_f32(&W, f, off, 1, 8, 8, 2, nullptr, f, s, a0, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_overlap_f32(&W, f, off, 1, 8, 8, 2, &no_net, f, s, a0, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_overlap_f32(&W, f, off, 1, 8, 8, 2, &no_mask, f, s, s, s, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_overlap_f32(&W, f, off, 1, 8, 8, 0, &ok, f, s, a0, a1, ctx), RAFT_E_SHAPE);
+    EXPECT_RC(raft_iterate_basic_overlap_f32(&W, f, off, 1, 8, 8, -1, &ok, f, s, s, s, ctx), RAFT_E_SHAPE);
+    EXPECT_RC(raft_iterate_basic_overlap_f32(&W, f, off, 1, 8, 0, 2, &ok, f, s, a0, a1, ctx), RAFT_E_SHAPE);
+    EXPECT_RC(raft_iterate_basic_overlap_f32(&W, f, off, 1, 8, 8, 2, &ok, f, s, s, a1, ctx), RAFT_E_UNSUPPORTED);    // aux0 == stream only
+    EXPECT_RC(raft_iterate_basic_overlap_f32(&W, f, off, 1, 8, 8, 2, &ok, f, s, a0, s, ctx), RAFT_E_UNSUPPORTED);    // aux1 == stream only
+    EXPECT_RC(raft_iterate_basic_overlap_f32(&W, f, off, 1, 8, 8, 2, &ok, f, s, a0, a0, ctx), RAFT_E_UNSUPPORTED);   // aux0 == aux1 != stream
+    EXPECT_RC(raft_iterate_basic_overlap_f32(&W, f, off, 1, 8, 8, 0, &ok, f, s, a0, a0, ctx), RAFT_E_SHAPE);         // dimensions before streams
+    EXPECT_RC(raft_iterate_basic_overlap_f32(&W, f, off, 1, 8, 8, 0, &ok, f, s, a0, a0, nullptr), RAFT_E_NULL);
+    // ---- raft_iterate_basic_ondemand_f32
+    EXPECT_RC(raft_iterate_basic_ondemand_f32(nullptr, f, f, 256, 1, 8, 8, 2, &ok, f, s, a0, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_ondemand_f32(&W, nullptr, f, 256, 1, 8, 8, 2, &ok, f, s, a0, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_ondemand_f32(&W, f, nullptr, 256, 1, 8, 8, 2, &ok, f, s, a0, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_ondemand_f32(&W, f, f, 256, 1, 8, 8, 2, &ok, nullptr, s, a0, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_ondemand_f32(&W, f, f, 256, 1, 8, 8, 2, &ok, f, s, nullptr, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_ondemand_f32(&W, f, f, 256, 1, 8, 8, 2, &ok, f, s, a0, nullptr, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_ondemand_f32(&W, f, f, 256, 1, 8, 8, 2, &ok, f, s, a0, a1, nullptr), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_ondemand_f32(&W, f, f, 256, 1, 8, 8, 2, &no_ctx, f, s, a0, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_ondemand_f32(&W, f, f, 256, 1, 8, 8, 2, &no_mask, f, s, a0, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_ondemand_f32(&W, f, f, 256, 1, 8, 8, 0, &ok, f, s, a0, a1, ctx), RAFT_E_SHAPE);
+    EXPECT_RC(raft_iterate_basic_ondemand_f32(&W, f, f, 256, 0, 8, 8, 2, &ok, f, s, s, s, ctx), RAFT_E_SHAPE);
+    EXPECT_RC(raft_iterate_basic_ondemand_f32(&W, f, f, 256, 1, 8, 8, 2, &ok, f, s, s, a1, ctx), RAFT_E_UNSUPPORTED);
+    EXPECT_RC(raft_iterate_basic_ondemand_f32(&W, f, f, 256, 1, 8, 8, 2, &ok, f, s, a0, s, ctx), RAFT_E_UNSUPPORTED);
+    EXPECT_RC(raft_iterate_basic_ondemand_f32(&W, f, f, 256, 1, 8, 8, 2, &ok, f, s, a0, a0, ctx), RAFT_E_UNSUPPORTED);
+    // ---- raft_iterate_basic_final_f32
+    EXPECT_RC(raft_iterate_basic_final_f32(nullptr, f, off, 1, 8, 8, 2, &ok, f, s, a0, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_final_f32(&W, nullptr, off, 1, 8, 8, 2, &ok, f, s, a0, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_final_f32(&W, f, nullptr, 1, 8, 8, 2, &ok, f, s, a0, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_final_f32(&no_fh1, f, off, 1, 8, 8, 2, &ok, f, s, a0, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_final_f32(&no_fh1, f, off, 1, 8, 8, 2, &ok, f, s, s, s, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_final_f32(&W, f, off, 1, 8, 8, 2, &ok, nullptr, s, a0, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_final_f32(&W, f, off, 1, 8, 8, 2, &ok, f, s, nullptr, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_final_f32(&W, f, off, 1, 8, 8, 2, &ok, f, s, a0, nullptr, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_final_f32(&W, f, off, 1, 8, 8, 2, &ok, f, s, a0, a1, nullptr), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_final_f32(&W, f, off, 1, 8, 8, 2, &ok, f, s, s, s, nullptr), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_final_f32(&W, f, off, 1, 8, 8, 2, &no_mask, f, s, a0, a1, ctx), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_basic_final_f32(&W, f, off, 1, 8, 8, 0, &ok, f, s, a0, a1, ctx), RAFT_E_SHAPE);
+    EXPECT_RC(raft_iterate_basic_final_f32(&W, f, off, 1, -8, 8, 2, &ok, f, s, s, s, ctx), RAFT_E_SHAPE);
+    EXPECT_RC(raft_iterate_basic_final_f32(&W, f, off, 1, 8, 8, 2, &ok, f, s, s, a1, ctx), RAFT_E_UNSUPPORTED);
+    EXPECT_RC(raft_iterate_basic_final_f32(&W, f, off, 1, 8, 8, 2, &ok, f, s, a0, s, ctx), RAFT_E_UNSUPPORTED);
+    EXPECT_RC(raft_iterate_basic_final_f32(&W, f, off, 1, 8, 8, 2, &ok, f, s, a0, a0, ctx), RAFT_E_UNSUPPORTED);
+    EXPECT_RC(raft_iterate_basic_final_f32(&no_fh1, f, off, 1, 8, 8, 0, &ok, f, s, a0, a0, ctx), RAFT_E_NULL);
+    // ---- SmallUpdateBlock: a state without mask and GRU context is complete
+    EXPECT_RC(raft_update_small_f32(nullptr, 1, 8, 8, &ok, s), RAFT_E_NULL);
+    EXPECT_RC(raft_update_small_f32(&SW, 1, 8, 8, &no_net, s), RAFT_E_NULL);
+    EXPECT_RC(raft_update_small_f32(&SW, 0, 8, 8, &no_mask, s), RAFT_E_SHAPE);
+    EXPECT_RC(raft_iterate_small_f32(nullptr, f, off, 1, 8, 8, 2, &ok, f, s), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_small_f32(&SW, nullptr, off, 1, 8, 8, 2, &ok, f, s), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_small_f32(&SW, f, nullptr, 1, 8, 8, 2, &ok, f, s), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_small_f32(&SW, f, off, 1, 8, 8, 2, &ok, nullptr, s), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_small_f32(&SW, f, off, 1, 8, 8, 2, nullptr, f, s), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_small_f32(&SW, f, off, 1, 8, 8, 2, &no_net, f, s), RAFT_E_NULL);
+    EXPECT_RC(raft_iterate_small_f32(&SW, f, off, 1, 8, 8, 0, &no_mask, f, s), RAFT_E_SHAPE);
+    EXPECT_RC(raft_iterate_small_f32(&SW, f, off, 1, 8, 8, 0, &no_ctx, f, s), RAFT_E_SHAPE);
+    EXPECT_RC(raft_iterate_small_f32(&SW, f, off, 1, 8, 8, -1, &ok, f, s), RAFT_E_SHAPE);
+#undef EXPECT_RC
+}
+
 // every launching entry point with arguments it has to reject before any launch (no GPU is present here)
 static void rejects() {
+    loop_rejects();
     float f[64] = {0};
     int64_t off[RAFT_MAX_LEVELS + 1] = {0, 32, 64, 96, 128};
     unsigned char u8[8] = {0};

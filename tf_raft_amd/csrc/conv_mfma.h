@@ -71,6 +71,14 @@ int raft_launch_conv(const ConvArgs &a, int kh, int kw, int epi, hipStream_t s, 
 int raft_launch_conv_wino(const ConvArgs &a, int epi, hipStream_t s, WinoPlan p);                      // conv_wino.hip
 int raft_launch_conv_wino1d(const ConvArgs &a, int kh, int kw, int epi, hipStream_t s, Wino1dPlan p);   // conv_wino1d.hip
 int raft_launch_conv_wino4(const ConvArgs &a, int epi, hipStream_t s, Wino4Plan p);                    // conv_wino4.hip
+// the two special convolutions of the update blocks (conv.hip): 7x7 on the flow, relu, cout = 128 or 64; flow_head.conv2 from
+// cin = 256 or 128 channels with the coordinate update (flow2 / flow3: optional copies of the flow, NULL = none).  Hidden: the
+// library exports what it did while their only callers were part of conv.hip
+__attribute__((visibility("hidden"))) int raft_launch_conv7x7_c2(const float *flow, const float *kernel, const float *bias, int cout,
+                                                                 int B, int H, int W, float *out, int ldo, hipStream_t s);
+__attribute__((visibility("hidden"))) int raft_launch_flowhead2(const float *x, int ldx, int cin, const float *wk, const float *bias,
+                                                                int B, int H, int W, float *delta, float *coords1, float *flow,
+                                                                float *flow2, int ldf2, float *flow3, hipStream_t s);
 
 // Operand checks of every launcher: 16-byte aligned sources and weights (RAFT_E_ALIGN); each operand spans < 2 GiB (32-bit buffer
 // offsets, RAFT_E_UNSUPPORTED).  wtaps: weight taps (kernel or Winograd transform); opt: optional operands checked where present.

@@ -202,7 +202,7 @@ static inline BasicLoopPlan raft_basic_loop_plan(const raft_basic_update_weights
     // RAFT_MASK_FUSED: the prediction loops run mask.2 and the convex upsampling as one kernel.  Default: from 2 pairs (2 x 3584
     // feature pixels) on.  Launched one workgroup per tile the fused kernel only pays from 4 pairs (single pair 152.7 pairs/s with two
     // kernels, 137.8 - 142.0 fused; two pairs 210.7 / 205.4; four 282.7 / 288.4: profiles/r08k_round3_options.txt, r07q); as the
-    // 32-workgroup background branch of the three-stream loop (struct Overlap) it pays from 2 pairs: 225.5 -> 244.1 pairs/s at two,
+    // 32-workgroup background branch of the three-stream loop (update_block.hip, LoopIter::mask_bg_wgs) it pays from 2 pairs: 225.5 -> 244.1 pairs/s at two,
     // 246.3 -> 256.3 at three (profiles/r09e_small_batch_mask.txt); a single pair stays on the two-kernel path (152 - 153 against
     // 148 - 155).
     p.mask_fused = raft_opt(RAFT_OPT_MASK_FUSED, m >= 2 * 3584 ? 1 : 0) != 0 && wt.mask2.wp != nullptr && wt.mask2.npad == 576;

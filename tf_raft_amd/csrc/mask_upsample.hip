@@ -185,7 +185,7 @@ __global__ void __launch_bounds__(512) mask_upsample_kernel(MaskUpArgs p) {
 }   // namespace
 
 // mask = 0.25 * mask.2(a) (1x1, 256 -> 576) and flow_up = RAFT.upsample_flow(flow, mask) in one kernel; `a` = (B*h*w, lda) with
-// the 256 input channels first, `wp` / `bias` = mask.2 packed for the direct kernels (npad 576).  Internal (conv.hip loops).
+// the 256 input channels first, `wp` / `bias` = mask.2 packed for the direct kernels (npad 576).  Internal (update_block.hip loops).
 // max_wgs > 0: BACKGROUND mode -- at most that many workgroups, each walking several tiles.  At 448 x 512 every kernel of the
 // dependent chain has 7 * 2^k workgroups (56 feature rows), i.e. it leaves 32 of the 256 CUs idle; a mask branch of 32 long-lived
 // workgroups (95 KB of LDS each: no chain workgroup fits beside one) settles on 32 CUs and the chain takes the other 224.

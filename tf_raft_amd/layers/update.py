@@ -1,7 +1,7 @@
 """Device mirror of reference ``tf_raft/layers/update.py``: ``BasicUpdateBlock`` and
 ``SmallUpdateBlock`` with the reference's call signature
 ``block([net, inp, corr, flow]) -> (net, mask, delta_flow)``, executed by the fp32-MFMA
-convolution kernels of ``csrc/conv.hip`` through the C ABI.
+update blocks of ``csrc/update_block.hip`` (convolution launchers: ``csrc/conv.hip``) through the C ABI.
 
 The recurrent loop of the model does not go through ``__call__`` (which has to marshal the four
 inputs into the fused state buffers on every call); it drives ``raft_iterate_*`` on a persistent

@@ -307,32 +307,33 @@ class RAFT:
     def __del__(self):
         self._free_loop_context()
 
+    def _loop_streams(self, dev, plan, need_ctx=True):
+        """``(s0, s1, s2, ctx)`` of a loop: the current stream and, on the three-stream schedule, the lane's flow and mask
+        streams (events inside the library); otherwise the current stream three times = the single-stream schedule of a lane.
+        ``ctx`` is the lane's loop context; ``need_ctx=False``: only where the streams differ (else None, none is created)."""
+        s0 = _dev.stream_ptr()
+        s1, s2 = ((a.cuda_stream for a in self._aux_streams(dev, plan.lane)) if plan.three_stream else (s0, s0))
+        return s0, s1, s2, (self._loop_context(dev, plan.lane) if need_ctx or plan.three_stream else None)
+
     def _iterate(self, corr: CorrBlock, st, iters, flow_up, plan=None):
         if plan is None:                            # called on its own: lane 0 of the serial schedule
             plan = self._plan(0, self.overlap, 1)
+        s0, s1, s2, ctx = self._loop_streams(flow_up.device, plan, need_ctx=False)
         if plan.three_stream:
-            # flow branch and mask branch of every iteration on two side streams (events inside the library)
-            dev = flow_up.device
-            aux = self._aux_streams(dev, plan.lane)
+            # flow branch and mask branch of every iteration on two side streams
             check(_dev.lib().raft_iterate_basic_overlap_f32(
                 C.byref(self.update_block.c), _dev.ptr(corr._pyr), corr._off, st.B, st.h, st.w, iters, C.byref(st.c),
-                _dev.ptr(flow_up), _dev.stream_ptr(), aux[0].cuda_stream, aux[1].cuda_stream,
-                self._loop_context(dev, plan.lane)), 'iterate_basic_overlap')
+                _dev.ptr(flow_up), s0, s1, s2, ctx), 'iterate_basic_overlap')
             return
         check(_dev.lib().raft_iterate_basic_f32(C.byref(self.update_block.c), _dev.ptr(corr._pyr), corr._off,
-                                                st.B, st.h, st.w, iters, C.byref(st.c), _dev.ptr(flow_up),
-                                                _dev.stream_ptr()), 'iterate_basic')
+                                                st.B, st.h, st.w, iters, C.byref(st.c), _dev.ptr(flow_up), s0), 'iterate_basic')
 
     def _iterate_alternate(self, corr: CorrBlock, st, iters, flow_up, plan):
         if self.variant == 'raft' and self.overlap:
-            # the same C loop (three streams, or the loop's own stream three times = the single-stream schedule of a lane),
-            # lookups computed on demand from fmap1 and the pooled fmap2 pyramid; overlap=False keeps the loop below
-            dev = flow_up.device
-            s0 = _dev.stream_ptr()
-            s1, s2 = ((a.cuda_stream for a in self._aux_streams(dev, plan.lane)) if plan.three_stream else (s0, s0))
+            # the same C loop, lookups computed on demand from fmap1 and the pooled fmap2 pyramid; overlap=False keeps the loop below
             check(_dev.lib().raft_iterate_basic_ondemand_f32(
                 C.byref(self.update_block.c), _dev.ptr(corr.fmap1), _dev.ptr(corr._f2pyr), corr.fmap1.shape[-1],
-                st.B, st.h, st.w, iters, C.byref(st.c), _dev.ptr(flow_up), s0, s1, s2, self._loop_context(dev, plan.lane)),
+                st.B, st.h, st.w, iters, C.byref(st.c), _dev.ptr(flow_up), *self._loop_streams(flow_up.device, plan)),
                 'iterate_basic_ondemand')
             return
         g = st.g
@@ -438,12 +439,9 @@ class RAFT:
         B, h, w = st.B, st.h, st.w
         if final_only:
             last = out
-            # single-stream schedule (several lanes): the flow / mask "branches" are the loop's own stream
-            s0 = _dev.stream_ptr()
-            s1, s2 = ((a.cuda_stream for a in self._aux_streams(last.device, plan.lane)) if plan.three_stream else (s0, s0))
             check(_dev.lib().raft_iterate_basic_final_f32(
                 C.byref(self.update_block.c), _dev.ptr(correlation._pyr), correlation._off, B, h, w, iters, C.byref(st.c),
-                _dev.ptr(last), s0, s1, s2, self._loop_context(last.device, plan.lane)), 'iterate_basic_final')
+                _dev.ptr(last), *self._loop_streams(last.device, plan)), 'iterate_basic_final')
             self._last_correlation = correlation
             return last
         flow_up = out
