@@ -10,7 +10,7 @@
  * Conventions
  *   - plain C: raw DEVICE pointers, explicit sizes, no torch / C++ types;
  *   - all tensors are fp32, NHWC (channels contiguous), exactly the reference's layouts (the one exception: the
- *     raft_crop_or_pad_u8* entries take or return bytes, the type frames and validity masks arrive in);
+ *     raft_crop_or_pad_u8* and raft_augment_* entries take or return bytes, the type frames and validity masks arrive in);
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream); calls only
  *     enqueue work, they never synchronise and never allocate.  Two documented exceptions:
  *     raft_loop_ctx_create / _destroy, which create and destroy the four cross-stream HIP events of
@@ -69,7 +69,7 @@
 extern "C" {
 #endif
 
-#define RAFT_HIP_VERSION 221          /* 0.2.1: ABI stamp, checked by the Python binding -- bump on ANY struct / signature change */
+#define RAFT_HIP_VERSION 222          /* 0.2.2: ABI stamp, checked by the Python binding -- bump on ANY struct / signature change */
 #define RAFT_MAX_LEVELS 4
 
 enum {
@@ -193,6 +193,45 @@ int raft_stream_copy_f32(const float *src, float *dst, int64_t n, void *stream);
 int raft_crop_or_pad_f32(const float *src, float *dst, int N, int Hs, int Ws, int Ht, int Wt, int C, void *stream);
 int raft_crop_or_pad_u8_f32(const uint8_t *src, float *dst, int N, int Hs, int Ws, int Ht, int Wt, int C, void *stream);
 int raft_crop_or_pad_u8(const uint8_t *src, uint8_t *dst, int N, int Hs, int Ws, int Ht, int Wt, int C, void *stream);
+
+/* ------------------------------------------------------------------ training augmentation */
+
+/* FlowAugmentor (reference tf_raft/datasets/augmentor.py:9-129, used at dataset.py:87-91) composed into one gather: every pixel
+ * of the crop is a bilinear blend of four source pixels (cv2.resize INTER_LINEAR as restated in DESIGN.md section 10), the colour
+ * map and the eraser rectangles of frame 2 are applied to the taps, the flow is rescaled and flipped on the way.  The host draws
+ * one record per sample (tf_raft_amd/augment.py) and uploads the records; no image-sized intermediate exists.
+ * Every operation is individually rounded (no fused multiply-add), so the results are reproducible bit for bit on the host. */
+typedef struct {
+    double inv_fx, inv_fy;   /* 1 / fx, 1 / fy: source coordinate of resized index d is (float)((d + 0.5) * inv - 0.5) */
+    double fx, fy;           /* flow factors (the resize factors) */
+    double hue[2], sat[2], val[2];   /* HueSaturationValue shifts of frame 1, frame 2 */
+    float alpha[2], beta[2]; /* RandomBrightnessContrast: v * alpha + beta (beta already times 255) */
+    int32_t W1, H1;          /* size after the resize (the source size when resize == 0) */
+    int32_t x0, y0;          /* origin of the crop in the resized, flipped frame */
+    int32_t resize;          /* 0: the taps are plain copies (the reference skips cv2.resize) */
+    int32_t flip_h, flip_v;
+    int32_t color[2];        /* per frame: bit 0 brightness / contrast on, bit 1 hue / saturation / value on */
+    int32_t n_rect;          /* 0..2 eraser rectangles */
+    int32_t rect[2][4];      /* x0, y0, x1, y1 (exclusive) in SOURCE coordinates of frame 2, clipped to the frame */
+} RaftAugmentParams;
+
+#define RAFT_AUGMENT_SUM_BLOCKS 64   /* partial sums per sample */
+
+/* sizeof(RaftAugmentParams): the binding checks its mirror against it.  Host-only. */
+int raft_augment_params_bytes(void);
+
+/* Per-sample channel sums of colour-mapped frame 2 (the eraser's fill is their truncated mean): img2 (N, H, W, 3) uint8,
+ * params: N records in DEVICE memory, partial: uint32[N][RAFT_AUGMENT_SUM_BLOCKS][4], written (not accumulated) for every sample
+ * whose n_rect > 0 and left untouched for the others.  H * W <= 2^24 so that 32 bits hold a channel's sum. */
+int raft_augment_sums_u8(const uint8_t *img2, const RaftAugmentParams *params, uint32_t *partial, int N, int H, int W, void *stream);
+
+/* The gather: img1, img2 (N, H, W, 3) uint8 and flow (N, H, W, 2) float -> out1, out2 (N, h, w, 3) uint8, out_flow (N, h, w, 2)
+ * float and valid (N, h, w) float = |u| < 1000 & |v| < 1000 (dataset.py:102).  params / partial as above (partial is read only
+ * for samples whose n_rect > 0).  The records are trusted to keep every tap inside the source (tf_raft_amd/augment.py draws
+ * them so); the kernel clamps tap indices to the frame regardless.  Every output element is written exactly once. */
+int raft_augment_gather_u8(const uint8_t *img1, const uint8_t *img2, const float *flow, const RaftAugmentParams *params,
+                           const uint32_t *partial, uint8_t *out1, uint8_t *out2, float *out_flow, float *valid,
+                           int N, int H, int W, int h, int w, void *stream);
 
 /* Measurement utility (no reference counterpart): `blocks` workgroups of 256 threads, every wave issuing `iters` x 8
  * independent v_mfma_f32_16x16x4_f32 (nothing else in the loop; non-zero lane-varying operands); out: blocks * 256

@@ -11,7 +11,7 @@ import threading
 
 _LOCK = threading.Lock()
 _LIB = None
-ABI_VERSION = 221     # include/raft_hip.h RAFT_HIP_VERSION: the ctypes mirrors below describe THIS revision of the structs
+ABI_VERSION = 222     # include/raft_hip.h RAFT_HIP_VERSION: the ctypes mirrors below describe THIS revision of the structs
 
 c_float_p = C.c_void_p      # raw device pointers travel as void*
 c_i64_p = C.POINTER(C.c_int64)
@@ -53,6 +53,18 @@ class State(C.Structure):
         'net', 'x', 'corr', 'coords1', 'flow', 'delta', 'mask', 'ws', 'ctx')]
 
 
+class AugmentParams(C.Structure):
+    """``RaftAugmentParams``: one sample's record of tf_raft_amd/augment.py (include/raft_hip.h has the field notes)."""
+    _fields_ = [('inv_fx', C.c_double), ('inv_fy', C.c_double), ('fx', C.c_double), ('fy', C.c_double),
+                ('hue', C.c_double * 2), ('sat', C.c_double * 2), ('val', C.c_double * 2),
+                ('alpha', C.c_float * 2), ('beta', C.c_float * 2),
+                ('W1', C.c_int32), ('H1', C.c_int32), ('x0', C.c_int32), ('y0', C.c_int32), ('resize', C.c_int32),
+                ('flip_h', C.c_int32), ('flip_v', C.c_int32), ('color', C.c_int32 * 2), ('n_rect', C.c_int32),
+                ('rect', (C.c_int32 * 4) * 2)]
+
+
+AUGMENT_SUM_BLOCKS = 64     # RAFT_AUGMENT_SUM_BLOCKS
+
 _P = C.c_void_p
 _I = C.c_int
 _SIGNATURES = {
@@ -79,6 +91,9 @@ _SIGNATURES = {
     'raft_crop_or_pad_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'raft_crop_or_pad_u8_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'raft_crop_or_pad_u8': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    'raft_augment_params_bytes': (_I, []),
+    'raft_augment_sums_u8': (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    'raft_augment_gather_u8': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'raft_mfma_probe_f32': (_I, [_P, _I, _I, _P]),
     'raft_metrics_workspace_doubles': (C.c_int64, []),
     'raft_flow_metrics_f32': (_I, [_P, _P, _P, C.c_int64, C.c_float, _P, _P, _P]),
@@ -204,6 +219,8 @@ def load_library():
             fn = getattr(lib, name)          # AttributeError => symbol missing: fail loudly
             fn.restype = res
             fn.argtypes = args
+        if lib.raft_augment_params_bytes() != C.sizeof(AugmentParams):
+            raise RuntimeError(f'{path}: RaftAugmentParams is {lib.raft_augment_params_bytes()} bytes, its mirror {C.sizeof(AugmentParams)}')
         if lib.raft_version() != ABI_VERSION:
             raise RuntimeError(f'{path} reports ABI {lib.raft_version()}, this binding mirrors ABI {ABI_VERSION}: '
                                'rebuild the library (python -m tf_raft_amd.build --force)')

@@ -1,0 +1,261 @@
+"""``FlowAugmentor`` of reference ``tf_raft/datasets/augmentor.py:9-129`` on the device: the augmentation every training sample of the
+reference passes through (``dataset.py:87-91``), without ``cv2`` and ``albumentations``.
+
+The work is split in two.  ``draw`` makes one sample's random decisions on the host, in the reference's order and with the
+reference's ``np.random`` calls (so the generator ends in the state the reference leaves it in), and returns them as a record.
+``apply`` uploads the records of a batch once and runs two kernels (``tf_raft_amd/csrc/augment.hip``): the channel sums of
+colour-mapped frame 2 for the samples whose eraser fired, and the gather that writes both crops, the flow and ``valid``.
+Composed, the reference's chain -- colour map, erase, resize, flip, crop, flow factors -- is a gather: every pixel of the crop is a
+bilinear blend of four source pixels.  DESIGN.md section 10 states the semantics and says which are executed and which recalled.
+
+The colour-jitter parameters are ``albumentations``' own draws in the reference and do not come from ``np.random``; here they
+come from a second generator, ``photo_rng``, by the protocol of ``draw_photo`` -- the first sequence stays aligned.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _dev
+from ._ffi import AUGMENT_SUM_BLOCKS, AugmentParams, check
+from .image_ops import _on_device
+
+__all__ = ['FlowAugmentor', 'PhotoAug', 'draw_photo']
+
+
+class PhotoAug:
+    """The limits of the reference's ``A.Compose([RandomBrightnessContrast, HueSaturationValue])`` (augmentor.py:27-37); each
+    transform fires with its own ``p``."""
+
+    def __init__(self, brightness_limit, contrast_limit, hue_shift_limit, sat_shift_limit, val_shift_limit, p=0.5):
+        self.brightness_limit, self.contrast_limit = float(brightness_limit), float(contrast_limit)
+        self.hue_shift_limit, self.sat_shift_limit, self.val_shift_limit = hue_shift_limit, sat_shift_limit, val_shift_limit
+        self.p = p
+
+
+def draw_photo(photo_rng, photo_aug):
+    """One application of the colour jitter: ``{'bc': None | (alpha, beta), 'hsv': None | (hue, sat, val)}``.
+
+    The protocol (tests/augstub/albumentations follows the same one): ``rand() < p`` decides brightness / contrast, and if it
+    fires ``alpha = 1 + uniform(-contrast_limit, contrast_limit)`` then ``beta = uniform(-brightness_limit, brightness_limit)``;
+    ``rand() < p`` decides hue / saturation / value, and if it fires the three shifts are ``uniform(-limit, limit)`` in that order."""
+    out = {'bc': None, 'hsv': None}
+    if photo_rng.rand() < photo_aug.p:
+        alpha = 1.0 + photo_rng.uniform(-photo_aug.contrast_limit, photo_aug.contrast_limit)
+        beta = 0.0 + photo_rng.uniform(-photo_aug.brightness_limit, photo_aug.brightness_limit)
+        out['bc'] = (alpha, beta)
+    if photo_rng.rand() < photo_aug.p:
+        out['hsv'] = tuple(photo_rng.uniform(-lim, lim) for lim in
+                           (photo_aug.hue_shift_limit, photo_aug.sat_shift_limit, photo_aug.val_shift_limit))
+    return out
+
+
+def cv_round(x) -> int:
+    """OpenCV's ``cvRound`` of a double: to the nearest integer, halves to even."""
+    return int(np.rint(x))
+
+
+class _Staging:
+    """Pinned host buffers for the records of a call.  A buffer is reused only once the copy that read it has completed, which is
+    asked of its event without waiting; while every buffer is still in flight a new one is made."""
+
+    def __init__(self):
+        self.free = []
+
+    def upload(self, raw: bytes, device) -> torch.Tensor:
+        for k, (buf, ev) in enumerate(self.free):
+            if buf.numel() >= len(raw) and ev.query():
+                del self.free[k]
+                break
+        else:
+            buf, ev = torch.empty(max(len(raw), 4096), dtype=torch.uint8).pin_memory(), torch.cuda.Event()
+        C.memmove(buf.data_ptr(), raw, len(raw))
+        dev = buf[:len(raw)].to(device, non_blocking=True)
+        ev.record(torch.cuda.current_stream(device))
+        self.free.append((buf, ev))
+        return dev
+
+
+class FlowAugmentor:
+    """``FlowAugmentor(crop_size, min_scale=-0.2, max_scale=0.5, do_flip=True)``: the reference's constructor, attribute names and
+    probabilities (augmentor.py:10-40).
+
+    ``aug(img1, img2, flow)`` -> ``(image1 uint8, image2 uint8, flow float32)`` device tensors at ``crop_size``;
+    ``aug.batch(img1, img2, flow)`` -> ``(image1, image2, flow, valid)`` with ``valid`` float32 ``(N, h, w)`` by dataset.py:102 --
+    the tuple ``RAFT.train_step`` takes.  Inputs: uint8 ``(H, W, 3)`` and float32 ``(H, W, 2)``, or ``(N, H, W, 3)`` and
+    ``(N, H, W, 2)``, NumPy or torch, host or device; the samples of a call share one source size.
+
+    ``rng``: a ``np.random.RandomState``, or None for the global ``np.random`` (what the reference draws from).  A batch is drawn
+    sample by sample, so a batch of N equals N reference calls.  ``photo_rng``: the generator of the colour parameters (None: one
+    of its own, seeded by the system)."""
+
+    def __init__(self, crop_size, min_scale=-0.2, max_scale=0.5, do_flip=True, *, rng=None, photo_rng=None):
+        # spatial augmentation params
+        self.crop_size = tuple(int(v) for v in crop_size)
+        if len(self.crop_size) != 2 or min(self.crop_size) < 1:
+            raise ValueError(f'crop_size must be (height, width) >= 1, got {crop_size!r}')
+        self.min_scale = min_scale
+        self.max_scale = max_scale
+        self.spatial_aug_prob = 0.8
+        self.stretch_prob = 0.8
+        self.max_stretch = 0.2
+        # flip augmentation params
+        self.do_flip = do_flip
+        self.h_flip_prob = 0.5
+        self.v_flip_prob = 0.1
+        # photometric augmentation params
+        self.photo_aug = PhotoAug(brightness_limit=0.4, contrast_limit=0.4, hue_shift_limit=int(0.5 / 3.14 * 180),
+                                  sat_shift_limit=int(0.4 * 255), val_shift_limit=int(0.))
+        self.asymmetric_color_aug_prob = 0.2
+        self.eraser_aug_prob = 0.5
+        self.eraser_bounds = (50, 100)
+        self.rng = rng
+        self.photo_rng = photo_rng if photo_rng is not None else np.random.RandomState()
+        self._staging = _Staging()
+
+    # ------------------------------------------------------------------ host: the draws
+    def _check_size(self, H, W):
+        """The crop has to fit the source after the minimum scale.  The resize never goes below ``(crop + 8) / source``, but one
+        sample in five is not resized at all and its crop origin is ``randint(0, source - crop)``: the source must be larger than
+        the crop on both axes."""
+        ch, cw = self.crop_size
+        if H <= ch or W <= cw:
+            raise ValueError(f'a {ch}x{cw} crop does not fit a {H}x{W} source: the source must be larger on both axes')
+
+    def _draw_one(self, H, W):
+        rng = self.rng if self.rng is not None else np.random
+        ch, cw = self.crop_size
+        # color_transform (augmentor.py:42-59)
+        asymmetric = bool(rng.rand() < self.asymmetric_color_aug_prob)
+        photo1 = draw_photo(self.photo_rng, self.photo_aug)
+        photo2 = draw_photo(self.photo_rng, self.photo_aug) if asymmetric else photo1
+        # eraser_transform (augmentor.py:61-74)
+        rects = []
+        if rng.rand() < self.eraser_aug_prob:
+            for _ in range(rng.randint(1, 3)):
+                x0 = rng.randint(0, W)
+                y0 = rng.randint(0, H)
+                dx = rng.randint(self.eraser_bounds[0], self.eraser_bounds[1])
+                dy = rng.randint(self.eraser_bounds[0], self.eraser_bounds[1])
+                rects.append((int(x0), int(y0), int(dx), int(dy)))
+        # spatial_transform (augmentor.py:76-118)
+        min_scale = np.maximum((ch + 8) / float(H), (cw + 8) / float(W))
+        scale = 2 ** rng.uniform(self.min_scale, self.max_scale)
+        scale_x = scale
+        scale_y = scale
+        stretch = bool(rng.rand() < self.stretch_prob)
+        if stretch:
+            scale_x *= 2 ** rng.uniform(-self.max_stretch, self.max_stretch)
+            scale_y *= 2 ** rng.uniform(-self.max_stretch, self.max_stretch)
+        clipped = bool(scale_x < min_scale or scale_y < min_scale)
+        scale_x = np.clip(scale_x, min_scale, None)
+        scale_y = np.clip(scale_y, min_scale, None)
+        resize = bool(rng.rand() < self.spatial_aug_prob)
+        H1, W1 = (cv_round(H * scale_y), cv_round(W * scale_x)) if resize else (H, W)
+        flip_h = flip_v = False
+        if self.do_flip:
+            flip_h = bool(rng.rand() < self.h_flip_prob)
+            flip_v = bool(rng.rand() < self.v_flip_prob)
+        y0 = int(rng.randint(0, H1 - ch))
+        x0 = int(rng.randint(0, W1 - cw))
+        return {'asymmetric': asymmetric, 'photo': (photo1, photo2), 'rects': rects, 'scale_x': float(scale_x), 'scale_y': float(scale_y),
+                'stretch': stretch, 'clipped': clipped, 'resize': resize, 'size': (H1, W1), 'flip_h': flip_h, 'flip_v': flip_v,
+                'y0': y0, 'x0': x0, 'source': (int(H), int(W))}
+
+    def draw(self, H, W, n=1):
+        """The parameter records of ``n`` samples of ``H x W`` frames, drawn one sample after the other; touches no device."""
+        H, W, n = int(H), int(W), int(n)
+        if n < 1:
+            raise ValueError(f'n must be >= 1, got {n}')
+        self._check_size(H, W)
+        return [self._draw_one(H, W) for _ in range(n)]
+
+    # ------------------------------------------------------------------ device: the kernels
+    def _records(self, params, H, W) -> bytes:
+        ch, cw = self.crop_size
+        recs = (AugmentParams * len(params))()
+        for r, p in zip(recs, params):
+            if tuple(p['source']) != (H, W):
+                raise ValueError(f"a record drawn for {tuple(p['source'])} frames cannot be applied to {H}x{W} frames")
+            H1, W1 = p['size']
+            if not (0 <= p['y0'] <= H1 - ch and 0 <= p['x0'] <= W1 - cw):
+                raise ValueError(f"crop origin ({p['y0']}, {p['x0']}) of a {ch}x{cw} crop lies outside the {H1}x{W1} frame")
+            if len(p['rects']) > 2:
+                raise ValueError('at most two eraser rectangles per sample')
+            r.resize = int(p['resize'])
+            r.fx, r.fy = (p['scale_x'], p['scale_y']) if p['resize'] else (1.0, 1.0)
+            r.inv_fx, r.inv_fy = 1.0 / r.fx, 1.0 / r.fy
+            r.W1, r.H1, r.x0, r.y0 = W1, H1, p['x0'], p['y0']
+            r.flip_h, r.flip_v = int(p['flip_h']), int(p['flip_v'])
+            for k, ph in enumerate(p['photo']):
+                r.alpha[k], r.beta[k] = 1.0, 0.0
+                if ph['bc'] is not None:
+                    r.color[k] |= 1
+                    r.alpha[k] = np.float32(ph['bc'][0])
+                    r.beta[k] = np.float32(ph['bc'][1] * 255)
+                if ph['hsv'] is not None:
+                    r.color[k] |= 2
+                    r.hue[k], r.sat[k], r.val[k] = ph['hsv']
+            r.n_rect = len(p['rects'])
+            for k, (x0, y0, dx, dy) in enumerate(p['rects']):
+                r.rect[k][:] = [x0, y0, min(x0 + dx, W), min(y0 + dy, H)]
+        return bytes(recs)
+
+    @staticmethod
+    def _inputs(img1, img2, flow):
+        """Shape of the frames after the argument checks (``ValueError``); converts nothing."""
+        def describe(x):
+            if isinstance(x, torch.Tensor):
+                return {torch.uint8: 'uint8', torch.float32: 'float32'}.get(x.dtype, str(x.dtype)), tuple(x.shape)
+            x = np.asarray(x)
+            return x.dtype.name, tuple(x.shape)
+        (d1, s1), (d2, s2), (df, sf) = describe(img1), describe(img2), describe(flow)
+        if (d1, d2, df) != ('uint8', 'uint8', 'float32'):
+            raise ValueError(f'FlowAugmentor takes uint8 frames and a float32 flow, got {d1}, {d2}, {df}')
+        if len(s1) not in (3, 4) or s1[-1] != 3 or sf[-1:] != (2,) or 0 in s1:
+            raise ValueError(f'expected (H, W, 3) / (H, W, 2) or (N, H, W, 3) / (N, H, W, 2), got {s1}, {s2}, {sf}')
+        if s2 != s1 or sf != s1[:-1] + (2,):
+            raise ValueError(f'the frames and the flow of a call share one size, got {s1}, {s2}, {sf}')
+        return s1
+
+    def apply(self, params, img1, img2, flow):
+        """Run the kernels with given records (one per sample) -> ``(image1, image2, flow, valid)`` on the device, with a leading
+        batch axis exactly when the inputs have one.  Current stream; no synchronisation, nothing returns to the host."""
+        shape = self._inputs(img1, img2, flow)
+        single = len(shape) == 3
+        N, (H, W) = (1 if single else shape[0]), shape[-3:-1]
+        if len(params) != N:
+            raise ValueError(f'{len(params)} records for {N} samples')
+        raw = self._records(params, H, W)
+        ch, cw = self.crop_size
+        img1, img2, flow = _on_device(img1), _on_device(img2), _on_device(flow)
+        dev = img1.device
+        if img2.device != dev or flow.device != dev:
+            raise ValueError('the frames and the flow must be on one device')
+        lib = _dev.lib()
+        with torch.cuda.device(dev):
+            recs = self._staging.upload(raw, dev)
+            partial = torch.empty((N, AUGMENT_SUM_BLOCKS, 4), dtype=torch.int32, device=dev)
+            out1 = torch.empty((N, ch, cw, 3), dtype=torch.uint8, device=dev)
+            out2 = torch.empty((N, ch, cw, 3), dtype=torch.uint8, device=dev)
+            oflow = torch.empty((N, ch, cw, 2), dtype=torch.float32, device=dev)
+            valid = torch.empty((N, ch, cw), dtype=torch.float32, device=dev)
+            stream = _dev.stream_ptr()
+            if any(p['rects'] for p in params):
+                check(lib.raft_augment_sums_u8(_dev.ptr(img2), _dev.ptr(recs), _dev.ptr(partial), N, H, W, stream), 'augment_sums')
+            check(lib.raft_augment_gather_u8(_dev.ptr(img1), _dev.ptr(img2), _dev.ptr(flow), _dev.ptr(recs), _dev.ptr(partial),
+                                             _dev.ptr(out1), _dev.ptr(out2), _dev.ptr(oflow), _dev.ptr(valid), N, H, W, ch, cw, stream),
+                  'augment_gather')
+        outs = (out1, out2, oflow, valid)
+        return tuple(_dev.wrap(o[0] if single else o) for o in outs)
+
+    def batch(self, img1, img2, flow):
+        """``(image1, image2, flow, valid)``: what ``RAFT.train_step`` takes."""
+        shape = self._inputs(img1, img2, flow)
+        H, W = shape[-3:-1]
+        return self.apply(self.draw(H, W, 1 if len(shape) == 3 else shape[0]), img1, img2, flow)
+
+    def __call__(self, img1, img2, flow):
+        return self.batch(img1, img2, flow)[:3]

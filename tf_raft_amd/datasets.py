@@ -1,6 +1,6 @@
 """Mirror of the batch-shaping stages of reference ``tf_raft/datasets/dataset.py`` that sit between a data set and the model:
 ``CropOrPadder`` (dataset.py:323-334) and ``ShapeSetter`` (dataset.py:309-316), as used by train_sintel.py:52-56, 72-75.
-The data-set readers and the augmentation are out of scope.
+The augmentation is ``tf_raft_amd/augment.py``; the data-set readers are out of scope.
 """
 from __future__ import annotations
 

@@ -1,0 +1,87 @@
+"""Measurements behind docs/NOTEBOOK.md section 15 (device-side FlowAugmentor).
+
+  python tools/augment_bench.py [--reps 200] [--warmup 20]
+      augmented pairs/s of `FlowAugmentor.batch` at batch 4 and the reference's training crop 368 x 496, from device-resident
+      uint8 frames of MPI-Sintel (436 x 1024) and FlyingChairs (384 x 512) size.  Per shape: the whole call (host draws + record
+      upload + two launches) timed with device events around `reps` back-to-back calls, as the median of five such windows after a
+      warm-up; the two kernels alone (fixed records, no host draw), the same way; and the host time of the draws alone.
+  python tools/augment_bench.py trace
+      a few calls per shape and nothing else, meant to run under `rocprofv3 --kernel-trace --memory-copy-trace --stats -- python ...`:
+      the structural claim is two launches and one small upload per batch.
+"""
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tf_raft_amd.augment import FlowAugmentor       # noqa: E402
+
+SHAPES = (('sintel', 436, 1024), ('chairs', 384, 512))
+CROP, BATCH = (368, 496), 4
+
+
+def inputs(H, W):
+    g = torch.Generator(device='cuda').manual_seed(0)
+    i1 = torch.randint(0, 256, (BATCH, H, W, 3), dtype=torch.uint8, device='cuda', generator=g)
+    i2 = torch.randint(0, 256, (BATCH, H, W, 3), dtype=torch.uint8, device='cuda', generator=g)
+    fl = torch.randn((BATCH, H, W, 2), device='cuda', generator=g) * 20
+    return i1, i2, fl
+
+
+def windows(fn, reps, n=5):
+    """Median over n windows of the device time of `reps` back-to-back calls, in microseconds per call."""
+    out = []
+    for _ in range(n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1) / reps * 1e3)
+    return float(np.median(out)), min(out), max(out)
+
+
+def bench(reps, warmup):
+    for name, H, W in SHAPES:
+        aug = FlowAugmentor(CROP, rng=np.random.RandomState(0), photo_rng=np.random.RandomState(1))
+        i1, i2, fl = inputs(H, W)
+        for _ in range(warmup):
+            aug.batch(i1, i2, fl)
+        torch.cuda.synchronize()
+        call = windows(lambda: aug.batch(i1, i2, fl), reps)
+        # the kernels alone: every fixed batch of records has its own mix of resize / colour / eraser work, so take several
+        kernel = []
+        for _ in range(8):
+            recs = aug.draw(H, W, BATCH)
+            aug.apply(recs, i1, i2, fl)
+            kernel.append(windows(lambda: aug.apply(recs, i1, i2, fl), reps, n=3)[0])
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            aug.draw(H, W, BATCH)
+        host = (time.perf_counter() - t0) / reps * 1e6
+        print(f'{name} {H}x{W} -> {CROP[0]}x{CROP[1]} batch {BATCH}: call {call[0]:.1f} us per batch (windows {call[1]:.1f} .. {call[2]:.1f}) = '
+              f'{BATCH / call[0] * 1e6:.0f} augmented pairs/s; apply with fixed records {np.median(kernel):.1f} us '
+              f'({min(kernel):.1f} .. {max(kernel):.1f} over 8 record sets); host draws alone {host:.1f} us per batch', flush=True)
+
+
+def trace():
+    for name, H, W in SHAPES:
+        aug = FlowAugmentor(CROP, rng=np.random.RandomState(0), photo_rng=np.random.RandomState(1))
+        i1, i2, fl = inputs(H, W)
+        torch.cuda.synchronize()
+        for _ in range(10):
+            aug.batch(i1, i2, fl)
+        torch.cuda.synchronize()
+        print(f'{name}: 10 batches of {BATCH}', flush=True)
+
+
+if __name__ == '__main__':
+    args = sys.argv[1:]
+    if args[:1] == ['trace']:
+        trace()
+    else:
+        bench(int(args[args.index('--reps') + 1]) if '--reps' in args else 200, int(args[args.index('--warmup') + 1]) if '--warmup' in args else 20)
