@@ -196,7 +196,8 @@ int raft_crop_or_pad_u8(const uint8_t *src, uint8_t *dst, int N, int Hs, int Ws,
 
 /* ------------------------------------------------------------------ training augmentation */
 
-/* FlowAugmentor (reference tf_raft/datasets/augmentor.py:9-129, used at dataset.py:87-91) composed into one gather: every pixel
+/* FlowAugmentor (reference tf_raft/datasets/augmentor.py:9-129, used at dataset.py:87-91) composed into one gather (the sparse
+ * augmentor shares the record and the frame path, see raft_augment_gather_sparse_u8): every pixel
  * of the crop is a bilinear blend of four source pixels (cv2.resize INTER_LINEAR as restated in DESIGN.md section 10), the colour
  * map and the eraser rectangles of frame 2 are applied to the taps, the flow is rescaled and flipped on the way.  The host draws
  * one record per sample (tf_raft_amd/augment.py) and uploads the records; no image-sized intermediate exists.
@@ -232,6 +233,20 @@ int raft_augment_sums_u8(const uint8_t *img2, const RaftAugmentParams *params, u
 int raft_augment_gather_u8(const uint8_t *img1, const uint8_t *img2, const float *flow, const RaftAugmentParams *params,
                            const uint32_t *partial, uint8_t *out1, uint8_t *out2, float *out_flow, float *valid,
                            int N, int H, int W, int h, int w, void *stream);
+
+/* SparseFlowAugmentor (reference tf_raft/datasets/augmentor.py:132-267, used at dataset.py:88-89): the frames as above; flow and
+ * validity of a resized sample by the reference's scatter (resize_sparse_flow_map) restated as a gather.  A
+ * valid source (x, y) lands on (rint(x f), rint(y f)) in double, halves to even, with f = params.fx for both axes; output pixel
+ * (X, Y) of the resized frame takes, of the sources with valid_in >= 1 that land on it, the last in row-major order: flow
+ * (float)((double)flow * f) and valid 1; without such a source, or with X == 0 or Y == 0, flow 0 and valid 0.  A sample that is not
+ * resized copies flow and valid_in as they are.  The horizontal flip negates u; flip_v is not read.  valid_in (N, H, W) float,
+ * valid_out (N, h, w) float; the rest as for raft_augment_gather_u8.  f >= 1/8 is the caller's promise (tf_raft_amd/augment.py
+ * checks it): the kernel looks no further than 5 sources beyond X / f.  No atomics, no intermediate; every output element is
+ * written exactly once.  Argument errors as for the dense entry: RAFT_E_NULL (-1) for a null pointer, RAFT_E_SHAPE (-2) for a
+ * bad size, H * W or h * w > 2^24, or N > 65535, and RAFT_E_ALIGN when flow is not 8-byte aligned (it is read as float2). */
+int raft_augment_gather_sparse_u8(const uint8_t *img1, const uint8_t *img2, const float *flow, const float *valid_in,
+                                  const RaftAugmentParams *params, const uint32_t *partial, uint8_t *out1, uint8_t *out2,
+                                  float *out_flow, float *valid_out, int N, int H, int W, int h, int w, void *stream);
 
 /* Measurement utility (no reference counterpart): `blocks` workgroups of 256 threads, every wave issuing `iters` x 8
  * independent v_mfma_f32_16x16x4_f32 (nothing else in the loop; non-zero lane-varying operands); out: blocks * 256

@@ -94,6 +94,7 @@ _SIGNATURES = {
     'raft_augment_params_bytes': (_I, []),
     'raft_augment_sums_u8': (_I, [_P, _P, _P, _I, _I, _I, _P]),
     'raft_augment_gather_u8': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    'raft_augment_gather_sparse_u8': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'raft_mfma_probe_f32': (_I, [_P, _I, _I, _P]),
     'raft_metrics_workspace_doubles': (C.c_int64, []),
     'raft_flow_metrics_f32': (_I, [_P, _P, _P, C.c_int64, C.c_float, _P, _P, _P]),

@@ -1,5 +1,6 @@
-"""``FlowAugmentor`` of reference ``tf_raft/datasets/augmentor.py:9-129`` on the device: the augmentation every training sample of the
-reference passes through (``dataset.py:87-91``), without ``cv2`` and ``albumentations``.
+"""``FlowAugmentor`` and ``SparseFlowAugmentor`` of reference ``tf_raft/datasets/augmentor.py`` on the device: the augmentation every
+training sample of the reference passes through (``dataset.py:87-91``; the sparse one for KITTI and HD1K), without ``cv2`` and
+``albumentations``.
 
 The work is split in two.  ``draw`` makes one sample's random decisions on the host, in the reference's order and with the
 reference's ``np.random`` calls (so the generator ends in the state the reference leaves it in), and returns them as a record.
@@ -7,6 +8,8 @@ reference's ``np.random`` calls (so the generator ends in the state the referenc
 colour-mapped frame 2 for the samples whose eraser fired, and the gather that writes both crops, the flow and ``valid``.
 Composed, the reference's chain -- colour map, erase, resize, flip, crop, flow factors -- is a gather: every pixel of the crop is a
 bilinear blend of four source pixels.  DESIGN.md section 10 states the semantics and says which are executed and which recalled.
+The sparse augmentor shares the host code and the frame path; its flow resize, a scatter in the reference, is a gather as well
+(DESIGN.md section 11).
 
 The colour-jitter parameters are ``albumentations``' own draws in the reference and do not come from ``np.random``; here they
 come from a second generator, ``photo_rng``, by the protocol of ``draw_photo`` -- the first sequence stays aligned.
@@ -22,7 +25,7 @@ from . import _dev
 from ._ffi import AUGMENT_SUM_BLOCKS, AugmentParams, check
 from .image_ops import _on_device
 
-__all__ = ['FlowAugmentor', 'PhotoAug', 'draw_photo']
+__all__ = ['FlowAugmentor', 'SparseFlowAugmentor', 'PhotoAug', 'draw_photo']
 
 
 class PhotoAug:
@@ -78,7 +81,138 @@ class _Staging:
         return dev
 
 
-class FlowAugmentor:
+class _Augmentor:
+    """What the two augmentors share on the host: the constructor's common part, the eraser's draws, the record of a sample, the
+    argument checks, the staging and the launches.  A subclass draws (``_check_size``, ``_draw_one``) and names its gather."""
+
+    _name = ''
+    _gather = ''                # the entry point of the gather
+    _label = ''                 # what an error of that entry is reported under
+
+    def _setup(self, crop_size, min_scale, max_scale, do_flip, rng, photo_rng):
+        self.crop_size = tuple(int(v) for v in crop_size)
+        if len(self.crop_size) != 2 or min(self.crop_size) < 1:
+            raise ValueError(f'crop_size must be (height, width) >= 1, got {crop_size!r}')
+        self.min_scale = min_scale
+        self.max_scale = max_scale
+        self.do_flip = do_flip
+        self.eraser_bounds = (50, 100)
+        self.rng = rng
+        self.photo_rng = photo_rng if photo_rng is not None else np.random.RandomState()
+        self._staging = _Staging()
+
+    # ------------------------------------------------------------------ host: the draws
+    def _draw_rects(self, rng, H, W):
+        """eraser_transform (augmentor.py:61-74, 170-181)."""
+        rects = []
+        if rng.rand() < self.eraser_aug_prob:
+            for _ in range(rng.randint(1, 3)):
+                x0 = rng.randint(0, W)
+                y0 = rng.randint(0, H)
+                dx = rng.randint(self.eraser_bounds[0], self.eraser_bounds[1])
+                dy = rng.randint(self.eraser_bounds[0], self.eraser_bounds[1])
+                rects.append((int(x0), int(y0), int(dx), int(dy)))
+        return rects
+
+    def draw(self, H, W, n=1):
+        """The parameter records of ``n`` samples of ``H x W`` frames, drawn one sample after the other; touches no device."""
+        H, W, n = int(H), int(W), int(n)
+        if n < 1:
+            raise ValueError(f'n must be >= 1, got {n}')
+        self._check_size(H, W)
+        return [self._draw_one(H, W) for _ in range(n)]
+
+    # ------------------------------------------------------------------ device: the kernels
+    def _check_record(self, p):
+        pass
+
+    def _records(self, params, H, W) -> bytes:
+        ch, cw = self.crop_size
+        recs = (AugmentParams * len(params))()
+        for r, p in zip(recs, params):
+            if tuple(p['source']) != (H, W):
+                raise ValueError(f"a record drawn for {tuple(p['source'])} frames cannot be applied to {H}x{W} frames")
+            H1, W1 = p['size']
+            if not (0 <= p['y0'] <= H1 - ch and 0 <= p['x0'] <= W1 - cw):
+                raise ValueError(f"crop origin ({p['y0']}, {p['x0']}) of a {ch}x{cw} crop lies outside the {H1}x{W1} frame")
+            if len(p['rects']) > 2:
+                raise ValueError('at most two eraser rectangles per sample')
+            self._check_record(p)
+            r.resize = int(p['resize'])
+            r.fx, r.fy = (p['scale_x'], p['scale_y']) if p['resize'] else (1.0, 1.0)
+            r.inv_fx, r.inv_fy = 1.0 / r.fx, 1.0 / r.fy
+            r.W1, r.H1, r.x0, r.y0 = W1, H1, p['x0'], p['y0']
+            r.flip_h, r.flip_v = int(p['flip_h']), int(p['flip_v'])
+            for k, ph in enumerate(p['photo']):
+                r.alpha[k], r.beta[k] = 1.0, 0.0
+                if ph['bc'] is not None:
+                    r.color[k] |= 1
+                    r.alpha[k] = np.float32(ph['bc'][0])
+                    r.beta[k] = np.float32(ph['bc'][1] * 255)
+                if ph['hsv'] is not None:
+                    r.color[k] |= 2
+                    r.hue[k], r.sat[k], r.val[k] = ph['hsv']
+            r.n_rect = len(p['rects'])
+            for k, (x0, y0, dx, dy) in enumerate(p['rects']):
+                r.rect[k][:] = [x0, y0, min(x0 + dx, W), min(y0 + dy, H)]
+        return bytes(recs)
+
+    @classmethod
+    def _inputs(cls, img1, img2, flow, *valid):
+        """Shape of the frames after the argument checks (``ValueError``); converts nothing."""
+        def describe(x):
+            if isinstance(x, torch.Tensor):
+                return {torch.uint8: 'uint8', torch.float32: 'float32'}.get(x.dtype, str(x.dtype)), tuple(x.shape)
+            x = np.asarray(x)
+            return x.dtype.name, tuple(x.shape)
+        (d1, s1), (d2, s2), (df, sf) = describe(img1), describe(img2), describe(flow)
+        if (d1, d2, df) != ('uint8', 'uint8', 'float32'):
+            raise ValueError(f'{cls._name} takes uint8 frames and a float32 flow, got {d1}, {d2}, {df}')
+        if len(s1) not in (3, 4) or s1[-1] != 3 or sf[-1:] != (2,) or 0 in s1:
+            raise ValueError(f'expected (H, W, 3) / (H, W, 2) or (N, H, W, 3) / (N, H, W, 2), got {s1}, {s2}, {sf}')
+        if s2 != s1 or sf != s1[:-1] + (2,):
+            raise ValueError(f'the frames and the flow of a call share one size, got {s1}, {s2}, {sf}')
+        for v in valid:
+            dv, sv = describe(v)
+            if dv != 'float32':
+                raise ValueError(f'{cls._name} takes a float32 validity map, got {dv}')
+            if sv != s1[:-1]:
+                raise ValueError(f'the validity map has the size of the frames, {s1[:-1]}, got {sv}')
+        return s1
+
+    def _run(self, params, img1, img2, flow, *valid):
+        shape = self._inputs(img1, img2, flow, *valid)
+        single = len(shape) == 3
+        N, (H, W) = (1 if single else shape[0]), shape[-3:-1]
+        if len(params) != N:
+            raise ValueError(f'{len(params)} records for {N} samples')
+        raw = self._records(params, H, W)
+        ch, cw = self.crop_size
+        img1, img2, flow = _on_device(img1), _on_device(img2), _on_device(flow)
+        valid = tuple(_on_device(v) for v in valid)
+        dev = img1.device
+        if any(t.device != dev for t in (img2, flow, *valid)):
+            raise ValueError('the frames, the flow and the validity map must be on one device' if valid else
+                             'the frames and the flow must be on one device')
+        lib = _dev.lib()
+        with torch.cuda.device(dev):
+            recs = self._staging.upload(raw, dev)
+            partial = torch.empty((N, AUGMENT_SUM_BLOCKS, 4), dtype=torch.int32, device=dev)
+            out1 = torch.empty((N, ch, cw, 3), dtype=torch.uint8, device=dev)
+            out2 = torch.empty((N, ch, cw, 3), dtype=torch.uint8, device=dev)
+            oflow = torch.empty((N, ch, cw, 2), dtype=torch.float32, device=dev)
+            ovalid = torch.empty((N, ch, cw), dtype=torch.float32, device=dev)
+            stream = _dev.stream_ptr()
+            if any(p['rects'] for p in params):
+                check(lib.raft_augment_sums_u8(_dev.ptr(img2), _dev.ptr(recs), _dev.ptr(partial), N, H, W, stream), 'augment_sums')
+            check(getattr(lib, self._gather)(_dev.ptr(img1), _dev.ptr(img2), _dev.ptr(flow), *(_dev.ptr(v) for v in valid), _dev.ptr(recs),
+                                             _dev.ptr(partial), _dev.ptr(out1), _dev.ptr(out2), _dev.ptr(oflow), _dev.ptr(ovalid),
+                                             N, H, W, ch, cw, stream), self._label)
+        outs = (out1, out2, oflow, ovalid)
+        return tuple(_dev.wrap(o[0] if single else o) for o in outs)
+
+
+class FlowAugmentor(_Augmentor):
     """``FlowAugmentor(crop_size, min_scale=-0.2, max_scale=0.5, do_flip=True)``: the reference's constructor, attribute names and
     probabilities (augmentor.py:10-40).
 
@@ -91,18 +225,17 @@ class FlowAugmentor:
     sample by sample, so a batch of N equals N reference calls.  ``photo_rng``: the generator of the colour parameters (None: one
     of its own, seeded by the system)."""
 
+    _name = 'FlowAugmentor'
+    _gather = 'raft_augment_gather_u8'
+    _label = 'augment_gather'
+
     def __init__(self, crop_size, min_scale=-0.2, max_scale=0.5, do_flip=True, *, rng=None, photo_rng=None):
+        self._setup(crop_size, min_scale, max_scale, do_flip, rng, photo_rng)
         # spatial augmentation params
-        self.crop_size = tuple(int(v) for v in crop_size)
-        if len(self.crop_size) != 2 or min(self.crop_size) < 1:
-            raise ValueError(f'crop_size must be (height, width) >= 1, got {crop_size!r}')
-        self.min_scale = min_scale
-        self.max_scale = max_scale
         self.spatial_aug_prob = 0.8
         self.stretch_prob = 0.8
         self.max_stretch = 0.2
         # flip augmentation params
-        self.do_flip = do_flip
         self.h_flip_prob = 0.5
         self.v_flip_prob = 0.1
         # photometric augmentation params
@@ -110,12 +243,7 @@ class FlowAugmentor:
                                   sat_shift_limit=int(0.4 * 255), val_shift_limit=int(0.))
         self.asymmetric_color_aug_prob = 0.2
         self.eraser_aug_prob = 0.5
-        self.eraser_bounds = (50, 100)
-        self.rng = rng
-        self.photo_rng = photo_rng if photo_rng is not None else np.random.RandomState()
-        self._staging = _Staging()
 
-    # ------------------------------------------------------------------ host: the draws
     def _check_size(self, H, W):
         """The crop has to fit the source after the minimum scale.  The resize never goes below ``(crop + 8) / source``, but one
         sample in five is not resized at all and its crop origin is ``randint(0, source - crop)``: the source must be larger than
@@ -131,15 +259,7 @@ class FlowAugmentor:
         asymmetric = bool(rng.rand() < self.asymmetric_color_aug_prob)
         photo1 = draw_photo(self.photo_rng, self.photo_aug)
         photo2 = draw_photo(self.photo_rng, self.photo_aug) if asymmetric else photo1
-        # eraser_transform (augmentor.py:61-74)
-        rects = []
-        if rng.rand() < self.eraser_aug_prob:
-            for _ in range(rng.randint(1, 3)):
-                x0 = rng.randint(0, W)
-                y0 = rng.randint(0, H)
-                dx = rng.randint(self.eraser_bounds[0], self.eraser_bounds[1])
-                dy = rng.randint(self.eraser_bounds[0], self.eraser_bounds[1])
-                rects.append((int(x0), int(y0), int(dx), int(dy)))
+        rects = self._draw_rects(rng, H, W)
         # spatial_transform (augmentor.py:76-118)
         min_scale = np.maximum((ch + 8) / float(H), (cw + 8) / float(W))
         scale = 2 ** rng.uniform(self.min_scale, self.max_scale)
@@ -164,92 +284,10 @@ class FlowAugmentor:
                 'stretch': stretch, 'clipped': clipped, 'resize': resize, 'size': (H1, W1), 'flip_h': flip_h, 'flip_v': flip_v,
                 'y0': y0, 'x0': x0, 'source': (int(H), int(W))}
 
-    def draw(self, H, W, n=1):
-        """The parameter records of ``n`` samples of ``H x W`` frames, drawn one sample after the other; touches no device."""
-        H, W, n = int(H), int(W), int(n)
-        if n < 1:
-            raise ValueError(f'n must be >= 1, got {n}')
-        self._check_size(H, W)
-        return [self._draw_one(H, W) for _ in range(n)]
-
-    # ------------------------------------------------------------------ device: the kernels
-    def _records(self, params, H, W) -> bytes:
-        ch, cw = self.crop_size
-        recs = (AugmentParams * len(params))()
-        for r, p in zip(recs, params):
-            if tuple(p['source']) != (H, W):
-                raise ValueError(f"a record drawn for {tuple(p['source'])} frames cannot be applied to {H}x{W} frames")
-            H1, W1 = p['size']
-            if not (0 <= p['y0'] <= H1 - ch and 0 <= p['x0'] <= W1 - cw):
-                raise ValueError(f"crop origin ({p['y0']}, {p['x0']}) of a {ch}x{cw} crop lies outside the {H1}x{W1} frame")
-            if len(p['rects']) > 2:
-                raise ValueError('at most two eraser rectangles per sample')
-            r.resize = int(p['resize'])
-            r.fx, r.fy = (p['scale_x'], p['scale_y']) if p['resize'] else (1.0, 1.0)
-            r.inv_fx, r.inv_fy = 1.0 / r.fx, 1.0 / r.fy
-            r.W1, r.H1, r.x0, r.y0 = W1, H1, p['x0'], p['y0']
-            r.flip_h, r.flip_v = int(p['flip_h']), int(p['flip_v'])
-            for k, ph in enumerate(p['photo']):
-                r.alpha[k], r.beta[k] = 1.0, 0.0
-                if ph['bc'] is not None:
-                    r.color[k] |= 1
-                    r.alpha[k] = np.float32(ph['bc'][0])
-                    r.beta[k] = np.float32(ph['bc'][1] * 255)
-                if ph['hsv'] is not None:
-                    r.color[k] |= 2
-                    r.hue[k], r.sat[k], r.val[k] = ph['hsv']
-            r.n_rect = len(p['rects'])
-            for k, (x0, y0, dx, dy) in enumerate(p['rects']):
-                r.rect[k][:] = [x0, y0, min(x0 + dx, W), min(y0 + dy, H)]
-        return bytes(recs)
-
-    @staticmethod
-    def _inputs(img1, img2, flow):
-        """Shape of the frames after the argument checks (``ValueError``); converts nothing."""
-        def describe(x):
-            if isinstance(x, torch.Tensor):
-                return {torch.uint8: 'uint8', torch.float32: 'float32'}.get(x.dtype, str(x.dtype)), tuple(x.shape)
-            x = np.asarray(x)
-            return x.dtype.name, tuple(x.shape)
-        (d1, s1), (d2, s2), (df, sf) = describe(img1), describe(img2), describe(flow)
-        if (d1, d2, df) != ('uint8', 'uint8', 'float32'):
-            raise ValueError(f'FlowAugmentor takes uint8 frames and a float32 flow, got {d1}, {d2}, {df}')
-        if len(s1) not in (3, 4) or s1[-1] != 3 or sf[-1:] != (2,) or 0 in s1:
-            raise ValueError(f'expected (H, W, 3) / (H, W, 2) or (N, H, W, 3) / (N, H, W, 2), got {s1}, {s2}, {sf}')
-        if s2 != s1 or sf != s1[:-1] + (2,):
-            raise ValueError(f'the frames and the flow of a call share one size, got {s1}, {s2}, {sf}')
-        return s1
-
     def apply(self, params, img1, img2, flow):
         """Run the kernels with given records (one per sample) -> ``(image1, image2, flow, valid)`` on the device, with a leading
         batch axis exactly when the inputs have one.  Current stream; no synchronisation, nothing returns to the host."""
-        shape = self._inputs(img1, img2, flow)
-        single = len(shape) == 3
-        N, (H, W) = (1 if single else shape[0]), shape[-3:-1]
-        if len(params) != N:
-            raise ValueError(f'{len(params)} records for {N} samples')
-        raw = self._records(params, H, W)
-        ch, cw = self.crop_size
-        img1, img2, flow = _on_device(img1), _on_device(img2), _on_device(flow)
-        dev = img1.device
-        if img2.device != dev or flow.device != dev:
-            raise ValueError('the frames and the flow must be on one device')
-        lib = _dev.lib()
-        with torch.cuda.device(dev):
-            recs = self._staging.upload(raw, dev)
-            partial = torch.empty((N, AUGMENT_SUM_BLOCKS, 4), dtype=torch.int32, device=dev)
-            out1 = torch.empty((N, ch, cw, 3), dtype=torch.uint8, device=dev)
-            out2 = torch.empty((N, ch, cw, 3), dtype=torch.uint8, device=dev)
-            oflow = torch.empty((N, ch, cw, 2), dtype=torch.float32, device=dev)
-            valid = torch.empty((N, ch, cw), dtype=torch.float32, device=dev)
-            stream = _dev.stream_ptr()
-            if any(p['rects'] for p in params):
-                check(lib.raft_augment_sums_u8(_dev.ptr(img2), _dev.ptr(recs), _dev.ptr(partial), N, H, W, stream), 'augment_sums')
-            check(lib.raft_augment_gather_u8(_dev.ptr(img1), _dev.ptr(img2), _dev.ptr(flow), _dev.ptr(recs), _dev.ptr(partial),
-                                             _dev.ptr(out1), _dev.ptr(out2), _dev.ptr(oflow), _dev.ptr(valid), N, H, W, ch, cw, stream),
-                  'augment_gather')
-        outs = (out1, out2, oflow, valid)
-        return tuple(_dev.wrap(o[0] if single else o) for o in outs)
+        return self._run(params, img1, img2, flow)
 
     def batch(self, img1, img2, flow):
         """``(image1, image2, flow, valid)``: what ``RAFT.train_step`` takes."""
@@ -259,3 +297,97 @@ class FlowAugmentor:
 
     def __call__(self, img1, img2, flow):
         return self.batch(img1, img2, flow)[:3]
+
+
+MIN_SPARSE_FACTOR = 1.0 / 8     # the sparse gather looks ceil(0.5 / f) + 1 <= 5 sources beyond X / f (csrc/augment.hip)
+SPARSE_MARGIN = (20, 50)        # margin_y, margin_x of the sparse crop origin's draw (augmentor.py:242-243)
+
+
+class SparseFlowAugmentor(_Augmentor):
+    """``SparseFlowAugmentor(crop_size, min_scale=-0.2, max_scale=0.5, do_flip=False)``: the reference's constructor, attribute names
+    and values (augmentor.py:132-161), for sparse ground truth (KITTI, HD1K: dataset.py:36-37, 88-89).
+
+    ``aug(img1, img2, flow, valid)`` and ``aug.batch(...)`` -> ``(image1 uint8, image2 uint8, flow float32, valid float32)`` device
+    tensors at ``crop_size``, as the reference's call returns all four.  ``valid``: float32 ``(H, W)`` or ``(N, H, W)``; the other
+    inputs, ``rng`` and ``photo_rng`` as for ``FlowAugmentor``.
+
+    One colour application serves both frames, one factor both axes, there is no vertical flip, and the crop origin is drawn beyond
+    the frame and clipped into it.  A resized sample takes flow and validity through ``resize_sparse_flow_map`` (augmentor.py:183-215):
+    every source with ``valid >= 1`` lands on ``(rint(x f), rint(y f))``, targets in row or column 0 are dropped, and of several
+    sources on one target the last in row-major order stays -- computed per output pixel as a gather."""
+
+    _name = 'SparseFlowAugmentor'
+    _gather = 'raft_augment_gather_sparse_u8'
+    _label = 'augment_gather_sparse'
+
+    def __init__(self, crop_size, min_scale=-0.2, max_scale=0.5, do_flip=False, *, rng=None, photo_rng=None):
+        self._setup(crop_size, min_scale, max_scale, do_flip, rng, photo_rng)
+        # spatial augmentation params
+        self.spatial_aug_prob = 0.8
+        self.stretch_prob = 0.8             # the reference keeps these two and never reads them
+        self.max_stretch = 0.2
+        # flip augmentation params
+        self.h_flip_prob = 0.5
+        self.v_flip_prob = 0.1              # never read by the reference either: there is no vertical flip
+        # photometric augmentation params
+        self.photo_aug = PhotoAug(brightness_limit=0.3, contrast_limit=0.3, hue_shift_limit=int(0.3 / 3.14 * 180),
+                                  sat_shift_limit=int(0.3 * 255), val_shift_limit=int(0.))
+        self.asymmetric_color_aug_prob = 0.2
+        self.eraser_aug_prob = 0.5
+
+    def _min_clip(self, H, W):
+        ch, cw = self.crop_size
+        return np.maximum((ch + 1) / float(H), (cw + 1) / float(W))
+
+    def _check_size(self, H, W):
+        """The crop origin is clipped into the frame, so a source of the crop's own size is legal (every resize then enlarges it);
+        a smaller one is not.  The smallest factor the draws can give is known beforehand and has to stay in the gather's reach."""
+        ch, cw = self.crop_size
+        if H < ch or W < cw:
+            raise ValueError(f'a {ch}x{cw} crop does not fit a {H}x{W} source')
+        lowest = max(2.0 ** min(self.min_scale, self.max_scale), float(self._min_clip(H, W)))
+        if not lowest >= MIN_SPARSE_FACTOR:
+            raise ValueError(f'scale exponents ({self.min_scale}, {self.max_scale}) allow a factor of {lowest:g}, below 1/8')
+
+    def _check_record(self, p):
+        if p['scale_x'] != p['scale_y'] or p['flip_v']:
+            raise ValueError('a sparse record has one factor for both axes and no vertical flip')
+        if p['resize'] and not p['scale_x'] >= MIN_SPARSE_FACTOR:
+            raise ValueError(f"factor {p['scale_x']:g} is below 1/8")
+        if p['photo'][0] != p['photo'][1]:
+            raise ValueError('a sparse record has one colour application for both frames')
+
+    def _draw_one(self, H, W):
+        rng = self.rng if self.rng is not None else np.random
+        ch, cw = self.crop_size
+        # color_transform (augmentor.py:163-168): always symmetric
+        photo = draw_photo(self.photo_rng, self.photo_aug)
+        rects = self._draw_rects(rng, H, W)
+        # spatial_transform (augmentor.py:217-255)
+        min_scale = self._min_clip(H, W)
+        scale = 2 ** rng.uniform(self.min_scale, self.max_scale)
+        clipped = bool(scale < min_scale)
+        scale = np.clip(scale, min_scale, None)
+        resize = bool(rng.rand() < self.spatial_aug_prob)
+        H1, W1 = (cv_round(H * scale), cv_round(W * scale)) if resize else (H, W)
+        flip_h = bool(rng.rand() < 0.5) if self.do_flip else False
+        y0 = int(rng.randint(0, H1 - ch + SPARSE_MARGIN[0]))
+        x0 = int(rng.randint(-SPARSE_MARGIN[1], W1 - cw + SPARSE_MARGIN[1]))
+        return {'photo': (photo, photo), 'rects': rects, 'scale_x': float(scale), 'scale_y': float(scale), 'clipped': clipped,
+                'resize': resize, 'size': (H1, W1), 'flip_h': flip_h, 'flip_v': False,
+                'y0': int(np.clip(y0, 0, H1 - ch)), 'x0': int(np.clip(x0, 0, W1 - cw)), 'y0_drawn': y0, 'x0_drawn': x0,
+                'source': (int(H), int(W))}
+
+    def apply(self, params, img1, img2, flow, valid):
+        """Run the kernels with given records (one per sample) -> ``(image1, image2, flow, valid)`` on the device, with a leading
+        batch axis exactly when the inputs have one.  Current stream; no synchronisation, nothing returns to the host."""
+        return self._run(params, img1, img2, flow, valid)
+
+    def batch(self, img1, img2, flow, valid):
+        """``(image1, image2, flow, valid)``: what ``RAFT.train_step`` takes."""
+        shape = self._inputs(img1, img2, flow, valid)
+        H, W = shape[-3:-1]
+        return self.apply(self.draw(H, W, 1 if len(shape) == 3 else shape[0]), img1, img2, flow, valid)
+
+    def __call__(self, img1, img2, flow, valid):
+        return self.batch(img1, img2, flow, valid)
