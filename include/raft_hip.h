@@ -194,6 +194,27 @@ int raft_crop_or_pad_f32(const float *src, float *dst, int N, int Hs, int Ws, in
 int raft_crop_or_pad_u8_f32(const uint8_t *src, float *dst, int N, int Hs, int Ws, int Ht, int Wt, int C, void *stream);
 int raft_crop_or_pad_u8(const uint8_t *src, uint8_t *dst, int N, int Hs, int Ws, int Ht, int Wt, int C, void *stream);
 
+/* Separable resize of NHWC images by per-axis tap tables: src (N, Hs, Ws, C) uint8 or float -> dst (N, Ht, Wt, C) float, both
+ * contiguous:
+ *     dst[n, y, x, c] = chan_scale[c] * sum_b x_weights[x][b] * sum_a y_weights[y][a] * src[n, y_first[y] + a, x_first[x] + b, c]
+ * An axis of n_out outputs is described by three DEVICE arrays: first[n_out] (first source index), count[n_out] (taps,
+ * 1 <= count <= max_taps) and weights[n_out * max_taps] (row i holds output i's count[i] weights).  The tables of the project
+ * are bilinear with half-pixel centres, optionally widened to an antialiasing triangle on a shrinking axis, derived in float64
+ * on the host (tf_raft_amd/image_ops.py resize_taps); any table whose first indices do not decrease and
+ * advance by at most ceil(n_in / n_out) + 1 per output is taken.  Indices are clamped to the source whatever a table holds.
+ * chan_scale: C device floats (a flow resized from (Hs, Ws) to (Ht, Wt) has its u scaled by Wt / Ws and its v by Ht / Hs), or
+ * NULL for none.  One launch over all N images on `stream`, no intermediate, nothing synchronised or copied back.  Any sizes
+ * >= 1, any C >= 1 and any alignment are accepted; W * C of either side must fit an int; max_taps up to 64 per axis (shrink
+ * ratios up to 31), and (x_max_taps + 2) * C + 30 must not exceed 2048: RAFT_E_SHAPE otherwise. */
+int raft_resize_f32(const float *src, float *dst, int N, int Hs, int Ws, int Ht, int Wt, int C,
+                    const int *y_first, const int *y_count, const float *y_weights, int y_max_taps,
+                    const int *x_first, const int *x_count, const float *x_weights, int x_max_taps,
+                    const float *chan_scale, void *stream);
+int raft_resize_u8_f32(const uint8_t *src, float *dst, int N, int Hs, int Ws, int Ht, int Wt, int C,
+                       const int *y_first, const int *y_count, const float *y_weights, int y_max_taps,
+                       const int *x_first, const int *x_count, const float *x_weights, int x_max_taps,
+                       const float *chan_scale, void *stream);
+
 /* ------------------------------------------------------------------ training augmentation */
 
 /* FlowAugmentor (reference tf_raft/datasets/augmentor.py:9-129, used at dataset.py:87-91) composed into one gather (the sparse

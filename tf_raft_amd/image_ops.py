@@ -11,8 +11,15 @@ crops the flow back, all with this one call.  The rule, per axis, with ``d = tar
 so an odd surplus goes to the bottom / right, and everything outside the window is zero in the input's own scale.
 The copy is one launch of the window-copy kernel (``raft_crop_or_pad_*``, tf_raft_amd/csrc/image_ops.hip) on the current
 stream; there is no host fallback.
+
+``resize`` / ``resize_flow`` are the other way between the two sizes: bilinear interpolation with half-pixel centres
+(``tf.image.resize(method='bilinear', antialias=...)``), for frames much larger than the model's size.
+The taps of an axis are derived here, on the host, in float64 (``resize_taps``) and each weight is rounded once to float32; the
+kernel (``raft_resize_*``) only applies tables, so no source coordinate is ever computed in float32.
 """
 from __future__ import annotations
+
+import collections
 
 import numpy as np
 import torch
@@ -89,3 +96,174 @@ def resize_with_crop_or_pad(x, target_height: int, target_width: int, dtype=None
         return _dev.wrap(t)
     out = window_copy(t if t.dim() == 4 else t[None], target_height, target_width, dtype)
     return _dev.wrap(out if t.dim() == 4 else out[0])
+
+
+# ---------------------------------------------------------------------------------------------------------------- resize
+RESIZE_MAX_TAPS = 64          # csrc/image_ops.hip kResizeMaxTaps
+_RESIZE_LDS_FLOATS = 2048     # csrc/image_ops.hip kResizeCap
+
+
+def resize_taps(n_in: int, n_out: int, antialias: bool = False):
+    """One axis of the bilinear resize ``n_in -> n_out`` with half-pixel centres, in float64: ``(first, count, weights)`` with
+    ``first[i]`` the first source index of output ``i``, ``count[i]`` its number of taps and ``weights[i, :count[i]]`` their
+    weights (non-negative, summing to 1; the rest of the row is 0).  ``antialias`` widens the triangle by ``n_in / n_out`` on an
+    axis that shrinks and changes nothing on one that grows."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f'sizes must be >= 1, got {n_in} -> {n_out}')
+    scale = np.float64(n_in) / np.float64(n_out)
+    support = max(scale, 1.0) if antialias else np.float64(1.0)
+    inv = 1.0 / support
+    center = scale * (np.arange(n_out, dtype=np.float64) + 0.5)
+    first = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)
+    last = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), n_in)
+    count = last - first
+    j = first[:, None] + np.arange(int(count.max()), dtype=np.int64)[None, :]
+    w = np.maximum(0.0, 1.0 - np.abs((j - center[:, None] + 0.5) * inv))
+    w[j >= last[:, None]] = 0.0
+    w /= w.sum(axis=1, keepdims=True)
+    return first.astype(np.int32), count.astype(np.int32), w
+
+
+class _DeviceTable:
+    """Device arrays uploaded once, with what a use on another stream than the one they were made under needs."""
+    __slots__ = ('tensors', 'host', 'stream', 'event', 'max_taps')
+
+    def __init__(self, arrays, device, max_taps=0):
+        self.host = [torch.from_numpy(np.ascontiguousarray(a)).pin_memory() for a in arrays]     # alive as long as the copies may run
+        self.stream = torch.cuda.current_stream(device)
+        self.tensors = [h.to(device, non_blocking=True) for h in self.host]
+        self.event = torch.cuda.Event()
+        self.event.record(self.stream)
+        self.max_taps = max_taps
+
+    def use(self, device):
+        cur = torch.cuda.current_stream(device)
+        if cur != self.stream:
+            cur.wait_event(self.event)              # behind the upload
+            for t in self.tensors:
+                t.record_stream(cur)                # an evicted table is not handed out again under a launch that reads it
+        return self.tensors
+
+
+_TABLES = {}                  # device index -> OrderedDict(key -> _DeviceTable), least recently used first
+_TABLES_PER_DEVICE = 32
+
+
+def _table(device, key, make):
+    cache = _TABLES.setdefault(device.index, collections.OrderedDict())
+    ent = cache.get(key)
+    if ent is None:
+        with torch.cuda.device(device):
+            ent = cache[key] = make()
+        while len(cache) > _TABLES_PER_DEVICE:
+            cache.popitem(last=False)
+    else:
+        cache.move_to_end(key)
+    return ent
+
+
+def _axis_table(device, n_in, n_out, antialias):
+    def make():
+        first, count, w = resize_taps(n_in, n_out, antialias)
+        if w.shape[1] > RESIZE_MAX_TAPS:
+            raise ValueError(f'resize {n_in} -> {n_out} needs {w.shape[1]} taps per output, the kernel takes up to {RESIZE_MAX_TAPS}')
+        return _DeviceTable([np.stack([first, count]), w.astype(np.float32)], device, w.shape[1])
+    return _table(device, (int(n_in), int(n_out), bool(antialias)), make)
+
+
+class ResizePlan:
+    """The device tables of one ``(Hs, Ws) -> (Ht, Wt)`` resize: both axes' taps and, for a flow, the two channel factors
+    (``u * Wt / Ws``, ``v * Ht / Hs``: float64 ratios rounded once).  Made (and, the first time, uploaded) on the CURRENT stream."""
+
+    def __init__(self, device, Hs, Ws, Ht, Wt, antialias=False, flow=False):
+        self.device = device
+        self.source, self.target, self.antialias = (int(Hs), int(Ws)), (int(Ht), int(Wt)), bool(antialias)
+        self.ys = _axis_table(device, Hs, Ht, antialias)
+        self.xs = _axis_table(device, Ws, Wt, antialias)
+        self.factors = (np.float32(np.float64(Wt) / np.float64(Ws)), np.float32(np.float64(Ht) / np.float64(Hs))) if flow else None
+        self.scale = None
+        if flow:
+            self.scale = _table(device, ('factors',) + self.source + self.target,
+                                lambda: _DeviceTable([np.array(self.factors, np.float32)], device))
+
+    def tensors(self):
+        return self.ys.tensors + self.xs.tensors + (self.scale.tensors if self.scale is not None else [])
+
+    def check(self, channels, itemsize):
+        """What ``raft_resize_*`` cannot take is an error here, before any launch."""
+        if self.scale is not None and channels != 2:
+            raise ValueError(f'a flow has 2 channels, got {channels}')
+        group = 16 // itemsize
+        if (_RESIZE_LDS_FLOATS - 2 * (group - 1)) // channels - self.xs.max_taps - 1 < 0:
+            raise ValueError(f'{self.xs.max_taps} taps of {channels} channels do not fit the resize kernel')
+
+
+def resize_launch(t: torch.Tensor, plan: ResizePlan, out=None) -> torch.Tensor:
+    """The launch itself: contiguous device ``(N, Hs, Ws, C)`` of uint8 / bool / float32 -> float32 ``(N, Ht, Wt, C)`` on the
+    CURRENT stream (plain ``torch.Tensor``), written into ``out`` when given (contiguous, of the result's shape)."""
+    N, H, W, Cn = t.shape
+    if (H, W) != plan.source or t.device != plan.device:
+        raise ValueError(f'plan of {plan.source} on {plan.device} used on {(H, W)} on {t.device}')
+    lib = _dev.lib()
+    if t.dtype == torch.float32:
+        fn, src = lib.raft_resize_f32, t
+    elif t.dtype in (torch.uint8, torch.bool):
+        fn, src = lib.raft_resize_u8_f32, t.view(torch.uint8)
+    else:
+        raise TypeError(f'resize takes uint8, bool or float32, got {t.dtype}')
+    plan.check(Cn, src.element_size())
+    shape = (N,) + plan.target + (Cn,)
+    if out is None:
+        out = torch.empty(shape, device=t.device, dtype=torch.float32)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != t.device or not out.is_contiguous():
+        raise ValueError(f'out must be a contiguous float32 tensor of shape {shape} on {t.device}')
+    with torch.cuda.device(t.device):
+        (yi, yw), (xi, xw) = plan.ys.use(t.device), plan.xs.use(t.device)
+        cs = plan.scale.use(t.device)[0] if plan.scale is not None else None
+        Ht, Wt = plan.target
+        check(fn(_dev.ptr(src), _dev.ptr(out), N, H, W, Ht, Wt, Cn,
+                 _dev.ptr(yi), _dev.ptr(yi) + 4 * Ht, _dev.ptr(yw), plan.ys.max_taps,
+                 _dev.ptr(xi), _dev.ptr(xi) + 4 * Wt, _dev.ptr(xw), plan.xs.max_taps,
+                 _dev.ptr(cs) if cs is not None else None, _dev.stream_ptr()), 'resize')
+    return out
+
+
+def _resize(x, height, width, antialias, out, flow):
+    height, width = int(height), int(width)
+    if height < 1 or width < 1:
+        raise ValueError(f'target size must be >= 1, got {height} x {width}')
+    t = _on_device(x)
+    if t.dim() < 3 or (not flow and t.dim() > 4):
+        raise ValueError(f'expected {"(..., H, W, 2)" if flow else "(H, W, C) or (N, H, W, C)"}, got {tuple(t.shape)}')
+    if 0 in t.shape:
+        raise ValueError(f'empty input {tuple(t.shape)}')
+    if t.dtype not in ((torch.float32,) if flow else (torch.float32, torch.uint8, torch.bool)):
+        raise TypeError(f'{"resize_flow takes float32" if flow else "resize takes uint8, bool or float32"}, got {t.dtype}')
+    if flow and t.shape[-1] != 2:
+        raise ValueError(f'a flow has 2 channels, got {tuple(t.shape)}')
+    shape = tuple(t.shape[:-3]) + (height, width, t.shape[-1])
+    if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != t.device or not out.is_contiguous()):
+        raise ValueError(f'out must be a contiguous float32 tensor of shape {shape} on {t.device}')
+    if tuple(t.shape[-3:-1]) == (height, width):
+        t = t if t.dtype == torch.float32 else t.to(torch.float32)
+        return _dev.wrap(t if out is None else out.copy_(t))
+    with torch.cuda.device(t.device):
+        plan = ResizePlan(t.device, t.shape[-3], t.shape[-2], height, width, antialias, flow)
+    res = resize_launch(t.reshape((-1,) + tuple(t.shape[-3:])), plan, None if out is None else out.view((-1,) + shape[-3:]))
+    return _dev.wrap(res.view(shape))
+
+
+def resize(x, height: int, width: int, antialias: bool = False, out=None) -> torch.Tensor:
+    """Bilinear resize with half-pixel centres (``tf.image.resize(x, (height, width), 'bilinear', antialias=antialias)``) of
+    ``(H, W, C)`` or ``(N, H, W, C)``: NumPy or torch, host or device, uint8 / bool / float32 (float64 narrows).  Returns a
+    contiguous float32 device tensor (``out`` when given), computed by one launch on the current stream.  A source that already
+    has the target size is returned unchanged, cast to float32 if needed (no launch).  A shrink ratio beyond what the kernel
+    takes (``RESIZE_MAX_TAPS`` taps per output) raises ``ValueError``."""
+    return _resize(x, height, width, antialias, out, False)
+
+
+def resize_flow(flow, height: int, width: int, antialias: bool = False, out=None) -> torch.Tensor:
+    """``resize`` of a float32 flow field ``(..., H, W, 2)`` over any leading axes in one launch, with ``u`` multiplied by
+    ``width / W`` and ``v`` by ``height / H`` in the same pass."""
+    return _resize(flow, height, width, antialias, out, True)

@@ -83,7 +83,7 @@ class RAFT:
 
     def __init__(self, drop_rate=0, iters=12, iters_pred=24, weights: Optional[Dict[str, np.ndarray]] = None,
                  seed=0, alternate_corr=False, overlap=None, pipeline=None, lanes=None, loop_concurrency=None, target_size=None,
-                 **kwargs):
+                 fit='crop_or_pad', antialias=True, **kwargs):
         # reference model.py:11-12 forwards **kwargs to tf.keras.Model, whose constructor takes `name` (and nothing a
         # forward pass depends on): accept it, reject the rest
         self.name = kwargs.pop('name', type(self).__name__.lower())
@@ -103,6 +103,10 @@ class RAFT:
         # least MIN_SIDE per axis; (Ht, Wt) = the reference's fixed target, larger frames are centre-cropped.  The returned flow
         # is cropped / zero-padded back to the frames' own size.  Training-mode calls and train_step are not affected.
         self.target_size = self._check_target_size(target_size)
+        # How the frames reach the model's size: 'crop_or_pad' = the reference's rule above; 'resize' = bilinear interpolation with
+        # half-pixel centres (tf.image.resize; `antialias` widens the triangle where an axis shrinks), the returned flow resized
+        # back with u scaled by W / Wt and v by H / Ht -- for frames much larger than the model's size.
+        self.fit, self.antialias = self._check_fit(fit, antialias, self.target_size)
         # three-stream schedule of the loop (RAFT only); RAFT_OVERLAP=0 forces the single-stream loop.  With several lanes
         # (below) the loops of a pipelined call default to the single-stream schedule: the other lanes fill the chain's idle CUs
         # and gaps better than a loop's own side branches do (profiles/r12b_lanes_ab_per_process.txt).
@@ -151,6 +155,16 @@ class RAFT:
             raise ValueError(f'target_size must be multiples of 8 and at least {cls.MIN_SIDE} per axis, got {th} x {tw}')
         return (th, tw)
 
+    @staticmethod
+    def _check_fit(fit, antialias, target_size):
+        if fit not in ('crop_or_pad', 'resize'):
+            raise ValueError(f"fit must be 'crop_or_pad' or 'resize', got {fit!r}")
+        if fit == 'resize' and target_size is None:
+            raise ValueError("fit='resize' needs a target_size ('auto' or (height, width))")
+        if not isinstance(antialias, (bool, np.bool_)):
+            raise ValueError(f'antialias must be True or False, got {antialias!r}')
+        return fit, bool(antialias)
+
     def _model_size(self, H, W):
         """The size the model runs at for frames of H x W under ``target_size``."""
         if self.target_size == 'auto':
@@ -159,7 +173,8 @@ class RAFT:
 
     def _fit_frames(self, image1, image2):
         """``target_size`` set: both frames as float32 device tensors of the model's size, and the frames' own (H, W) when that
-        differs (None: nothing was launched).  uint8 frames are cast and windowed in one pass."""
+        differs (None: nothing was launched).  uint8 frames are cast and windowed (or resized) in one pass.  ``fit='resize'``: the
+        third entry of the returned window is the plan of the flow's way back, its tables already on the device."""
         image1, image2 = image_ops._on_device(image1), image_ops._on_device(image2)
         if image1.dim() != 4 or image1.shape[-1] != 3 or image1.shape != image2.shape or image1.dtype != image2.dtype or 0 in image1.shape:
             raise ValueError(f'images must both be (bs, H, W, 3) of one type, got {tuple(image1.shape)} {image1.dtype} / '
@@ -170,6 +185,13 @@ class RAFT:
             return _dev.to_device(image1), _dev.to_device(image2), None
         if image1.dtype not in (torch.uint8, torch.float32):
             image1, image2 = image1.to(torch.float32), image2.to(torch.float32)
+        if self.fit == 'resize':
+            # both directions' tables are made (the first time: uploaded) here, on the caller's stream: the launch that resizes
+            # the predictions, on the loop's stream of a pipelined call, finds everything in place
+            with torch.cuda.device(image1.device):
+                fwd = image_ops.ResizePlan(image1.device, H, W, th, tw, self.antialias)
+                back = image_ops.ResizePlan(image1.device, th, tw, H, W, self.antialias, flow=True)
+            return image_ops.resize_launch(image1, fwd), image_ops.resize_launch(image2, fwd), (H, W, back)
         return (image_ops.window_copy(image1, th, tw, torch.float32), image_ops.window_copy(image2, th, tw, torch.float32), (H, W))
 
     @staticmethod
@@ -177,6 +199,10 @@ class RAFT:
         """Predictions (..., Ht, Wt, 2) of the model's size -> the frames' own size, ONE launch over all leading axes, on the
         current stream."""
         lead = tuple(out.shape[:-3])
+        if len(window) > 2:
+            res = image_ops.resize_launch(out.view((-1,) + tuple(out.shape[-3:])), window[2],
+                                          out=None if into is None else into.view((-1,) + tuple(into.shape[-3:])))
+            return res.view(lead + tuple(res.shape[-3:]))
         res = image_ops.window_copy(out.view((-1,) + tuple(out.shape[-3:])), window[0], window[1],
                                     out=None if into is None else into.view((-1,) + tuple(into.shape[-3:])))
         return res.view(lead + tuple(res.shape[-3:]))
@@ -516,7 +542,8 @@ class RAFT:
                 self._fit_flow(out, window, into=res)
             done = torch.cuda.Event()
             done.record(loop)
-        for t in (out, res, getattr(correlation, '_pyr', None), getattr(correlation, '_f2pyr', None), correlation.fmap1, correlation.fmap2):
+        tables = window[2].tensors() if window is not None and len(window) > 2 else []
+        for t in (out, res, getattr(correlation, '_pyr', None), getattr(correlation, '_f2pyr', None), correlation.fmap1, correlation.fmap2, *tables):
             if isinstance(t, torch.Tensor) and t.is_cuda:
                 t.as_subclass(torch.Tensor).record_stream(loop)      # allocated under `cur`, in use on `loop`
         ent[1] = done
