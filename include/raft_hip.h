@@ -215,6 +215,26 @@ int raft_resize_u8_f32(const uint8_t *src, float *dst, int N, int Hs, int Ws, in
                        const int *x_first, const int *x_count, const float *x_weights, int x_max_taps,
                        const float *chan_scale, void *stream);
 
+/* Flow colour coding (reference tf_raft/datasets/flow_viz.py:109-132 flow_to_image, the Middlebury colour wheel): a flow
+ * (N, Hs, Ws, 2) seen through the crop-or-pad window above at a destination size (Ht, Wt) -> pictures (N, Ht, Wt, 3) uint8,
+ * in two launches on `stream` with no atomics, no memset and nothing synchronised.  Destination pixels outside the window are
+ * zero flow (white); source pixels outside it count for nothing.  clip >= 0: np.clip(flow, 0, clip) first, as the reference
+ * does it (negative components become 0); any negative clip: none.
+ *   raft_flow_rad_max_f32: partial maxima of sqrt(u*u + v*v) in float32, each product and the sum rounded on its own, into
+ *     partial[raft_flow_to_image_workspace_floats(N)] (every element is written; image n's maximum is the largest of its
+ *     raft_flow_to_image_workspace_floats(1) consecutive elements -- exact in any order, so bit-identical to NumPy's).
+ *   raft_flow_to_image_u8: the picture.  Each image is normalised by its own maximum from `partial`; fixed_rad_max > 0
+ *     replaces it for every image (partial may then be NULL), and vectors beyond it take the reference's darkened
+ *     out-of-range branch.  bgr != 0 stores the channels in reverse.  float32 up to the wheel position, float64 from there on,
+ *     as NumPy 2 types the reference's expressions; atan2 is computed in double and rounded once.  A NaN
+ *     or infinite flow is outside the contract; it never reads outside the 55-entry wheel.
+ * flow must be 8-byte aligned (RAFT_E_ALIGN); image may have any alignment.  Ws * 2, Wt * 3 and Ht * Wt must fit an int
+ * (RAFT_E_SHAPE, like non-positive sizes); RAFT_E_NULL for a null pointer.  All checks precede any launch. */
+int64_t raft_flow_to_image_workspace_floats(int N);
+int raft_flow_rad_max_f32(const float *flow, float *partial, int N, int Hs, int Ws, int Ht, int Wt, float clip, void *stream);
+int raft_flow_to_image_u8(const float *flow, const float *partial, uint8_t *image, int N, int Hs, int Ws, int Ht, int Wt,
+                          float clip, int bgr, float fixed_rad_max, void *stream);
+
 /* ------------------------------------------------------------------ training augmentation */
 
 /* FlowAugmentor (reference tf_raft/datasets/augmentor.py:9-129, used at dataset.py:87-91) composed into one gather (the sparse

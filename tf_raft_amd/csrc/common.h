@@ -33,6 +33,15 @@ static inline bool raft_aligned16(const void *p) { return (((uintptr_t)p) & 15u)
 
 static inline int raft_ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// One axis of tf.image.resize_with_crop_or_pad, with d = target - source (floor division): the source window starts at
+// max(-d // 2, 0), lands at max(d // 2, 0) in the target and is min(source, target) long (image_ops.hip, flow_viz.hip).
+static inline void raft_axis_window(int source, int target, int *crop, int *pad, int *ext) {
+    const int d = target - source;
+    *crop = d < 0 ? (-d) / 2 : 0;     // max(-d // 2, 0)
+    *pad = d > 0 ? d / 2 : 0;         // max( d // 2, 0)
+    *ext = source < target ? source : target;
+}
+
 // Layout of one per-query correlation map (and of the rows of the pooled fmap2 pyramid): 4 x 8 tiles of 32
 // floats = one 128-byte line each, tiles row-major, maps padded to whole tiles.  The (2r+2)^2 lookup footprint
 // then touches ~6.9 lines of a large map instead of ~12.8 with row-major rows (the lookup is

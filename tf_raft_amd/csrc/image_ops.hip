@@ -91,13 +91,6 @@ __global__ void __launch_bounds__(64 * kRowsPerBlock) window_copy_kernel(const S
     }
 }
 
-inline void axis_window(int source, int target, int *crop, int *pad, int *ext) {
-    const int d = target - source;
-    *crop = d < 0 ? (-d) / 2 : 0;     // max(-d // 2, 0)
-    *pad = d > 0 ? d / 2 : 0;         // max( d // 2, 0)
-    *ext = source < target ? source : target;
-}
-
 template <typename S, typename D>
 int window_copy(const S *src, D *dst, int N, int Hs, int Ws, int Ht, int Wt, int C, void *stream) {
     RAFT_REQUIRE_PTR(src);
@@ -106,8 +99,8 @@ int window_copy(const S *src, D *dst, int N, int Hs, int Ws, int Ht, int Wt, int
     RAFT_REQUIRE((int64_t)Ws * C <= 0x7fffffff && (int64_t)Wt * C <= 0x7fffffff, RAFT_E_SHAPE);
     WindowGeom g;
     int crop_x, pad_x, ext_x;
-    axis_window(Hs, Ht, &g.crop_y, &g.pad_y, &g.ext_y);
-    axis_window(Ws, Wt, &crop_x, &pad_x, &ext_x);
+    raft_axis_window(Hs, Ht, &g.crop_y, &g.pad_y, &g.ext_y);
+    raft_axis_window(Ws, Wt, &crop_x, &pad_x, &ext_x);
     g.rows = (int64_t)N * Ht;
     g.Hs = Hs;
     g.Ht = Ht;

@@ -16,6 +16,10 @@ stream; there is no host fallback.
 (``tf.image.resize(method='bilinear', antialias=...)``), for frames much larger than the model's size.
 The taps of an axis are derived here, on the host, in float64 (``resize_taps``) and each weight is rounded once to float32; the
 kernel (``raft_resize_*``) only applies tables, so no source coordinate is ever computed in float32.
+
+``flow_to_image`` is the reference's flow colour coding (tf_raft/datasets/flow_viz.py) as two launches
+(``raft_flow_rad_max_f32`` / ``raft_flow_to_image_u8``, tf_raft_amd/csrc/flow_viz.hip), optionally seen
+through the same crop-or-pad window, so a prediction leaves the device as a 3-byte picture instead of an 8-byte flow.
 """
 from __future__ import annotations
 
@@ -267,3 +271,95 @@ def resize_flow(flow, height: int, width: int, antialias: bool = False, out=None
     """``resize`` of a float32 flow field ``(..., H, W, 2)`` over any leading axes in one launch, with ``u`` multiplied by
     ``width / W`` and ``v`` by ``height / H`` in the same pass."""
     return _resize(flow, height, width, antialias, out, True)
+
+
+# ---------------------------------------------------------------------------------------------------------- colour coding
+def _viz_args(clip_flow, rad_max):
+    clip = -1.0 if clip_flow is None else float(clip_flow)
+    if clip_flow is not None and not clip >= 0.0:
+        raise ValueError(f'clip_flow must be >= 0, got {clip_flow!r}')
+    fixed = 0.0 if rad_max is None else float(rad_max)
+    if rad_max is not None and not (fixed > 0.0 and np.isfinite(np.float32(fixed))):
+        raise ValueError(f'rad_max must be a positive float, got {rad_max!r}')
+    return clip, fixed
+
+
+def _flow_4d(flow, size):
+    t = _on_device(flow)
+    if t.dim() not in (3, 4) or t.shape[-1] != 2:
+        raise ValueError(f'expected a flow (H, W, 2) or (N, H, W, 2), got {tuple(t.shape)}')
+    if 0 in t.shape:
+        raise ValueError(f'empty input {tuple(t.shape)}')
+    if t.dtype != torch.float32:
+        raise TypeError(f'a flow is float32, got {t.dtype}')
+    h, w = (int(v) for v in (t.shape[-3:-1] if size is None else size))
+    if h < 1 or w < 1:
+        raise ValueError(f'size must be >= 1 per axis, got {h} x {w}')
+    return t, (t if t.dim() == 4 else t[None]), h, w
+
+
+def flow_rad_max_launch(t: torch.Tensor, height: int, width: int, clip: float = -1.0) -> torch.Tensor:
+    """The first launch of the colour coding (``raft_flow_rad_max_f32``) on the CURRENT stream: contiguous float32 device
+    ``(N, H, W, 2)`` -> the partial maxima of every image's flow magnitude inside the crop-or-pad window to ``(height, width)``,
+    ``(N, raft_flow_to_image_workspace_floats(1))`` float32, every element written."""
+    N, H, W, _ = t.shape
+    lib = _dev.lib()
+    partial = torch.empty((N, int(lib.raft_flow_to_image_workspace_floats(1))), device=t.device, dtype=torch.float32)
+    with torch.cuda.device(t.device):
+        check(lib.raft_flow_rad_max_f32(_dev.ptr(t), _dev.ptr(partial), N, H, W, int(height), int(width), clip, _dev.stream_ptr()),
+              'flow_rad_max')
+    return partial
+
+
+def flow_to_image_launch(t: torch.Tensor, height: int, width: int, clip: float = -1.0, bgr: bool = False, fixed_rad_max: float = 0.0,
+                         out=None) -> torch.Tensor:
+    """The launches themselves: contiguous float32 device ``(N, H, W, 2)`` -> uint8 ``(N, height, width, 3)`` on the CURRENT
+    stream (plain ``torch.Tensor``), written into ``out`` when given.  Two launches; one when ``fixed_rad_max > 0`` (nothing
+    needs the images' own maxima then)."""
+    N, H, W, _ = t.shape
+    shape = (N, int(height), int(width), 3)
+    if out is None:
+        out = torch.empty(shape, device=t.device, dtype=torch.uint8)
+    elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != t.device or not out.is_contiguous():
+        raise ValueError(f'out must be a contiguous uint8 tensor of shape {shape} on {t.device}')
+    partial = flow_rad_max_launch(t, height, width, clip) if not fixed_rad_max > 0.0 else None
+    with torch.cuda.device(t.device):
+        check(_dev.lib().raft_flow_to_image_u8(_dev.ptr(t), _dev.ptr(partial) if partial is not None else None, _dev.ptr(out), N, H, W,
+                                               shape[1], shape[2], clip, int(bool(bgr)), fixed_rad_max, _dev.stream_ptr()), 'flow_to_image')
+    return out
+
+
+def flow_to_image(flow, size=None, clip_flow=None, convert_to_bgr=False, rad_max=None, out=None) -> torch.Tensor:
+    """The reference's ``flow_to_image`` (tf_raft/datasets/flow_viz.py:109-132, the Middlebury colour wheel) on the device:
+    a flow ``(H, W, 2)`` or ``(N, H, W, 2)`` (NumPy or torch, host or device, float32; float64 narrows) -> a uint8 device
+    tensor ``(..., H, W, 3)`` of the same rank (``out`` when given), computed by two launches on the current stream.
+
+    Each image is normalised by its own largest magnitude, as the reference does per call.  ``rad_max`` (a positive float) fixes
+    the radius instead -- one scale for all frames of a video -- and vectors beyond it take the reference's out-of-range
+    branch, which darkens them: the picture is ``flow_uv_to_colors(u / (R + eps), v / (R + eps))`` with ``R + eps`` in float32.
+    ``clip_flow`` is the reference's ``np.clip(flow, 0, clip_flow)`` (negative components become 0) and ``convert_to_bgr`` its
+    channel order.  ``size=(h, w)``: the picture of ``resize_with_crop_or_pad(flow, h, w)`` without that copy; flow cropped
+    away does not set the scale, padding is zero flow (white).
+
+    Values agree with the reference's NumPy to within one level in at most a few values per million (``atan2`` is computed in
+    double and rounded once; NumPy's float32 ``arctan2`` is not correctly rounded -- DESIGN.md section 13).  A NaN or infinite flow
+    is outside the contract.  ``tf_raft_amd.io.flow_to_image`` is the host version."""
+    clip, fixed = _viz_args(clip_flow, rad_max)
+    t, t4, h, w = _flow_4d(flow, size)
+    if out is not None:
+        shape = tuple(t.shape[:-3]) + (h, w, 3)
+        if tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != t.device or not out.is_contiguous():
+            raise ValueError(f'out must be a contiguous uint8 tensor of shape {shape} on {t.device}')
+        out = out.as_subclass(torch.Tensor)
+    res = flow_to_image_launch(t4, h, w, clip, convert_to_bgr, fixed, None if out is None else (out if t.dim() == 4 else out[None]))
+    return _dev.wrap(res if t.dim() == 4 else res[0])
+
+
+def flow_rad_max(flow, size=None, clip_flow=None) -> torch.Tensor:
+    """The radius ``flow_to_image`` normalises each image by: float32 ``(N,)`` (a scalar tensor for ``(H, W, 2)``), bit for bit
+    the reference's ``np.max(np.sqrt(np.square(u) + np.square(v)))`` over the window to ``size``.  The first launch alone; its
+    partial maxima are folded by a torch reduction here (``flow_to_image`` never calls this: its second kernel folds them itself)."""
+    clip, _ = _viz_args(clip_flow, None)
+    t, t4, h, w = _flow_4d(flow, size)
+    m = flow_rad_max_launch(t4, h, w, clip).amax(dim=1)
+    return _dev.wrap(m if t.dim() == 4 else m[0])

@@ -561,15 +561,23 @@ class RAFT:
             return self._forward([image1, image2], training=False, final_only=True, pipelined=_pipelined)
         return self._forward([image1, image2], training=False, pipelined=_pipelined)[-1]
 
-    def predict(self, x, batch_size=None, steps=None, **kwargs):
+    def predict(self, x, batch_size=None, steps=None, output='flow', clip_flow=None, convert_to_bgr=False, rad_max=None, **kwargs):
         """``keras.Model.predict`` over ``predict_step`` (reference model.py:160-166): the final flow of every image
         pair as one host array ``(N, H, W, 2)``.
 
         ``x`` is ``[image1, image2]`` (host or device arrays ``(N, H, W, 3)``, split into batches of ``batch_size``,
         Keras' default 32) or an iterable of ``(image1, image2, ...)`` batches (the reference's ``tf.data`` datasets).
         Host batches are uploaded one batch ahead of the compute stream and the predictions come back through pinned
-        buffers one batch behind it (``tf_raft_amd.prefetch``), so neither transfer sits on the critical path."""
+        buffers one batch behind it (``tf_raft_amd.prefetch``), so neither transfer sits on the critical path.
+
+        ``output='image'`` returns the colour-coded flow instead, uint8 ``(N, H, W, 3)``: what the reference's
+        ``flow_to_image`` makes of each prediction (``tf_raft_amd.image_ops.flow_to_image``, which takes ``clip_flow``,
+        ``convert_to_bgr`` and ``rad_max``), coloured on the download stream in front of the copy, so 3 instead of 8 bytes per
+        pixel cross to the host."""
         from .prefetch import prefetch_to_device
+        if output not in ('flow', 'image'):
+            raise ValueError(f"output must be 'flow' or 'image', got {output!r}")
+        viz = image_ops._viz_args(clip_flow, rad_max) if output == 'image' else None
         dev = _dev.require_gpu()
         arrays = isinstance(x, (list, tuple)) and len(x) == 2 and all(getattr(a, 'ndim', 0) == 4 for a in x)
         if arrays:
@@ -607,13 +615,16 @@ class RAFT:
         for i, (image1, image2) in enumerate(prefetch_to_device(batches, buffer_size=1, device=dev)):
             res = self.predict_step((image1, image2), _pipelined=True)   # consumed below on `down`: the compute stream never waits for a loop
             cur = torch.cuda.current_stream(dev)
-            key = (i & 1, tuple(res.shape))
+            shape, dtype = (tuple(res.shape), res.dtype) if viz is None else (tuple(res.shape[:-1]) + (3,), torch.uint8)
+            key = (i & 1, shape)
             if key not in pins:
-                pins[key] = torch.empty(res.shape, dtype=res.dtype).pin_memory()
+                pins[key] = torch.empty(shape, dtype=dtype).pin_memory()
             down.wait_stream(cur)
             with torch.cuda.stream(down):
                 out = res.as_subclass(torch.Tensor)      # pipelined forward: `down`, not the compute stream, waits for the loop
-                pins[key].copy_(out, non_blocking=True)
+                # the picture (and its workspace) are allocated, written and read under `down` alone
+                src = out if viz is None else image_ops.flow_to_image_launch(out, shape[1], shape[2], viz[0], convert_to_bgr, viz[1])
+                pins[key].copy_(src, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(down)
             out.record_stream(down)

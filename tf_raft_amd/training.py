@@ -115,14 +115,18 @@ class VisFlowCallback:
     (or of randomly chosen) samples of ``dataset`` and write ``[image1, image2, colour-coded flow]`` stacked vertically to
     ``logdir/epoch{NNN}_{iii}.png``.  Each frame is padded (or cropped) to ``target_size`` for the model and the final flow is
     cropped (or padded) back to the frame's own size, both on the device (``tf_raft_amd.image_ops``).  ``dataset[i]`` yields
-    ``(image1, image2, ...)`` of shape ``(H, W, 3)``, values 0..255."""
+    ``(image1, image2, ...)`` of shape ``(H, W, 3)``, values 0..255.  ``colour_on_device=True`` colours the flow on the device
+    as well (``image_ops.flow_to_image`` with the crop back fused into it: two launches, and only the uint8 picture comes to the
+    host); the default is the host's ``io.flow_to_image``, the reference's NumPy bit for bit."""
 
-    def __init__(self, dataset, target_size=(448, 1024), num_visualize=1, choose_random=False, logdir='predicted_flows'):
+    def __init__(self, dataset, target_size=(448, 1024), num_visualize=1, choose_random=False, logdir='predicted_flows',
+                 colour_on_device=False):
         self.dataset = dataset
         self.target_size = tuple(int(v) for v in target_size)
         self.num_visualize = num_visualize
         self.choose_random = choose_random
         self.logdir = logdir
+        self.colour_on_device = bool(colour_on_device)
         self.model = None
         os.makedirs(logdir, exist_ok=True)
 
@@ -131,7 +135,7 @@ class VisFlowCallback:
 
     def on_epoch_end(self, epoch, logs=None):
         from . import io
-        from .image_ops import resize_with_crop_or_pad
+        from .image_ops import flow_to_image, resize_with_crop_or_pad
         if self.model is None:
             raise RuntimeError('VisFlowCallback has no model: call set_model(model) first')
         if self.choose_random:
@@ -145,8 +149,11 @@ class VisFlowCallback:
             h_origin, w_origin, _ = image1.shape
             padded = [resize_with_crop_or_pad(im, *self.target_size, dtype=torch.float32)[None] for im in (image1, image2)]
             flow_pred = self.model(padded, training=False)[-1][0]
-            flow_pred = resize_with_crop_or_pad(flow_pred, h_origin, w_origin)
-            flow_img = io.flow_to_image(flow_pred.numpy()).astype(np.uint8)
+            if self.colour_on_device:
+                flow_img = flow_to_image(flow_pred, size=(h_origin, w_origin)).numpy()
+            else:
+                flow_pred = resize_with_crop_or_pad(flow_pred, h_origin, w_origin)
+                flow_img = io.flow_to_image(flow_pred.numpy()).astype(np.uint8)
             frames = [np.clip(io._to_numpy(im), 0, 255).astype(np.uint8) for im in (image1, image2)]
             contents = np.concatenate(frames + [flow_img], axis=0)
             io.write_png(os.path.join(self.logdir, f'epoch{str(epoch + 1).zfill(3)}_{str(int(i) + 1).zfill(3)}.png'), contents)
