@@ -215,6 +215,44 @@ int raft_resize_u8_f32(const uint8_t *src, float *dst, int N, int Hs, int Ws, in
                        const int *x_first, const int *x_count, const float *x_weights, int x_max_taps,
                        const float *chan_scale, void *stream);
 
+/* Tiled inference (no reference counterpart): a frame larger than the model's size is covered by a product
+ * grid of ny x nx overlapping model-sized tiles, each tile is predicted on its own, and the predictions are cross-faded where
+ * tiles overlap.  The origins of the tiles in the frame (tf_raft_amd/image_ops.py tile_origins; negative where a frame shorter
+ * than the tile is centred in it by the crop-or-pad rule) travel by value: */
+#define RAFT_TILE_MAX_PER_AXIS 32
+#define RAFT_TILE_MAX_TAPS 4
+typedef struct RaftTileOrigins {
+    int32_t ny, nx;                          /* tiles per axis, 1 .. RAFT_TILE_MAX_PER_AXIS */
+    int32_t oy[RAFT_TILE_MAX_PER_AXIS];      /* frame row of tile row 0, the first ny are read */
+    int32_t ox[RAFT_TILE_MAX_PER_AXIS];      /* frame column of tile column 0, the first nx are read */
+} RaftTileOrigins;
+
+/* The gather in front of the model: src (N, Hs, Ws, C) uint8 or float -> dst (N * ny * nx, Ht, Wt, C) float, both contiguous,
+ * tile (n * ny + ky) * nx + kx holding dst[y, x] = src[n, oy[ky] + y, ox[kx] + x] and zero outside the frame (uint8 is cast in
+ * the same pass).  Every element of dst is written exactly once, in one launch on `stream`.  Any sizes >= 1, any C >= 1 and any
+ * alignment are accepted, as by raft_crop_or_pad_*; W * C of either side must fit an int.  RAFT_E_SHAPE for a non-positive
+ * size, for ny or nx outside 1 .. RAFT_TILE_MAX_PER_AXIS and for a tile that lies wholly outside the frame; RAFT_E_NULL for a
+ * null pointer.  All checks precede the launch. */
+int raft_tile_gather_f32(const float *src, float *dst, int N, int Hs, int Ws, int Ht, int Wt, int C, RaftTileOrigins origins,
+                         void *stream);
+int raft_tile_gather_u8_f32(const uint8_t *src, float *dst, int N, int Hs, int Ws, int Ht, int Wt, int C, RaftTileOrigins origins,
+                            void *stream);
+
+/* The blend behind the model: tiles (M, N * ny * nx, Ht, Wt, 2) -> dst (M, N, H, W, 2), both contiguous floats, M the
+ * flattened leading axes (the iterations of a call):
+ *     dst[m, n, y, x] = sum_b x_weights[x][b] * sum_a y_weights[y][a] * tiles[m, (n * ny + ky) * nx + kx, y - oy[ky], x - ox[kx]]
+ * with ky = y_first[y] + a and kx = x_first[x] + b, the sums in this order.  An axis of L frame coordinates is described by
+ * three DEVICE arrays, as an axis of raft_resize_*: first[L] (first tile index), count[L] (tiles covering the coordinate,
+ * 1 <= count <= max_taps <= RAFT_TILE_MAX_TAPS) and weights[L * max_taps] (the normalised tent weights of those tiles, derived
+ * in float64 on the host and rounded once: tf_raft_amd/image_ops.py tile_taps).  Flow vectors are not scaled.  One launch on
+ * `stream`; no atomics, no memset, no intermediate, nothing synchronised; every element of dst is written exactly once, and
+ * element offsets are 64-bit.  Tile indices and tile coordinates are clamped into the tiles whatever the tables hold.  tiles
+ * and dst must be 8-byte aligned (RAFT_E_ALIGN: they are read and written as float2).  RAFT_E_SHAPE for a non-positive size,
+ * ny / nx / max_taps out of range, or Ht * Wt beyond an int; RAFT_E_NULL for a null pointer.  All checks precede the launch. */
+int raft_tile_blend_f32(const float *tiles, float *dst, int64_t M, int N, int H, int W, int Ht, int Wt, RaftTileOrigins origins,
+                        const int *y_first, const int *y_count, const float *y_weights, int y_max_taps,
+                        const int *x_first, const int *x_count, const float *x_weights, int x_max_taps, void *stream);
+
 /* Flow colour coding (reference tf_raft/datasets/flow_viz.py:109-132 flow_to_image, the Middlebury colour wheel): a flow
  * (N, Hs, Ws, 2) seen through the crop-or-pad window above at a destination size (Ht, Wt) -> pictures (N, Ht, Wt, 3) uint8,
  * in two launches on `stream` with no atomics, no memset and nothing synchronised.  Destination pixels outside the window are

@@ -53,6 +53,15 @@ class State(C.Structure):
         'net', 'x', 'corr', 'coords1', 'flow', 'delta', 'mask', 'ws', 'ctx')]
 
 
+TILE_MAX_PER_AXIS = 32      # include/raft_hip.h RAFT_TILE_MAX_PER_AXIS
+TILE_MAX_TAPS = 4           # include/raft_hip.h RAFT_TILE_MAX_TAPS
+
+
+class TileOrigins(C.Structure):
+    """``RaftTileOrigins``: the tile grid of one frame size, passed by value."""
+    _fields_ = [('ny', C.c_int32), ('nx', C.c_int32), ('oy', C.c_int32 * TILE_MAX_PER_AXIS), ('ox', C.c_int32 * TILE_MAX_PER_AXIS)]
+
+
 class AugmentParams(C.Structure):
     """``RaftAugmentParams``: one sample's record of tf_raft_amd/augment.py (include/raft_hip.h has the field notes)."""
     _fields_ = [('inv_fx', C.c_double), ('inv_fy', C.c_double), ('fx', C.c_double), ('fy', C.c_double),
@@ -93,6 +102,9 @@ _SIGNATURES = {
     'raft_crop_or_pad_u8': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'raft_resize_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
     'raft_resize_u8_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
+    'raft_tile_gather_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, TileOrigins, _P]),
+    'raft_tile_gather_u8_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, TileOrigins, _P]),
+    'raft_tile_blend_f32': (_I, [_P, _P, C.c_int64, _I, _I, _I, _I, _I, TileOrigins, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
     'raft_flow_to_image_workspace_floats': (C.c_int64, [_I]),
     'raft_flow_rad_max_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, C.c_float, _P]),
     'raft_flow_to_image_u8': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.c_float, _I, C.c_float, _P]),

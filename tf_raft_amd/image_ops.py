@@ -17,6 +17,13 @@ stream; there is no host fallback.
 The taps of an axis are derived here, on the host, in float64 (``resize_taps``) and each weight is rounded once to float32; the
 kernel (``raft_resize_*``) only applies tables, so no source coordinate is ever computed in float32.
 
+``tile_gather`` / ``tile_blend`` are the third way, for large frames at their OWN resolution: the frame is covered
+by a product grid of overlapping tiles of the model's size (``tile_origins``: one tile placed by the crop-or-pad rule where the frame
+is no longer than the tile, else the fewest tiles sharing at least ``overlap`` pixels, spread evenly), every tile is predicted on its
+own, and the predictions are cross-faded with tent weights normalised per pixel (``tile_taps``, float64 on the host, each weight
+rounded once; separable on a product grid).  One launch each (``raft_tile_gather_*`` / ``raft_tile_blend_f32``); flow vectors are not
+scaled.
+
 ``flow_to_image`` is the reference's flow colour coding (tf_raft/datasets/flow_viz.py) as two launches
 (``raft_flow_rad_max_f32`` / ``raft_flow_to_image_u8``, tf_raft_amd/csrc/flow_viz.hip), optionally seen
 through the same crop-or-pad window, so a prediction leaves the device as a 3-byte picture instead of an 8-byte flow.
@@ -29,6 +36,7 @@ import numpy as np
 import torch
 
 from . import _dev
+from . import _ffi
 from ._ffi import check
 
 
@@ -271,6 +279,225 @@ def resize_flow(flow, height: int, width: int, antialias: bool = False, out=None
     """``resize`` of a float32 flow field ``(..., H, W, 2)`` over any leading axes in one launch, with ``u`` multiplied by
     ``width / W`` and ``v`` by ``height / H`` in the same pass."""
     return _resize(flow, height, width, antialias, out, True)
+
+
+# ----------------------------------------------------------------------------------------------------------------- tiles
+TILE_MAX_PER_AXIS = _ffi.TILE_MAX_PER_AXIS      # include/raft_hip.h RAFT_TILE_MAX_PER_AXIS
+TILE_MAX_TAPS = _ffi.TILE_MAX_TAPS              # include/raft_hip.h RAFT_TILE_MAX_TAPS
+
+
+def _check_overlap(tile, overlap):
+    if isinstance(overlap, (bool, np.bool_)) or not isinstance(overlap, (int, np.integer)):
+        raise ValueError(f'overlap must be an int, got {overlap!r}')
+    if not 0 <= int(overlap) <= int(tile) // 2:
+        raise ValueError(f'overlap must be between 0 and half the tile ({int(tile) // 2} for tiles of {int(tile)}), got {overlap}')
+    return int(overlap)
+
+
+def _overlap_pair(overlap, Ht, Wt):
+    """``overlap`` as an int or ``(oy, ox)`` -> both, each validated against its axis."""
+    if isinstance(overlap, (tuple, list)):
+        if len(overlap) != 2:
+            raise ValueError(f'overlap must be an int or (overlap_y, overlap_x), got {overlap!r}')
+        oy, ox = overlap
+    else:
+        oy = ox = overlap
+    return _check_overlap(Ht, oy), _check_overlap(Wt, ox)
+
+
+def tile_origins(length: int, tile: int, overlap: int):
+    """One axis of the tiling rule: the origins, in frame coordinates, of the tiles of length ``tile`` that
+    cover ``length`` with consecutive tiles sharing at least ``overlap`` pixels.  A frame no longer than the tile takes one tile
+    with the frame where ``resize_with_crop_or_pad`` puts it (origin ``-((tile - length) // 2)``); a longer one takes
+    ``ceil((length - tile) / (tile - overlap)) + 1`` tiles spread evenly from 0 to ``length - tile``, rounded half up."""
+    L, T = int(length), int(tile)
+    if L < 1 or T < 1:
+        raise ValueError(f'sizes must be >= 1, got a frame of {L} and tiles of {T}')
+    o = _check_overlap(T, overlap)
+    if L <= T:
+        return [-((T - L) // 2)]
+    n = -(-(L - T) // (T - o)) + 1
+    return [(2 * i * (L - T) + (n - 1)) // (2 * (n - 1)) for i in range(n)]
+
+
+def tile_taps(length: int, tile: int, origins):
+    """The blend table of one axis, in float64: ``(first, count, weights)`` with ``first[p]`` the first tile that covers frame
+    coordinate ``p``, ``count[p]`` how many consecutive tiles do and ``weights[p, :count[p]]`` their tent weights
+    ``min(t + 1, tile - t)`` at the tile-local coordinate ``t = p - origin``, normalised to sum 1 (the rest of the row is 0)."""
+    L, T = int(length), int(tile)
+    org = np.asarray(list(origins), np.int64)
+    if L < 1 or T < 1 or org.ndim != 1 or org.size < 1:
+        raise ValueError(f'expected sizes >= 1 and at least one origin, got {L}, {T}, {origins!r}')
+    if np.any(np.diff(org) < 1):
+        raise ValueError(f'origins must increase, got {origins!r}')
+    t = np.arange(L, dtype=np.int64)[:, None] - org[None, :]
+    cover = (t >= 0) & (t < T)
+    count = cover.sum(axis=1)
+    if np.any(count < 1):
+        raise ValueError(f'tiles of {T} at {origins!r} do not cover a frame of {L}')
+    first = cover.argmax(axis=1)
+    w = np.where(cover, np.minimum(t + 1, T - t), 0).astype(np.float64)
+    j = first[:, None] + np.arange(int(count.max()), dtype=np.int64)[None, :]
+    inside = j < (first + count)[:, None]                    # (tiles of one length with increasing origins cover a run)
+    w = np.where(inside, np.take_along_axis(w, np.minimum(j, org.size - 1), axis=1), 0.0)
+    w /= w.sum(axis=1, keepdims=True)
+    return first.astype(np.int32), count.astype(np.int32), w
+
+
+def _tile_axis_table(device, length, tile, overlap):
+    def make():
+        first, count, w = tile_taps(length, tile, tile_origins(length, tile, overlap))
+        if w.shape[1] > TILE_MAX_TAPS:
+            raise ValueError(f'{w.shape[1]} tiles of {tile} overlap in one coordinate of {length}, the kernel takes up to {TILE_MAX_TAPS}')
+        return _DeviceTable([np.stack([first, count]), w.astype(np.float32)], device, w.shape[1])
+    return _table(device, ('tile', int(length), int(tile), int(overlap)), make)
+
+
+class TilePlan:
+    """The tile grid of ``(H, W)`` frames under ``(Ht, Wt)`` tiles (``tile_origins`` per axis, ``K = ny * nx`` tiles per frame,
+    tile ``ky * nx + kx`` at ``(origins_y[ky], origins_x[kx])``) and the two device tables of the blend.  ``overlap``: an int or
+    ``(overlap_y, overlap_x)``.  Made (and, the first time, uploaded) on the CURRENT stream.  What the kernels cannot take -- more
+    than ``TILE_MAX_PER_AXIS`` tiles per axis, more than ``TILE_MAX_TAPS`` tiles over one coordinate -- is a ``ValueError`` here."""
+
+    def __init__(self, device, H, W, Ht, Wt, overlap):
+        self.device = device
+        self.frame, self.tile = (int(H), int(W)), (int(Ht), int(Wt))
+        self.overlap = _overlap_pair(overlap, Ht, Wt)
+        self.origins_y = tile_origins(H, Ht, self.overlap[0])
+        self.origins_x = tile_origins(W, Wt, self.overlap[1])
+        self.ny, self.nx = len(self.origins_y), len(self.origins_x)
+        self.K = self.ny * self.nx
+        if max(self.ny, self.nx) > TILE_MAX_PER_AXIS:
+            raise ValueError(f'{self.frame} frames take {self.ny} x {self.nx} tiles of {self.tile}, the kernels take up to '
+                             f'{TILE_MAX_PER_AXIS} per axis')
+        self.origins = _ffi.TileOrigins(self.ny, self.nx)
+        self.origins.oy[:self.ny] = self.origins_y
+        self.origins.ox[:self.nx] = self.origins_x
+        self.ys = _tile_axis_table(device, H, Ht, self.overlap[0])
+        self.xs = _tile_axis_table(device, W, Wt, self.overlap[1])
+
+    def tensors(self):
+        return self.ys.tensors + self.xs.tensors
+
+
+def tile_gather_launch(t: torch.Tensor, plan: TilePlan, out=None) -> torch.Tensor:
+    """The launch itself: contiguous device ``(N, H, W, C)`` of uint8 / bool / float32 -> float32 ``(N * K, Ht, Wt, C)`` on the
+    CURRENT stream (plain ``torch.Tensor``), written into ``out`` when given (contiguous, of the result's shape)."""
+    N, H, W, Cn = t.shape
+    if (H, W) != plan.frame or t.device != plan.device:
+        raise ValueError(f'plan of {plan.frame} on {plan.device} used on {(H, W)} on {t.device}')
+    lib = _dev.lib()
+    if t.dtype == torch.float32:
+        fn, src = lib.raft_tile_gather_f32, t
+    elif t.dtype in (torch.uint8, torch.bool):
+        fn, src = lib.raft_tile_gather_u8_f32, t.view(torch.uint8)
+    else:
+        raise TypeError(f'tile_gather takes uint8, bool or float32, got {t.dtype}')
+    shape = (N * plan.K,) + plan.tile + (Cn,)
+    if out is None:
+        out = torch.empty(shape, device=t.device, dtype=torch.float32)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != t.device or not out.is_contiguous():
+        raise ValueError(f'out must be a contiguous float32 tensor of shape {shape} on {t.device}')
+    with torch.cuda.device(t.device):
+        check(fn(_dev.ptr(src), _dev.ptr(out), N, H, W, plan.tile[0], plan.tile[1], Cn, plan.origins, _dev.stream_ptr()), 'tile_gather')
+    return out
+
+
+def tile_blend_launch(t: torch.Tensor, plan: TilePlan, out=None) -> torch.Tensor:
+    """The launch itself: contiguous float32 device ``(M, N * K, Ht, Wt, 2)`` -> ``(M, N, H, W, 2)`` on the CURRENT stream (plain
+    ``torch.Tensor``), written into ``out`` when given (contiguous, of the result's shape)."""
+    M, NK, Ht, Wt, Cn = t.shape
+    if (Ht, Wt) != plan.tile or t.device != plan.device:
+        raise ValueError(f'plan of {plan.tile} tiles on {plan.device} used on {(Ht, Wt)} on {t.device}')
+    if t.dtype != torch.float32:
+        raise TypeError(f'tile_blend takes float32, got {t.dtype}')
+    if Cn != 2:
+        raise ValueError(f'a flow has 2 channels, got {Cn}')
+    if NK % plan.K:
+        raise ValueError(f'{NK} tiles are no whole number of frames of {plan.ny} x {plan.nx} tiles')
+    H, W = plan.frame
+    shape = (M, NK // plan.K, H, W, 2)
+    if out is None:
+        out = torch.empty(shape, device=t.device, dtype=torch.float32)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != t.device or not out.is_contiguous():
+        raise ValueError(f'out must be a contiguous float32 tensor of shape {shape} on {t.device}')
+    if t.data_ptr() % 8 or out.data_ptr() % 8:
+        raise ValueError('tile_blend reads and writes whole flow vectors: tiles and out must be 8-byte aligned')
+    with torch.cuda.device(t.device):
+        (yi, yw), (xi, xw) = plan.ys.use(t.device), plan.xs.use(t.device)
+        check(_dev.lib().raft_tile_blend_f32(_dev.ptr(t), _dev.ptr(out), M, shape[1], H, W, Ht, Wt, plan.origins,
+                                             _dev.ptr(yi), _dev.ptr(yi) + 4 * H, _dev.ptr(yw), plan.ys.max_taps,
+                                             _dev.ptr(xi), _dev.ptr(xi) + 4 * W, _dev.ptr(xw), plan.xs.max_taps, _dev.stream_ptr()), 'tile_blend')
+    return out
+
+
+def _check_out(out, shape, device):
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != torch.float32
+                            or out.device != device or not out.is_contiguous()):
+        raise ValueError(f'out must be a contiguous float32 tensor of shape {shape} on {device}')
+    return None if out is None else out.as_subclass(torch.Tensor)
+
+
+def tile_gather(x, height: int, width: int, overlap=64, out=None) -> torch.Tensor:
+    """The tiles of ``(H, W, C)`` or ``(N, H, W, C)`` frames under the tiling rule (``tile_origins`` per axis with tiles of
+    ``height x width``; ``overlap`` an int or ``(overlap_y, overlap_x)``): NumPy or torch, host or device, uint8 / bool / float32
+    (float64 narrows) -> a contiguous float32 device tensor ``(N * K, height, width, C)`` (``out`` when given) with frame ``n``'s
+    tile ``(ky, kx)`` at index ``(n * ny + ky) * nx + kx``, zero outside the frame.  One launch on the current stream.  Frames
+    that already have the tile's size are returned unchanged, cast to float32 if needed (no launch)."""
+    height, width = int(height), int(width)
+    if height < 1 or width < 1:
+        raise ValueError(f'tile size must be >= 1, got {height} x {width}')
+    pair = _overlap_pair(overlap, height, width)
+    t = _on_device(x)
+    if t.dim() not in (3, 4):
+        raise ValueError(f'expected (H, W, C) or (N, H, W, C), got {tuple(t.shape)}')
+    if 0 in t.shape:
+        raise ValueError(f'empty input {tuple(t.shape)}')
+    if t.dtype not in (torch.float32, torch.uint8, torch.bool):
+        raise TypeError(f'tile_gather takes uint8, bool or float32, got {t.dtype}')
+    t4 = t if t.dim() == 4 else t[None]
+    if tuple(t4.shape[1:3]) == (height, width):
+        out = _check_out(out, tuple(t4.shape), t.device)
+        t4 = t4 if t4.dtype == torch.float32 else t4.to(torch.float32)
+        return _dev.wrap(t4 if out is None else out.copy_(t4))
+    with torch.cuda.device(t.device):
+        plan = TilePlan(t.device, t4.shape[1], t4.shape[2], height, width, pair)
+    out = _check_out(out, (t4.shape[0] * plan.K, height, width, t4.shape[3]), t.device)
+    return _dev.wrap(tile_gather_launch(t4, plan, out))
+
+
+def tile_blend(tiles, H: int, W: int, overlap=64, out=None) -> torch.Tensor:
+    """The way back: float32 predictions ``(..., N * K, Ht, Wt, 2)`` on the tiles of ``tile_gather`` (same ``overlap``) ->
+    ``(..., N, H, W, 2)`` at the frames' own size (``out`` when given), every pixel the tent-weighted mean of the tiles that cover
+    it (``tile_taps``), over any leading axes in one launch on the current stream.  Flow vectors are not scaled: the tiles are at
+    the frame's resolution.  Tiles of the frame's own size are returned unchanged (no launch)."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f'frame size must be >= 1, got {H} x {W}')
+    shape = tuple(tiles.shape) if hasattr(tiles, 'shape') else np.shape(tiles)
+    if len(shape) < 4:
+        raise ValueError(f'expected (..., N * K, Ht, Wt, 2), got {shape}')
+    if 0 in shape:
+        raise ValueError(f'empty input {shape}')
+    if shape[-1] != 2:
+        raise ValueError(f'a flow has 2 channels, got {shape}')
+    Ht, Wt = (int(v) for v in shape[-3:-1])
+    pair = _overlap_pair(overlap, Ht, Wt)
+    t = _on_device(tiles)
+    if t.dtype != torch.float32:
+        raise TypeError(f'tile_blend takes float32, got {t.dtype}')
+    lead = tuple(t.shape[:-4])
+    if (Ht, Wt) == (H, W):
+        out = _check_out(out, tuple(t.shape), t.device)
+        return _dev.wrap(t if out is None else out.copy_(t))
+    with torch.cuda.device(t.device):
+        plan = TilePlan(t.device, H, W, Ht, Wt, pair)
+    if t.shape[-4] % plan.K:
+        raise ValueError(f'{t.shape[-4]} tiles are no whole number of frames of {plan.ny} x {plan.nx} tiles')
+    shape = lead + (t.shape[-4] // plan.K, H, W, 2)
+    out = _check_out(out, shape, t.device)
+    res = tile_blend_launch(t.reshape((-1,) + tuple(t.shape[-4:])), plan, None if out is None else out.view((-1,) + shape[-4:]))
+    return _dev.wrap(res.view(shape))
 
 
 # ---------------------------------------------------------------------------------------------------------- colour coding

@@ -83,7 +83,7 @@ class RAFT:
 
     def __init__(self, drop_rate=0, iters=12, iters_pred=24, weights: Optional[Dict[str, np.ndarray]] = None,
                  seed=0, alternate_corr=False, overlap=None, pipeline=None, lanes=None, loop_concurrency=None, target_size=None,
-                 fit='crop_or_pad', antialias=True, **kwargs):
+                 fit='crop_or_pad', antialias=True, tile_overlap=None, **kwargs):
         # reference model.py:11-12 forwards **kwargs to tf.keras.Model, whose constructor takes `name` (and nothing a
         # forward pass depends on): accept it, reject the rest
         self.name = kwargs.pop('name', type(self).__name__.lower())
@@ -106,7 +106,10 @@ class RAFT:
         # How the frames reach the model's size: 'crop_or_pad' = the reference's rule above; 'resize' = bilinear interpolation with
         # half-pixel centres (tf.image.resize; `antialias` widens the triangle where an axis shrinks), the returned flow resized
         # back with u scaled by W / Wt and v by H / Ht -- for frames much larger than the model's size.
+        # 'tile' = overlapping tiles of the model's size at the frame's own resolution, run as one batch and cross-faded back
+        # (`tile_overlap` pixels, an int or (overlap_y, overlap_x), at least shared by neighbouring tiles).
         self.fit, self.antialias = self._check_fit(fit, antialias, self.target_size)
+        self.tile_overlap = self._check_tile_overlap(self.fit, tile_overlap, self.target_size)
         # three-stream schedule of the loop (RAFT only); RAFT_OVERLAP=0 forces the single-stream loop.  With several lanes
         # (below) the loops of a pipelined call default to the single-stream schedule: the other lanes fill the chain's idle CUs
         # and gaps better than a loop's own side branches do (profiles/r12b_lanes_ab_per_process.txt).
@@ -157,13 +160,25 @@ class RAFT:
 
     @staticmethod
     def _check_fit(fit, antialias, target_size):
-        if fit not in ('crop_or_pad', 'resize'):
-            raise ValueError(f"fit must be 'crop_or_pad' or 'resize', got {fit!r}")
+        if fit not in ('crop_or_pad', 'resize', 'tile'):
+            raise ValueError(f"fit must be 'crop_or_pad', 'resize' or 'tile', got {fit!r}")
+        if fit == 'tile' and not isinstance(target_size, tuple):
+            raise ValueError("fit='tile' needs a target_size (height, width): the size of a tile")
         if fit == 'resize' and target_size is None:
             raise ValueError("fit='resize' needs a target_size ('auto' or (height, width))")
         if not isinstance(antialias, (bool, np.bool_)):
             raise ValueError(f'antialias must be True or False, got {antialias!r}')
         return fit, bool(antialias)
+
+    DEFAULT_TILE_OVERLAP = 64      # eight feature cells of context on each side of a seam: a choice, not a measured optimum
+
+    @classmethod
+    def _check_tile_overlap(cls, fit, tile_overlap, target_size):
+        if fit != 'tile':
+            if tile_overlap is not None:
+                raise ValueError(f"tile_overlap belongs to fit='tile', got fit={fit!r}")
+            return None
+        return image_ops._overlap_pair(cls.DEFAULT_TILE_OVERLAP if tile_overlap is None else tile_overlap, *target_size)
 
     def _model_size(self, H, W):
         """The size the model runs at for frames of H x W under ``target_size``."""
@@ -174,7 +189,8 @@ class RAFT:
     def _fit_frames(self, image1, image2):
         """``target_size`` set: both frames as float32 device tensors of the model's size, and the frames' own (H, W) when that
         differs (None: nothing was launched).  uint8 frames are cast and windowed (or resized) in one pass.  ``fit='resize'``: the
-        third entry of the returned window is the plan of the flow's way back, its tables already on the device."""
+        third entry of the returned window is the plan of the flow's way back, its tables already on the device.  ``fit='tile'``:
+        each frame becomes its K tiles (batch N * K), the third entry is the ``TilePlan``."""
         image1, image2 = image_ops._on_device(image1), image_ops._on_device(image2)
         if image1.dim() != 4 or image1.shape[-1] != 3 or image1.shape != image2.shape or image1.dtype != image2.dtype or 0 in image1.shape:
             raise ValueError(f'images must both be (bs, H, W, 3) of one type, got {tuple(image1.shape)} {image1.dtype} / '
@@ -192,12 +208,21 @@ class RAFT:
                 fwd = image_ops.ResizePlan(image1.device, H, W, th, tw, self.antialias)
                 back = image_ops.ResizePlan(image1.device, th, tw, H, W, self.antialias, flow=True)
             return image_ops.resize_launch(image1, fwd), image_ops.resize_launch(image2, fwd), (H, W, back)
+        if self.fit == 'tile':
+            with torch.cuda.device(image1.device):
+                plan = image_ops.TilePlan(image1.device, H, W, th, tw, self.tile_overlap)      # (tables: as above)
+            return image_ops.tile_gather_launch(image1, plan), image_ops.tile_gather_launch(image2, plan), (H, W, plan)
         return (image_ops.window_copy(image1, th, tw, torch.float32), image_ops.window_copy(image2, th, tw, torch.float32), (H, W))
 
     @staticmethod
     def _fit_flow(out, window, into=None):
         """Predictions (..., Ht, Wt, 2) of the model's size -> the frames' own size, ONE launch over all leading axes, on the
         current stream."""
+        if len(window) > 2 and isinstance(window[2], image_ops.TilePlan):
+            lead = tuple(out.shape[:-4])
+            res = image_ops.tile_blend_launch(out.view((-1,) + tuple(out.shape[-4:])), window[2],
+                                              out=None if into is None else into.view((-1,) + tuple(into.shape[-4:])))
+            return res.view(lead + tuple(res.shape[-4:]))
         lead = tuple(out.shape[:-3])
         if len(window) > 2:
             res = image_ops.resize_launch(out.view((-1,) + tuple(out.shape[-3:])), window[2],
@@ -531,7 +556,9 @@ class RAFT:
         correlation = CorrBlock(fmap1, fmap2, num_levels=self.corr_levels, radius=self.corr_radius,
                                 alternate=self.alternate_corr)                           # model.py:77
         out = self._alloc_out(self.iters_pred, B, H, W, dev, final_only)      # from the caller's stream's pool, like every other buffer
-        res = out if window is None else self._alloc_out(self.iters_pred, B, window[0], window[1], dev, final_only)
+        # (the tiles of fit='tile' are a batch of N * K: the result has the frames' batch)
+        frames = B // window[2].K if window is not None and len(window) > 2 and isinstance(window[2], image_ops.TilePlan) else B
+        res = out if window is None else self._alloc_out(self.iters_pred, frames, window[0], window[1], dev, final_only)
         ready = torch.cuda.Event()
         ready.record(cur)
         loop.wait_event(ready)
