@@ -275,6 +275,41 @@ def test_pipelined_calls_with_auto_target_are_bitwise_the_serial_calls(variant, 
         np.testing.assert_array_equal(_np(ps[k]), got[k][-1])
 
 
+# ------------------------------------------------------------------ the route object
+@pytest.mark.parametrize('fit,antialias', [('crop_or_pad', True), ('resize', False), ('resize', True), ('tile', True)])
+def test_route_object_is_bitwise_the_public_functions(fit, antialias):
+    """The one object ``_fit_frames`` builds per call, asked directly: frames in, result size, flow back (fresh and into a
+    caller's tensor) and tables, bit for bit the public functions, which have kernel tests of their own.  Tiles of 64 x 96 at
+    overlap 16: the 100 x 150 frames take 2 x 2 tiles, the 60 x 200 frame one padded row of 3."""
+    from tf_raft_amd import image_ops
+    th, tw, ov = 64, 96, 16
+    overlap = _cls('raft')._check_tile_overlap(fit, ov if fit == 'tile' else None, (th, tw))        # as the constructor keeps it
+    rng = np.random.default_rng(23)
+    for x, K in ((rng.integers(0, 256, size=(2, 100, 150, 3), dtype=np.uint8), 4), (rng.uniform(0, 255, (1, 60, 200, 3)).astype(np.float32), 3)):
+        t = torch.as_tensor(x).cuda()
+        N, H, W, _ = t.shape
+        route = image_ops.fit_route(fit, t.device, H, W, th, tw, antialias, overlap)
+        want_in = {'crop_or_pad': lambda: image_ops.resize_with_crop_or_pad(t, th, tw, torch.float32),
+                   'resize': lambda: image_ops.resize(t, th, tw, antialias), 'tile': lambda: image_ops.tile_gather(t, th, tw, ov)}[fit]()
+        got_in = route.frames_in(t)
+        B = N * K if fit == 'tile' else N
+        assert got_in.dtype == torch.float32 and tuple(got_in.shape) == (B, th, tw, 3)
+        np.testing.assert_array_equal(_np(got_in), _np(want_in))
+        pred = torch.as_tensor(rng.normal(size=(3, B, th, tw, 2)).astype(np.float32) * 4).cuda()
+        want = {'crop_or_pad': lambda: torch.stack([image_ops.resize_with_crop_or_pad(p, H, W) for p in pred]),
+                'resize': lambda: image_ops.resize_flow(pred, H, W, antialias), 'tile': lambda: image_ops.tile_blend(pred, H, W, ov)}[fit]()
+        assert tuple(want.shape) == (3, N, H, W, 2) and route.result_size(B) == tuple(want.shape[1:4])
+        fresh = route.flow_back(pred)
+        assert tuple(fresh.shape) == (3, N, H, W, 2) and fresh.is_contiguous()
+        np.testing.assert_array_equal(_np(fresh), _np(want))
+        into = torch.full((3, N, H, W, 2), float('nan'), device='cuda')
+        assert route.flow_back(pred, into=into) is into
+        np.testing.assert_array_equal(_np(into), _np(want))
+        tables = route.tensors()
+        assert isinstance(tables, list) and all(isinstance(v, torch.Tensor) and v.is_cuda for v in tables)
+        assert (len(tables) == 0) == (fit == 'crop_or_pad')
+
+
 # ------------------------------------------------------------------ against the CPU oracle
 def _conditioned(variant, H, W, seed):
     sys.path.insert(0, GOLDEN)

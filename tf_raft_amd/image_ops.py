@@ -27,6 +27,12 @@ scaled.
 ``flow_to_image`` is the reference's flow colour coding (tf_raft/datasets/flow_viz.py) as two launches
 (``raft_flow_rad_max_f32`` / ``raft_flow_to_image_u8``, tf_raft_amd/csrc/flow_viz.hip), optionally seen
 through the same crop-or-pad window, so a prediction leaves the device as a 3-byte picture instead of an 8-byte flow.
+
+The model reaches the three ways through ONE object per call (``fit_route``: a ``CropOrPadRoute``, a ``ResizeRoute`` or a
+``TilePlan``), which answers the same four questions whichever way it is: ``frames_in(t)`` (a frame batch -> the float32 batch
+the model runs on, one launch), ``result_size(B)`` (batch and size of the result for a model batch ``B``), ``flow_back(pred,
+into)`` (predictions over any leading axes -> the frames' own size, one launch) and ``tensors()`` (the device tables a launch
+on another stream reads).  Making the object makes -- the first time: uploads -- both directions' tables on the current stream.
 """
 from __future__ import annotations
 
@@ -62,6 +68,49 @@ def _on_device(x) -> torch.Tensor:
     return t.contiguous()
 
 
+_FRAME_TYPES = (torch.float32, torch.uint8, torch.bool)
+
+
+def _entry(x, what, dtypes=_FRAME_TYPES, lead=False):
+    """What every public op asks of its input before any launch: ``(H, W, C)`` or ``(N, H, W, C)`` (``lead``: any leading axes),
+    not empty, of one of ``dtypes`` (None: the caller judges).  Returns the contiguous device tensor and its 4-D view."""
+    t = _on_device(x)
+    if t.dim() < 3 or (t.dim() > 4 and not lead):
+        raise ValueError(f'{what} expects {"(..., H, W, C)" if lead else "(H, W, C) or (N, H, W, C)"}, got {tuple(t.shape)}')
+    if 0 in t.shape:
+        raise ValueError(f'empty input {tuple(t.shape)}')
+    if dtypes is not None and t.dtype not in dtypes:
+        raise TypeError(f'{what} takes {" / ".join(str(d)[6:] for d in dtypes)}, got {t.dtype}')
+    return t, t.reshape((-1,) + tuple(t.shape[-3:]))
+
+
+def _check_out(out, shape, dtype, device, alloc=True):
+    """The tensor a launch writes: the caller's ``out`` as a plain tensor if it is a contiguous one of exactly this shape, type and
+    device (anything else is a ``ValueError``), without one a new tensor (``alloc=False``: None, for a check ahead of the launch)."""
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype) if alloc else None
+    if (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device
+            or not out.is_contiguous()):
+        raise ValueError(f'out must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}')
+    return out if type(out) is torch.Tensor else out.as_subclass(torch.Tensor)
+
+
+def _over_leading(launch, t, keep, out=None):
+    """``launch(t', out')`` with all axes of ``t`` in front of its last ``keep`` folded into one (``out`` likewise): ONE launch over
+    any leading axes.  Returns ``out``, or the new result with ``t``'s leading axes back."""
+    res = launch(t.reshape((-1,) + tuple(t.shape[-keep:])), None if out is None else out.view((-1,) + tuple(out.shape[-keep:])))
+    return out if out is not None else res.view(tuple(t.shape[:-keep]) + tuple(res.shape[1:]))
+
+
+def _source_entry(t, what):
+    """``raft_<what>_f32`` or ``raft_<what>_u8_f32`` for a float32 or uint8 / bool source, and the tensor to read it through."""
+    if t.dtype == torch.float32:
+        return getattr(_dev.lib(), f'raft_{what}_f32'), t
+    if t.dtype in (torch.uint8, torch.bool):
+        return getattr(_dev.lib(), f'raft_{what}_u8_f32'), t.view(torch.uint8)
+    raise TypeError(f'{what} takes uint8, bool or float32, got {t.dtype}')
+
+
 def window_copy(t: torch.Tensor, target_height: int, target_width: int, dtype=None, out=None) -> torch.Tensor:
     """The launch itself: contiguous device ``(N, H, W, C)`` of uint8 / bool / float32 -> a new ``(N, Ht, Wt, C)`` tensor on the
     CURRENT stream (plain ``torch.Tensor``; the callers wrap it).  ``out``: a contiguous tensor of the result's shape and type to
@@ -76,11 +125,7 @@ def window_copy(t: torch.Tensor, target_height: int, target_width: int, dtype=No
         fn, src, out_dtype = lib.raft_crop_or_pad_u8, t.view(torch.uint8), torch.uint8
     else:
         raise TypeError(f'resize_with_crop_or_pad takes uint8, bool or float32 (optionally uint8 -> float32), got {t.dtype} -> {dtype}')
-    shape = (N, int(target_height), int(target_width), Cn)
-    if out is None:
-        out = torch.empty(shape, device=t.device, dtype=out_dtype)
-    elif tuple(out.shape) != shape or out.dtype != out_dtype or out.device != t.device or not out.is_contiguous():
-        raise ValueError(f'out must be a contiguous {out_dtype} tensor of shape {shape} on {t.device}')
+    out = _check_out(out, (N, int(target_height), int(target_width), Cn), out_dtype, t.device)
     with torch.cuda.device(t.device):
         check(fn(_dev.ptr(src), _dev.ptr(out), N, H, W, int(target_height), int(target_width), Cn, _dev.stream_ptr()), 'crop_or_pad')
     return out.view(torch.bool) if (t.dtype == torch.bool and dtype is None) else out
@@ -95,19 +140,14 @@ def resize_with_crop_or_pad(x, target_height: int, target_width: int, dtype=None
     target_height, target_width = int(target_height), int(target_width)
     if target_height < 1 or target_width < 1:
         raise ValueError(f'target size must be >= 1, got {target_height} x {target_width}')
-    t = _on_device(x)
-    if t.dim() not in (3, 4):
-        raise ValueError(f'expected (H, W, C) or (N, H, W, C), got {tuple(t.shape)}')
-    if 0 in t.shape:
-        raise ValueError(f'empty input {tuple(t.shape)}')
+    t, _ = _entry(x, 'resize_with_crop_or_pad', dtypes=None)      # (the PAIR of types is window_copy's to judge)
     if tuple(t.shape[-3:-1]) == (target_height, target_width):
         if dtype is not None and dtype != t.dtype:
             if not (t.dtype in (torch.uint8, torch.bool) and dtype == torch.float32):
                 raise TypeError(f'resize_with_crop_or_pad takes uint8, bool or float32 (optionally uint8 -> float32), got {t.dtype} -> {dtype}')
             t = t.to(dtype)
         return _dev.wrap(t)
-    out = window_copy(t if t.dim() == 4 else t[None], target_height, target_width, dtype)
-    return _dev.wrap(out if t.dim() == 4 else out[0])
+    return _dev.wrap(_over_leading(lambda s, o: window_copy(s, target_height, target_width, dtype), t, 3))
 
 
 # ---------------------------------------------------------------------------------------------------------------- resize
@@ -175,13 +215,20 @@ def _table(device, key, make):
     return ent
 
 
-def _axis_table(device, n_in, n_out, antialias):
+def _taps_table(device, key, taps, limit, too_many):
+    """The cached device table of one axis: ``taps()`` gives ``(first, count, weights)``; rows wider than ``limit`` are a
+    ``ValueError`` saying ``too_many(width)``."""
     def make():
-        first, count, w = resize_taps(n_in, n_out, antialias)
-        if w.shape[1] > RESIZE_MAX_TAPS:
-            raise ValueError(f'resize {n_in} -> {n_out} needs {w.shape[1]} taps per output, the kernel takes up to {RESIZE_MAX_TAPS}')
+        first, count, w = taps()
+        if w.shape[1] > limit:
+            raise ValueError(f'{too_many(w.shape[1])}, the kernel takes up to {limit}')
         return _DeviceTable([np.stack([first, count]), w.astype(np.float32)], device, w.shape[1])
-    return _table(device, (int(n_in), int(n_out), bool(antialias)), make)
+    return _table(device, key, make)
+
+
+def _axis_table(device, n_in, n_out, antialias):
+    return _taps_table(device, (int(n_in), int(n_out), bool(antialias)), lambda: resize_taps(n_in, n_out, antialias), RESIZE_MAX_TAPS,
+                       lambda k: f'resize {n_in} -> {n_out} needs {k} taps per output')
 
 
 class ResizePlan:
@@ -217,19 +264,9 @@ def resize_launch(t: torch.Tensor, plan: ResizePlan, out=None) -> torch.Tensor:
     N, H, W, Cn = t.shape
     if (H, W) != plan.source or t.device != plan.device:
         raise ValueError(f'plan of {plan.source} on {plan.device} used on {(H, W)} on {t.device}')
-    lib = _dev.lib()
-    if t.dtype == torch.float32:
-        fn, src = lib.raft_resize_f32, t
-    elif t.dtype in (torch.uint8, torch.bool):
-        fn, src = lib.raft_resize_u8_f32, t.view(torch.uint8)
-    else:
-        raise TypeError(f'resize takes uint8, bool or float32, got {t.dtype}')
+    fn, src = _source_entry(t, 'resize')
     plan.check(Cn, src.element_size())
-    shape = (N,) + plan.target + (Cn,)
-    if out is None:
-        out = torch.empty(shape, device=t.device, dtype=torch.float32)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != t.device or not out.is_contiguous():
-        raise ValueError(f'out must be a contiguous float32 tensor of shape {shape} on {t.device}')
+    out = _check_out(out, (N,) + plan.target + (Cn,), torch.float32, t.device)
     with torch.cuda.device(t.device):
         (yi, yw), (xi, xw) = plan.ys.use(t.device), plan.xs.use(t.device)
         cs = plan.scale.use(t.device)[0] if plan.scale is not None else None
@@ -245,25 +282,15 @@ def _resize(x, height, width, antialias, out, flow):
     height, width = int(height), int(width)
     if height < 1 or width < 1:
         raise ValueError(f'target size must be >= 1, got {height} x {width}')
-    t = _on_device(x)
-    if t.dim() < 3 or (not flow and t.dim() > 4):
-        raise ValueError(f'expected {"(..., H, W, 2)" if flow else "(H, W, C) or (N, H, W, C)"}, got {tuple(t.shape)}')
-    if 0 in t.shape:
-        raise ValueError(f'empty input {tuple(t.shape)}')
-    if t.dtype not in ((torch.float32,) if flow else (torch.float32, torch.uint8, torch.bool)):
-        raise TypeError(f'{"resize_flow takes float32" if flow else "resize takes uint8, bool or float32"}, got {t.dtype}')
+    t, _ = _entry(x, 'resize_flow' if flow else 'resize', (torch.float32,) if flow else _FRAME_TYPES, lead=flow)
     if flow and t.shape[-1] != 2:
         raise ValueError(f'a flow has 2 channels, got {tuple(t.shape)}')
-    shape = tuple(t.shape[:-3]) + (height, width, t.shape[-1])
-    if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != t.device or not out.is_contiguous()):
-        raise ValueError(f'out must be a contiguous float32 tensor of shape {shape} on {t.device}')
+    out = _check_out(out, tuple(t.shape[:-3]) + (height, width, t.shape[-1]), torch.float32, t.device, alloc=False)
     if tuple(t.shape[-3:-1]) == (height, width):
         t = t if t.dtype == torch.float32 else t.to(torch.float32)
         return _dev.wrap(t if out is None else out.copy_(t))
-    with torch.cuda.device(t.device):
-        plan = ResizePlan(t.device, t.shape[-3], t.shape[-2], height, width, antialias, flow)
-    res = resize_launch(t.reshape((-1,) + tuple(t.shape[-3:])), plan, None if out is None else out.view((-1,) + shape[-3:]))
-    return _dev.wrap(res.view(shape))
+    plan = ResizePlan(t.device, t.shape[-3], t.shape[-2], height, width, antialias, flow)
+    return _dev.wrap(_over_leading(lambda s, o: resize_launch(s, plan, o), t, 3, out))
 
 
 def resize(x, height: int, width: int, antialias: bool = False, out=None) -> torch.Tensor:
@@ -345,12 +372,8 @@ def tile_taps(length: int, tile: int, origins):
 
 
 def _tile_axis_table(device, length, tile, overlap):
-    def make():
-        first, count, w = tile_taps(length, tile, tile_origins(length, tile, overlap))
-        if w.shape[1] > TILE_MAX_TAPS:
-            raise ValueError(f'{w.shape[1]} tiles of {tile} overlap in one coordinate of {length}, the kernel takes up to {TILE_MAX_TAPS}')
-        return _DeviceTable([np.stack([first, count]), w.astype(np.float32)], device, w.shape[1])
-    return _table(device, ('tile', int(length), int(tile), int(overlap)), make)
+    return _taps_table(device, ('tile', int(length), int(tile), int(overlap)), lambda: tile_taps(length, tile, tile_origins(length, tile, overlap)),
+                       TILE_MAX_TAPS, lambda k: f'{k} tiles of {tile} overlap in one coordinate of {length}')
 
 
 class TilePlan:
@@ -379,6 +402,16 @@ class TilePlan:
     def tensors(self):
         return self.ys.tensors + self.xs.tensors
 
+    # the route of fit='tile' (see ``fit_route``): the tiles of a frame batch are a model batch of N * K
+    def frames_in(self, t):
+        return tile_gather_launch(t, self)
+
+    def result_size(self, B):
+        return (B // self.K,) + self.frame
+
+    def flow_back(self, pred, into=None):
+        return _over_leading(lambda s, o: tile_blend_launch(s, self, o), pred, 4, into)
+
 
 def tile_gather_launch(t: torch.Tensor, plan: TilePlan, out=None) -> torch.Tensor:
     """The launch itself: contiguous device ``(N, H, W, C)`` of uint8 / bool / float32 -> float32 ``(N * K, Ht, Wt, C)`` on the
@@ -386,18 +419,8 @@ def tile_gather_launch(t: torch.Tensor, plan: TilePlan, out=None) -> torch.Tenso
     N, H, W, Cn = t.shape
     if (H, W) != plan.frame or t.device != plan.device:
         raise ValueError(f'plan of {plan.frame} on {plan.device} used on {(H, W)} on {t.device}')
-    lib = _dev.lib()
-    if t.dtype == torch.float32:
-        fn, src = lib.raft_tile_gather_f32, t
-    elif t.dtype in (torch.uint8, torch.bool):
-        fn, src = lib.raft_tile_gather_u8_f32, t.view(torch.uint8)
-    else:
-        raise TypeError(f'tile_gather takes uint8, bool or float32, got {t.dtype}')
-    shape = (N * plan.K,) + plan.tile + (Cn,)
-    if out is None:
-        out = torch.empty(shape, device=t.device, dtype=torch.float32)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != t.device or not out.is_contiguous():
-        raise ValueError(f'out must be a contiguous float32 tensor of shape {shape} on {t.device}')
+    fn, src = _source_entry(t, 'tile_gather')
+    out = _check_out(out, (N * plan.K,) + plan.tile + (Cn,), torch.float32, t.device)
     with torch.cuda.device(t.device):
         check(fn(_dev.ptr(src), _dev.ptr(out), N, H, W, plan.tile[0], plan.tile[1], Cn, plan.origins, _dev.stream_ptr()), 'tile_gather')
     return out
@@ -417,10 +440,7 @@ def tile_blend_launch(t: torch.Tensor, plan: TilePlan, out=None) -> torch.Tensor
         raise ValueError(f'{NK} tiles are no whole number of frames of {plan.ny} x {plan.nx} tiles')
     H, W = plan.frame
     shape = (M, NK // plan.K, H, W, 2)
-    if out is None:
-        out = torch.empty(shape, device=t.device, dtype=torch.float32)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != t.device or not out.is_contiguous():
-        raise ValueError(f'out must be a contiguous float32 tensor of shape {shape} on {t.device}')
+    out = _check_out(out, shape, torch.float32, t.device)
     if t.data_ptr() % 8 or out.data_ptr() % 8:
         raise ValueError('tile_blend reads and writes whole flow vectors: tiles and out must be 8-byte aligned')
     with torch.cuda.device(t.device):
@@ -429,13 +449,6 @@ def tile_blend_launch(t: torch.Tensor, plan: TilePlan, out=None) -> torch.Tensor
                                              _dev.ptr(yi), _dev.ptr(yi) + 4 * H, _dev.ptr(yw), plan.ys.max_taps,
                                              _dev.ptr(xi), _dev.ptr(xi) + 4 * W, _dev.ptr(xw), plan.xs.max_taps, _dev.stream_ptr()), 'tile_blend')
     return out
-
-
-def _check_out(out, shape, device):
-    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != torch.float32
-                            or out.device != device or not out.is_contiguous()):
-        raise ValueError(f'out must be a contiguous float32 tensor of shape {shape} on {device}')
-    return None if out is None else out.as_subclass(torch.Tensor)
 
 
 def tile_gather(x, height: int, width: int, overlap=64, out=None) -> torch.Tensor:
@@ -448,21 +461,12 @@ def tile_gather(x, height: int, width: int, overlap=64, out=None) -> torch.Tenso
     if height < 1 or width < 1:
         raise ValueError(f'tile size must be >= 1, got {height} x {width}')
     pair = _overlap_pair(overlap, height, width)
-    t = _on_device(x)
-    if t.dim() not in (3, 4):
-        raise ValueError(f'expected (H, W, C) or (N, H, W, C), got {tuple(t.shape)}')
-    if 0 in t.shape:
-        raise ValueError(f'empty input {tuple(t.shape)}')
-    if t.dtype not in (torch.float32, torch.uint8, torch.bool):
-        raise TypeError(f'tile_gather takes uint8, bool or float32, got {t.dtype}')
-    t4 = t if t.dim() == 4 else t[None]
+    t, t4 = _entry(x, 'tile_gather')
     if tuple(t4.shape[1:3]) == (height, width):
-        out = _check_out(out, tuple(t4.shape), t.device)
+        out = _check_out(out, tuple(t4.shape), torch.float32, t.device, alloc=False)
         t4 = t4 if t4.dtype == torch.float32 else t4.to(torch.float32)
         return _dev.wrap(t4 if out is None else out.copy_(t4))
-    with torch.cuda.device(t.device):
-        plan = TilePlan(t.device, t4.shape[1], t4.shape[2], height, width, pair)
-    out = _check_out(out, (t4.shape[0] * plan.K, height, width, t4.shape[3]), t.device)
+    plan = TilePlan(t.device, t4.shape[1], t4.shape[2], height, width, pair)
     return _dev.wrap(tile_gather_launch(t4, plan, out))
 
 
@@ -486,18 +490,65 @@ def tile_blend(tiles, H: int, W: int, overlap=64, out=None) -> torch.Tensor:
     t = _on_device(tiles)
     if t.dtype != torch.float32:
         raise TypeError(f'tile_blend takes float32, got {t.dtype}')
-    lead = tuple(t.shape[:-4])
     if (Ht, Wt) == (H, W):
-        out = _check_out(out, tuple(t.shape), t.device)
+        out = _check_out(out, tuple(t.shape), torch.float32, t.device, alloc=False)
         return _dev.wrap(t if out is None else out.copy_(t))
-    with torch.cuda.device(t.device):
-        plan = TilePlan(t.device, H, W, Ht, Wt, pair)
+    plan = TilePlan(t.device, H, W, Ht, Wt, pair)
     if t.shape[-4] % plan.K:
         raise ValueError(f'{t.shape[-4]} tiles are no whole number of frames of {plan.ny} x {plan.nx} tiles')
-    shape = lead + (t.shape[-4] // plan.K, H, W, 2)
-    out = _check_out(out, shape, t.device)
-    res = tile_blend_launch(t.reshape((-1,) + tuple(t.shape[-4:])), plan, None if out is None else out.view((-1,) + shape[-4:]))
-    return _dev.wrap(res.view(shape))
+    out = _check_out(out, tuple(t.shape[:-4]) + plan.result_size(t.shape[-4]) + (2,), torch.float32, t.device, alloc=False)
+    return _dev.wrap(plan.flow_back(t, out))
+
+
+# ---------------------------------------------------------------------------------------------------------------- routes
+class CropOrPadRoute:
+    """``fit='crop_or_pad'`` between ``(H, W)`` frames and a model of ``(Ht, Wt)``: the window copy both ways, no tables."""
+
+    def __init__(self, H, W, Ht, Wt):
+        self.frame, self.model = (int(H), int(W)), (int(Ht), int(Wt))
+
+    def frames_in(self, t):
+        return window_copy(t, *self.model, torch.float32)
+
+    def result_size(self, B):
+        return (B,) + self.frame
+
+    def flow_back(self, pred, into=None):
+        return _over_leading(lambda s, o: window_copy(s, *self.frame, out=o), pred, 3, into)
+
+    def tensors(self):
+        return []
+
+
+class ResizeRoute:
+    """``fit='resize'``: the plan of the frames' way in and the plan of the flow's way back (``u``, ``v`` scaled), both made here."""
+
+    def __init__(self, device, H, W, Ht, Wt, antialias):
+        self.fwd = ResizePlan(device, H, W, Ht, Wt, antialias)
+        self.back = ResizePlan(device, Ht, Wt, H, W, antialias, flow=True)
+
+    def frames_in(self, t):
+        return resize_launch(t, self.fwd)
+
+    def result_size(self, B):
+        return (B,) + self.back.target
+
+    def flow_back(self, pred, into=None):
+        return _over_leading(lambda s, o: resize_launch(s, self.back, o), pred, 3, into)
+
+    def tensors(self):
+        return self.back.tensors()          # (the way in runs on the stream the tables were made on)
+
+
+def fit_route(fit, device, H, W, Ht, Wt, antialias=False, overlap=None):
+    """The route object of one call (module docstring) between ``(H, W)`` frames on ``device`` and a model of ``(Ht, Wt)``.  Both
+    directions' tables are made -- the first time: uploaded -- here, on the CURRENT stream, so a ``flow_back`` launched on another
+    stream finds everything in place."""
+    if fit == 'resize':
+        return ResizeRoute(device, H, W, Ht, Wt, antialias)
+    if fit == 'tile':
+        return TilePlan(device, H, W, Ht, Wt, overlap)
+    return CropOrPadRoute(H, W, Ht, Wt)
 
 
 # ---------------------------------------------------------------------------------------------------------- colour coding
@@ -545,10 +596,7 @@ def flow_to_image_launch(t: torch.Tensor, height: int, width: int, clip: float =
     needs the images' own maxima then)."""
     N, H, W, _ = t.shape
     shape = (N, int(height), int(width), 3)
-    if out is None:
-        out = torch.empty(shape, device=t.device, dtype=torch.uint8)
-    elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != t.device or not out.is_contiguous():
-        raise ValueError(f'out must be a contiguous uint8 tensor of shape {shape} on {t.device}')
+    out = _check_out(out, shape, torch.uint8, t.device)
     partial = flow_rad_max_launch(t, height, width, clip) if not fixed_rad_max > 0.0 else None
     with torch.cuda.device(t.device):
         check(_dev.lib().raft_flow_to_image_u8(_dev.ptr(t), _dev.ptr(partial) if partial is not None else None, _dev.ptr(out), N, H, W,
@@ -573,11 +621,7 @@ def flow_to_image(flow, size=None, clip_flow=None, convert_to_bgr=False, rad_max
     is outside the contract.  ``tf_raft_amd.io.flow_to_image`` is the host version."""
     clip, fixed = _viz_args(clip_flow, rad_max)
     t, t4, h, w = _flow_4d(flow, size)
-    if out is not None:
-        shape = tuple(t.shape[:-3]) + (h, w, 3)
-        if tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != t.device or not out.is_contiguous():
-            raise ValueError(f'out must be a contiguous uint8 tensor of shape {shape} on {t.device}')
-        out = out.as_subclass(torch.Tensor)
+    out = _check_out(out, tuple(t.shape[:-3]) + (h, w, 3), torch.uint8, t.device, alloc=False)
     res = flow_to_image_launch(t4, h, w, clip, convert_to_bgr, fixed, None if out is None else (out if t.dim() == 4 else out[None]))
     return _dev.wrap(res if t.dim() == 4 else res[0])
 

@@ -108,6 +108,7 @@ class RAFT:
         # back with u scaled by W / Wt and v by H / Ht -- for frames much larger than the model's size.
         # 'tile' = overlapping tiles of the model's size at the frame's own resolution, run as one batch and cross-faded back
         # (`tile_overlap` pixels, an int or (overlap_y, overlap_x), at least shared by neighbouring tiles).
+        # Whichever it is, a call whose frames differ from the model's size builds ONE route object (_fit_frames) and asks it alone.
         self.fit, self.antialias = self._check_fit(fit, antialias, self.target_size)
         self.tile_overlap = self._check_tile_overlap(self.fit, tile_overlap, self.target_size)
         # three-stream schedule of the loop (RAFT only); RAFT_OVERLAP=0 forces the single-stream loop.  With several lanes
@@ -187,10 +188,10 @@ class RAFT:
         return self.target_size
 
     def _fit_frames(self, image1, image2):
-        """``target_size`` set: both frames as float32 device tensors of the model's size, and the frames' own (H, W) when that
-        differs (None: nothing was launched).  uint8 frames are cast and windowed (or resized) in one pass.  ``fit='resize'``: the
-        third entry of the returned window is the plan of the flow's way back, its tables already on the device.  ``fit='tile'``:
-        each frame becomes its K tiles (batch N * K), the third entry is the ``TilePlan``."""
+        """``target_size`` set: both frames as float32 device tensors of the model's size, and the call's route between the frames'
+        own size and the model's (``image_ops.fit_route``: crop-or-pad, resize or tiles behind one interface; None when the sizes
+        are equal and nothing was launched).  uint8 frames are cast on their way in, in the same pass; with ``fit='tile'`` each
+        frame becomes its K tiles (batch N * K).  The route's ``flow_back`` takes the predictions to the frames' own size."""
         image1, image2 = image_ops._on_device(image1), image_ops._on_device(image2)
         if image1.dim() != 4 or image1.shape[-1] != 3 or image1.shape != image2.shape or image1.dtype != image2.dtype or 0 in image1.shape:
             raise ValueError(f'images must both be (bs, H, W, 3) of one type, got {tuple(image1.shape)} {image1.dtype} / '
@@ -201,36 +202,10 @@ class RAFT:
             return _dev.to_device(image1), _dev.to_device(image2), None
         if image1.dtype not in (torch.uint8, torch.float32):
             image1, image2 = image1.to(torch.float32), image2.to(torch.float32)
-        if self.fit == 'resize':
-            # both directions' tables are made (the first time: uploaded) here, on the caller's stream: the launch that resizes
-            # the predictions, on the loop's stream of a pipelined call, finds everything in place
-            with torch.cuda.device(image1.device):
-                fwd = image_ops.ResizePlan(image1.device, H, W, th, tw, self.antialias)
-                back = image_ops.ResizePlan(image1.device, th, tw, H, W, self.antialias, flow=True)
-            return image_ops.resize_launch(image1, fwd), image_ops.resize_launch(image2, fwd), (H, W, back)
-        if self.fit == 'tile':
-            with torch.cuda.device(image1.device):
-                plan = image_ops.TilePlan(image1.device, H, W, th, tw, self.tile_overlap)      # (tables: as above)
-            return image_ops.tile_gather_launch(image1, plan), image_ops.tile_gather_launch(image2, plan), (H, W, plan)
-        return (image_ops.window_copy(image1, th, tw, torch.float32), image_ops.window_copy(image2, th, tw, torch.float32), (H, W))
-
-    @staticmethod
-    def _fit_flow(out, window, into=None):
-        """Predictions (..., Ht, Wt, 2) of the model's size -> the frames' own size, ONE launch over all leading axes, on the
-        current stream."""
-        if len(window) > 2 and isinstance(window[2], image_ops.TilePlan):
-            lead = tuple(out.shape[:-4])
-            res = image_ops.tile_blend_launch(out.view((-1,) + tuple(out.shape[-4:])), window[2],
-                                              out=None if into is None else into.view((-1,) + tuple(into.shape[-4:])))
-            return res.view(lead + tuple(res.shape[-4:]))
-        lead = tuple(out.shape[:-3])
-        if len(window) > 2:
-            res = image_ops.resize_launch(out.view((-1,) + tuple(out.shape[-3:])), window[2],
-                                          out=None if into is None else into.view((-1,) + tuple(into.shape[-3:])))
-            return res.view(lead + tuple(res.shape[-3:]))
-        res = image_ops.window_copy(out.view((-1,) + tuple(out.shape[-3:])), window[0], window[1],
-                                    out=None if into is None else into.view((-1,) + tuple(into.shape[-3:])))
-        return res.view(lead + tuple(res.shape[-3:]))
+        # both directions' tables are made (the first time: uploaded) here, on the caller's stream: the launch that takes the
+        # predictions back, on the loop's stream of a pipelined call, finds everything in place
+        route = image_ops.fit_route(self.fit, image1.device, H, W, th, tw, self.antialias, self.tile_overlap)
+        return route.frames_in(image1), route.frames_in(image2), route
 
     def _build(self, weights):
         self.fnet = BasicEncoder(output_dim=256, norm_type='instance', drop_rate=self.drop_rate,
@@ -415,9 +390,9 @@ class RAFT:
     def _forward(self, inputs, training=False, final_only=False, pipelined=None):
         self._sync_inference_weights()
         image1, image2 = inputs
-        window = None
+        route = None
         if self.target_size is not None and not training:
-            image1, image2, window = self._fit_frames(image1, image2)
+            image1, image2, route = self._fit_frames(image1, image2)
         image1 = _dev.to_device(image1)
         image2 = _dev.to_device(image2)
         if image1.dim() != 4 or image1.shape[-1] != 3 or image1.shape != image2.shape:
@@ -435,11 +410,11 @@ class RAFT:
             # with several lanes the loops are single-stream unless overlap was asked for: the lanes are each other's side branches
             plan = self._plan(n % lanes, self.overlap and not (lanes > 1 and not self._overlap_given), lanes)
             with _hinted(plan.pre_hint):
-                return self._forward_lane(image1, image2, final_only, n, lanes, plan, window)
+                return self._forward_lane(image1, image2, final_only, n, lanes, plan, route)
         self._join_pipeline()                       # (a training-mode or serial call after pipelined ones)
         plan = self._plan(0, self.overlap, 1 if training else self.loop_concurrency)
         with _hinted(plan.pre_hint):
-            return self._forward_serial(image1, image2, training, final_only, plan, window)
+            return self._forward_serial(image1, image2, training, final_only, plan, route)
 
     def _plan(self, lane, three_stream, hint):
         """The loop plan of one call.  ``hint`` is the number of loops that share the chip: the lanes of a pipelined call,
@@ -448,7 +423,7 @@ class RAFT:
         return _LoopPlan(lane, three_stream, hint if (hint > 1 and self._shape_hint == 'all') else None,
                          hint if self._shape_hint in ('loop', 'all') else 1)
 
-    def _forward_serial(self, image1, image2, training, final_only, plan, window=None):
+    def _forward_serial(self, image1, image2, training, final_only, plan, route=None):
         B, H, W, _ = image1.shape
         if self.overlap and not training:
             # the context encoder does not depend on the feature encoder or the volume: it runs on a side stream
@@ -477,8 +452,8 @@ class RAFT:
         iters = self.iters if training else self.iters_pred
         with _ffi.thread_concurrency(plan.loop_hint):
             out = self._run_loop(correlation, st, iters, self._alloc_out(iters, B, H, W, image1.device, final_only), final_only, plan)
-        if window is not None:
-            out = self._fit_flow(out, window)       # follows the loop on the current stream
+        if route is not None:
+            out = route.flow_back(out)              # to the frames' own size: follows the loop on the current stream
         return _dev.wrap(out) if final_only else [_dev.wrap(out[i]) for i in range(iters)]   # model.py:109
 
     @staticmethod
@@ -540,7 +515,7 @@ class RAFT:
     # raft_loop_ctx of its own), so up to D loops of consecutive calls are resident together and each fills the other's gaps and
     # idle CUs; the UpdateState ring has D + 1 slots (call n + D + 1's pre-loop waits for loop n).  Each call still runs exactly
     # the kernels of the serial schedule in the same order on its own buffers: results stay bit-identical per call.
-    def _forward_lane(self, image1, image2, final_only, n, lanes, plan, window=None):
+    def _forward_lane(self, image1, image2, final_only, n, lanes, plan, route=None):
         B, H, W, _ = image1.shape
         h, w = H // 8, W // 8
         dev = image1.device
@@ -556,20 +531,19 @@ class RAFT:
         correlation = CorrBlock(fmap1, fmap2, num_levels=self.corr_levels, radius=self.corr_radius,
                                 alternate=self.alternate_corr)                           # model.py:77
         out = self._alloc_out(self.iters_pred, B, H, W, dev, final_only)      # from the caller's stream's pool, like every other buffer
-        # (the tiles of fit='tile' are a batch of N * K: the result has the frames' batch)
-        frames = B // window[2].K if window is not None and len(window) > 2 and isinstance(window[2], image_ops.TilePlan) else B
-        res = out if window is None else self._alloc_out(self.iters_pred, frames, window[0], window[1], dev, final_only)
+        # (the result has the frames' batch and size: the tiles of fit='tile' are a batch of N * K)
+        res = out if route is None else self._alloc_out(self.iters_pred, *route.result_size(B), dev, final_only)
         ready = torch.cuda.Event()
         ready.record(cur)
         loop.wait_event(ready)
         with torch.cuda.stream(loop), _ffi.thread_concurrency(plan.loop_hint):
             self._run_loop(correlation, st, self.iters_pred, out, final_only, plan)
-            if window is not None:
+            if route is not None:
                 # back to the frames' own size on the LOOP's stream, in front of `done`: the caller's stream never waits for the loop
-                self._fit_flow(out, window, into=res)
+                route.flow_back(out, into=res)
             done = torch.cuda.Event()
             done.record(loop)
-        tables = window[2].tensors() if window is not None and len(window) > 2 else []
+        tables = route.tensors() if route is not None else []
         for t in (out, res, getattr(correlation, '_pyr', None), getattr(correlation, '_f2pyr', None), correlation.fmap1, correlation.fmap2, *tables):
             if isinstance(t, torch.Tensor) and t.is_cuda:
                 t.as_subclass(torch.Tensor).record_stream(loop)      # allocated under `cur`, in use on `loop`
