@@ -173,27 +173,10 @@ __global__ void __launch_bounds__(256) conv_halo_kernel(ConvArgs p) {
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // ---- epilogue resources (set up here so that the epilogue inputs can be prefetched)
-    const int w0 = (EPI == EPI_GRU_ZR) ? p.hid : p.nvalid;          // valid columns of o0
-    const int w1 = (EPI == EPI_GRU_ZR) ? p.nvalid - p.hid : 0;      // valid columns of o1
-    const __amdgpu_buffer_rsrc_t ro0 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.o0, 0, (int)((((long)M - 1) * p.ldo0 + w0) * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t ro1 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(w1 > 0 ? p.o1 : p.o0), 0, w1 > 0 ? (int)((((long)M - 1) * p.ldo1 + w1) * 4) : 0, 0x00020000);
-    const bool has_e0 = EPI == EPI_GRU_ZR || EPI == EPI_GRU_Q || EPI == EPI_RES, has_e1 = EPI == EPI_GRU_Q;
-    const int we = (EPI == EPI_GRU_ZR) ? p.hid : p.nvalid;
-    const __amdgpu_buffer_rsrc_t re0 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(has_e0 ? (const void *)p.e0 : (const void *)p.o0), 0,
-        has_e0 ? (int)((((long)M - 1) * p.lde0 + we) * 4) : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t re1 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(has_e1 ? (const void *)p.e1 : (const void *)p.o0), 0,
-        has_e1 ? (int)((((long)M - 1) * p.lde1 + we) * 4) : 0, 0x00020000);
-    auto bstore = [](float v, __amdgpu_buffer_rsrc_t r, unsigned off) {
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)off, 0, 0);
-    };
-    auto bload = [](__amdgpu_buffer_rsrc_t r, unsigned off) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0));
-    };
+    // ---- epilogue resources (set up here so that the epilogue inputs can be prefetched).  Descriptors, loads / stores, value
+    // formulas and the STATS tail are the shared ones of conv_epilogue.h; the channel predicates (nok, isz, which operand a
+    // channel touches) stay written out here, per register as `cond ? offset : RAFT_OOB` -- see EpiChannel there
+    const EpiBuffers eb = raft_epi_buffers<EPI>(p, M);
     // gate / residual inputs of the epilogue are fetched BEFORE the K loop (a layer that leaves one workgroup per CU
     // has nothing to hide their latency behind afterwards); masked pixels / channels read through RAFT_OOB -> 0
     float pe0[TH][TN][4], pe1[TH][TN][4];
@@ -212,8 +195,8 @@ __global__ void __launch_bounds__(256) conv_halo_kernel(ConvArgs p) {
                     const int yy = y0 + i, xx = x0 + 4 * G + r;
                     const bool mokr = (yy < p.H) & (xx < p.W);
                     const unsigned m = (unsigned)((b * p.H + yy) * p.W + xx);
-                    pe0[i][j][r] = bload(re0, (want0 & mokr) ? (m * p.lde0 + ne) * 4u : RAFT_OOB);
-                    if (EPI == EPI_GRU_Q) pe1[i][j][r] = bload(re1, (nok & mokr) ? (m * p.lde1 + n) * 4u : RAFT_OOB);
+                    pe0[i][j][r] = raft_buffer_load_f32(eb.e0, (want0 & mokr) ? (m * p.lde0 + ne) * 4u : RAFT_OOB);
+                    if (EPI == EPI_GRU_Q) pe1[i][j][r] = raft_buffer_load_f32(eb.e1, (nok & mokr) ? (m * p.lde1 + n) * 4u : RAFT_OOB);
                 }
             }
     }
@@ -222,8 +205,7 @@ __global__ void __launch_bounds__(256) conv_halo_kernel(ConvArgs p) {
     if (p.init) {
         // accumulators start from a precomputed partial sum (lane owns channel n; register r of
         // accumulator (i, j) is pixel (y0 + i, x0 + 4G + r)); issued behind the first tile's loads
-        const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)p.init, 0, (int)((((long)M - 1) * p.ldi + p.nvalid) * 4), 0x00020000);
+        const __amdgpu_buffer_rsrc_t ri = raft_epi_init_buffer(p, M);
 #pragma unroll
         for (int i = 0; i < TH; ++i)
 #pragma unroll
@@ -234,8 +216,7 @@ __global__ void __launch_bounds__(256) conv_halo_kernel(ConvArgs p) {
                     const int yy = y0 + i, xx = x0 + 4 * G + r;
                     const bool ok = (yy < p.H) & (xx < p.W) & (n < p.nvalid);
                     const unsigned m = (unsigned)((b * p.H + yy) * p.W + xx);
-                    acc[i][j][r] = __builtin_bit_cast(
-                        float, __builtin_amdgcn_raw_buffer_load_b32(ri, ok ? (int)((m * p.ldi + n) * 4u) : (int)RAFT_OOB, 0, 0));
+                    acc[i][j][r] = raft_buffer_load_f32(ri, ok ? (m * p.ldi + n) * 4u : RAFT_OOB);
                 }
             }
     }
@@ -337,57 +318,31 @@ __global__ void __launch_bounds__(256) conv_halo_kernel(ConvArgs p) {
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int n = n0 + (wn * TN + j) * 16 + LR;
-            const bool nok = n < p.nvalid;
+            const bool nok = n < p.nvalid, isz = n < p.hid;
+            const unsigned nh = (unsigned)((EPI == EPI_GRU_ZR && !isz) ? n - p.hid : n);
             const float bias = biasv[j];
-            if (EPI == EPI_LINEAR || EPI == EPI_RELU) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float v = acc[i][j][r] + bias;
-                    if (EPI == EPI_RELU) v = fmaxf(v, 0.f);
-                    v *= p.scale;
+            for (int r = 0; r < 4; ++r) {
+                if constexpr (EPI == EPI_GRU_ZR) {
+                    float z, rh;
+                    raft_epi_gate_zr(acc[i][j][r] + bias, pe0[i][j][r], &z, &rh);
+                    const bool ok = nok & mok[r];
+                    raft_buffer_store_f32(z, eb.o0, (ok & isz) ? (mrow[r] * p.ldo0 + nh) * 4u : RAFT_OOB);
+                    raft_buffer_store_f32(rh, eb.o1, (ok & !isz) ? (mrow[r] * p.ldo1 + nh) * 4u : RAFT_OOB);
+                } else {
+                    const float v = raft_epi_act<EPI>(acc[i][j][r] + bias, pe0[i][j][r], pe1[i][j][r], p.scale);
                     if (STATS && mok[r]) {
                         s1[j] += v;
                         s2[j] = fmaf(v, v, s2[j]);
                     }
-                    bstore(v, ro0, (nok & mok[r]) ? (mrow[r] * p.ldo0 + n) * 4u : RAFT_OOB);
-                }
-            } else if (EPI == EPI_RES) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    bstore(fmaxf(pe0[i][j][r] + fmaxf(acc[i][j][r] + bias, 0.f), 0.f), ro0,
-                           (nok & mok[r]) ? (mrow[r] * p.ldo0 + n) * 4u : RAFT_OOB);
-            } else if (EPI == EPI_GRU_ZR) {
-                const bool isz = n < p.hid;
-                const unsigned nh = (unsigned)(isz ? n : n - p.hid);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float g = raft_sigmoid(acc[i][j][r] + bias);
-                    const bool ok = nok & mok[r];
-                    bstore(g, ro0, (ok & isz) ? (mrow[r] * p.ldo0 + nh) * 4u : RAFT_OOB);
-                    bstore(g * pe0[i][j][r], ro1, (ok & !isz) ? (mrow[r] * p.ldo1 + nh) * 4u : RAFT_OOB);
-                }
-            } else {   // EPI_GRU_Q
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float q = raft_tanh(acc[i][j][r] + bias);
-                    bstore((1.0f - pe1[i][j][r]) * pe0[i][j][r] + pe1[i][j][r] * q, ro0,
-                           (nok & mok[r]) ? (mrow[r] * p.ldo0 + n) * 4u : RAFT_OOB);
+                    raft_buffer_store_f32(v, eb.o0, (nok & mok[r]) ? (mrow[r] * p.ldo0 + nh) * 4u : RAFT_OOB);
                 }
             }
         }
     }
-    if (STATS) {
-        // per-tile moments of the raw output: lanes LR, LR+16, LR+32, LR+48 hold the same channel
+    if (STATS) {   // per-tile moments of the raw output
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            float a = s1[j], q = s2[j];
-            a += __shfl_xor(a, 16, 64);
-            q += __shfl_xor(q, 16, 64);
-            a += __shfl_xor(a, 32, 64);
-            q += __shfl_xor(q, 32, 64);
-            const int n = n0 + (wn * TN + j) * 16 + LR;
-            if (G == 0) *(float2 *)(p.stats + ((long)mt * p.npad + n) * 2) = make_float2(a, q);
-        }
+        for (int j = 0; j < TN; ++j) raft_epi_stats_store(p, s1[j], s2[j], G, mt, n0 + (wn * TN + j) * 16 + LR);
     }
 }
 
@@ -403,24 +358,36 @@ static inline bool raft_conv_deep(const ConvArgs &, int, int tn, int) {
     return tn == 1;
 }
 
-template <int KH, int KW, int EPI>
+template <int V>
+using IC = std::integral_constant<int, V>;
+
+// The tile switch of every direct-kernel launcher (update blocks here, encoders in encoder.hip): th x 16 pixels, 64 tn channels.
+// TH4 = false leaves the 4-row tiles out (the encoders never pick them: nothing is instantiated for them).
+template <int KH, int KW, int EPI, int STRIDE = 1, int PRE = 0, int STATS = 0, int STEM = 0, bool TH4 = true>
 static int raft_launch_conv_halo_tile(const ConvArgs &a, int th, int tn, hipStream_t s) {
     const int tiles = a.B * ((a.H + th - 1) / th) * ((a.W + 15) / 16);
     const int grid = tiles * (a.npad / (64 * tn));
-    const int key = th * 10 + tn + (raft_conv_deep(a, th, tn, grid) ? 100 : 0);
-    switch (key) {
-        case 141: conv_halo_kernel<KH, KW, 4, 1, EPI, 1, 0, 0, 0, 1><<<grid, 256, 0, s>>>(a); break;
-        case 171: conv_halo_kernel<KH, KW, 7, 1, EPI, 1, 0, 0, 0, 1><<<grid, 256, 0, s>>>(a); break;
-        case 181: conv_halo_kernel<KH, KW, 8, 1, EPI, 1, 0, 0, 0, 1><<<grid, 256, 0, s>>>(a); break;
-        case 41: conv_halo_kernel<KH, KW, 4, 1, EPI><<<grid, 256, 0, s>>>(a); break;
-        case 42: conv_halo_kernel<KH, KW, 4, 2, EPI><<<grid, 256, 0, s>>>(a); break;
-        case 71: conv_halo_kernel<KH, KW, 7, 1, EPI><<<grid, 256, 0, s>>>(a); break;
-        case 72: conv_halo_kernel<KH, KW, 7, 2, EPI><<<grid, 256, 0, s>>>(a); break;
-        case 81: conv_halo_kernel<KH, KW, 8, 1, EPI><<<grid, 256, 0, s>>>(a); break;
-        case 82: conv_halo_kernel<KH, KW, 8, 2, EPI><<<grid, 256, 0, s>>>(a); break;
+    auto run = [&](auto th_c, auto tn_c, auto deep_c) -> int {
+        constexpr int TH = decltype(th_c)::value, TN = decltype(tn_c)::value, DEEP = decltype(deep_c)::value;
+        if constexpr (TH == 4 && !TH4) {
+            return RAFT_E_UNSUPPORTED;
+        } else {
+            conv_halo_kernel<KH, KW, TH, TN, EPI, STRIDE, PRE, STATS, STEM, DEEP><<<grid, 256, 0, s>>>(a);
+            return raft_launch_status();
+        }
+    };
+    switch (th * 10 + tn + (raft_conv_deep(a, th, tn, grid) ? 100 : 0)) {
+        case 141: return run(IC<4>(), IC<1>(), IC<1>());
+        case 171: return run(IC<7>(), IC<1>(), IC<1>());
+        case 181: return run(IC<8>(), IC<1>(), IC<1>());
+        case 41: return run(IC<4>(), IC<1>(), IC<0>());
+        case 42: return run(IC<4>(), IC<2>(), IC<0>());
+        case 71: return run(IC<7>(), IC<1>(), IC<0>());
+        case 72: return run(IC<7>(), IC<2>(), IC<0>());
+        case 81: return run(IC<8>(), IC<1>(), IC<0>());
+        case 82: return run(IC<8>(), IC<2>(), IC<0>());
         default: return RAFT_E_UNSUPPORTED;
     }
-    return raft_launch_status();
 }
 
 template <int KH, int KW>

@@ -270,37 +270,17 @@ __global__ void __launch_bounds__(256 * KS, KS == 2 ? 1 : ((TNW == 1 && !SB && !
     // ---- epilogue: lane owns channel n; register r of an accumulator is tile m = 4G + r of the row block
     // GRU gates (the 3x3 ConvGRU of SmallRAFT, reference update.py:17-35) as in conv_halo.h: GRU_ZR writes z to o0 and
     // r * h to o1 (h = e0), GRU_Q writes (1 - z) h + z tanh(.) (h = e0, z = e1)
-    constexpr bool GRU = EPI == EPI_GRU_ZR || EPI == EPI_GRU_Q, HAS_E0 = EPI == EPI_RES || GRU;
-    const int w0 = (EPI == EPI_GRU_ZR) ? p.hid : p.nvalid;          // valid columns of o0
-    const int w1 = (EPI == EPI_GRU_ZR) ? p.nvalid - p.hid : 0;      // valid columns of o1
-    const int we = (EPI == EPI_GRU_ZR) ? p.hid : p.nvalid;
-    const __amdgpu_buffer_rsrc_t ro0 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.o0, 0, (int)((((long)M - 1) * p.ldo0 + w0) * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t ro1 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(w1 > 0 ? p.o1 : p.o0), 0, w1 > 0 ? (int)((((long)M - 1) * p.ldo1 + w1) * 4) : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t re0 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(HAS_E0 ? (const void *)p.e0 : (const void *)p.o0), 0,
-        HAS_E0 ? (int)((((long)M - 1) * p.lde0 + we) * 4) : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t re1 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(EPI == EPI_GRU_Q ? (const void *)p.e1 : (const void *)p.o0), 0,
-        EPI == EPI_GRU_Q ? (int)((((long)M - 1) * p.lde1 + we) * 4) : 0, 0x00020000);
+    constexpr bool HAS_E0 = EPI == EPI_RES || EPI == EPI_GRU_ZR || EPI == EPI_GRU_Q;
+    const EpiBuffers eb = raft_epi_buffers<EPI>(p, M);
     // Addresses: one lane base per tensor (pixel (yy, x0 + 8G), channel n; RAFT_OOB when the lane's channel takes no
     // part) + a wave-uniform element offset in the instruction's scalar operand; elements outside the image (only in
     // tiles cut by the border) get the out-of-range bit.
-    auto bstore = [](float v, __amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)voff, soff, 0);
-    };
-    auto bload = [](__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, soff, 0));
-    };
     const bool interior = (y0 + TH <= p.H) & (x0 + TW <= p.W);   // wave-uniform
 #pragma unroll
     for (int j = 0; j < TNW; ++j) {
         const int n = n0 + (cg * TNW + j) * 16 + LR;
-        const bool nok = n < p.nvalid;
+        const EpiChannel<EPI> ch(p, n);
         const float bias = p.bias[n];                         // bias has npad entries
-        const bool isz = n < p.hid;
-        const unsigned nh = (unsigned)((EPI == EPI_GRU_ZR && !isz) ? n - p.hid : n);
         float s1 = 0.f, s2 = 0.f;
         // A^T over the tap rows: T[i][tx], i = 0: M0 + M1 + M2, i = 1: M1 - M2 - M3
         f32x4 T[2][4];
@@ -320,18 +300,15 @@ __global__ void __launch_bounds__(256 * KS, KS == 2 ? 1 : ((TNW == 1 && !SB && !
 #pragma unroll
                 for (int jx = 0; jx < 2; ++jx)
                     dead[r][jx] = (interior | ((yy < p.H) & (xb + 2 * r + jx < p.W))) ? 0u : RAFT_OOB;
-            const unsigned bo0 = (EPI == EPI_GRU_ZR ? (nok & isz) : nok) ? (pix0 * p.ldo0 + nh) * 4u : RAFT_OOB;
-            const unsigned bo1 = (EPI == EPI_GRU_ZR && nok && !isz) ? (pix0 * p.ldo1 + nh) * 4u : RAFT_OOB;
-            const unsigned be0 = (HAS_E0 && (EPI == EPI_GRU_ZR ? (nok & !isz) : nok)) ? (pix0 * p.lde0 + nh) * 4u : RAFT_OOB;
-            const unsigned be1 = (EPI == EPI_GRU_Q && nok) ? (pix0 * p.lde1 + n) * 4u : RAFT_OOB;
-            float xv[4][2], zv[4][2];
+            const EpiBases ba = raft_epi_bases<EPI>(p, ch, pix0);
+            float xv[4][2] = {}, zv[4][2] = {};
             if (HAS_E0) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
 #pragma unroll
                     for (int jx = 0; jx < 2; ++jx) {
-                        xv[r][jx] = bload(re0, be0 | dead[r][jx], (2 * r + jx) * p.lde0 * 4);
-                        if (EPI == EPI_GRU_Q) zv[r][jx] = bload(re1, be1 | dead[r][jx], (2 * r + jx) * p.lde1 * 4);
+                        xv[r][jx] = raft_buffer_load_f32(eb.e0, ba.e0 | dead[r][jx], (2 * r + jx) * p.lde0 * 4);
+                        if (EPI == EPI_GRU_Q) zv[r][jx] = raft_buffer_load_f32(eb.e1, ba.e1 | dead[r][jx], (2 * r + jx) * p.lde1 * 4);
                     }
             }
 #pragma unroll
@@ -340,36 +317,24 @@ __global__ void __launch_bounds__(256 * KS, KS == 2 ? 1 : ((TNW == 1 && !SB && !
                 for (int jx = 0; jx < 2; ++jx) {
                     float v = (jx ? yb[r] : ya[r]) + bias;
                     const int so0 = (2 * r + jx) * p.ldo0 * 4;
-                    if (EPI == EPI_GRU_ZR) {
-                        const float g = raft_sigmoid(v);
-                        bstore(g, ro0, bo0 | dead[r][jx], so0);
-                        bstore(g * xv[r][jx], ro1, bo1 | dead[r][jx], (2 * r + jx) * p.ldo1 * 4);
-                        continue;
-                    }
-                    if (EPI == EPI_GRU_Q) {
-                        v = (1.0f - zv[r][jx]) * xv[r][jx] + zv[r][jx] * raft_tanh(v);
-                    } else if (EPI == EPI_RES) {
-                        v = fmaxf(xv[r][jx] + fmaxf(v, 0.f), 0.f);
+                    if constexpr (EPI == EPI_GRU_ZR) {
+                        float z, rh;
+                        raft_epi_gate_zr(v, xv[r][jx], &z, &rh);
+                        raft_buffer_store_f32(z, eb.o0, ba.o0 | dead[r][jx], so0);
+                        raft_buffer_store_f32(rh, eb.o1, ba.o1 | dead[r][jx], (2 * r + jx) * p.ldo1 * 4);
                     } else {
-                        if (EPI == EPI_RELU) v = fmaxf(v, 0.f);
-                        v *= p.scale;
+                        v = raft_epi_act<EPI>(v, xv[r][jx], zv[r][jx], p.scale);
+                        if (STATS && dead[r][jx] == 0u) {
+                            s1 += v;
+                            s2 = fmaf(v, v, s2);
+                        }
+                        if ((RAFT_WINO_ABL & 8) && v != 12345.678f) continue;
+                        raft_buffer_store_f32(v, eb.o0, ba.o0 | dead[r][jx], so0);
                     }
-                    if (STATS && dead[r][jx] == 0u) {
-                        s1 += v;
-                        s2 = fmaf(v, v, s2);
-                    }
-                    if ((RAFT_WINO_ABL & 8) && v != 12345.678f) continue;
-                    bstore(v, ro0, bo0 | dead[r][jx], so0);
                 }
             }
         }
-        if (STATS) {   // lanes LR, LR+16, LR+32, LR+48 hold the same channel
-            s1 += __shfl_xor(s1, 16, 64);
-            s2 += __shfl_xor(s2, 16, 64);
-            s1 += __shfl_xor(s1, 32, 64);
-            s2 += __shfl_xor(s2, 32, 64);
-            if (G == 0) *(float2 *)(p.stats + ((long)(2 * mt + rb) * p.npad + n) * 2) = make_float2(s1, s2);
-        }
+        if (STATS) raft_epi_stats_store(p, s1, s2, G, 2 * mt + rb, n);   // entry = (pixel tile, row block)
     }
 }
 

@@ -60,32 +60,11 @@ template <int AXIS, int TNW, int EPI, int TM, int MO>
 __device__ __forceinline__ void wino1d_epilogue(const ConvArgs &p, f32x4 (&acc)[TM][MO + 4][TNW], int rbp, int cg, int G, int LR,
                                                 int b, int y0, int x0, int n0, int M) {
     constexpr int TILE_H = AXIS == 0 ? 2 * TM : 2 * MO * TM, TILE_W = AXIS == 0 ? 16 * MO : 16;
-    const int w0 = (EPI == EPI_GRU_ZR) ? p.hid : p.nvalid;          // valid columns of o0
-    const int w1 = (EPI == EPI_GRU_ZR) ? p.nvalid - p.hid : 0;      // valid columns of o1
-    const __amdgpu_buffer_rsrc_t ro0 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.o0, 0, (int)((((long)M - 1) * p.ldo0 + w0) * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t ro1 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(w1 > 0 ? p.o1 : p.o0), 0, w1 > 0 ? (int)((((long)M - 1) * p.ldo1 + w1) * 4) : 0, 0x00020000);
-    const bool has_e0 = EPI == EPI_GRU_ZR || EPI == EPI_GRU_Q, has_e1 = EPI == EPI_GRU_Q;
-    const int we = (EPI == EPI_GRU_ZR) ? p.hid : p.nvalid;
-    const __amdgpu_buffer_rsrc_t re0 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(has_e0 ? (const void *)p.e0 : (const void *)p.o0), 0,
-        has_e0 ? (int)((((long)M - 1) * p.lde0 + we) * 4) : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t re1 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(has_e1 ? (const void *)p.e1 : (const void *)p.o0), 0,
-        has_e1 ? (int)((((long)M - 1) * p.lde1 + we) * 4) : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(p.init ? (const void *)p.init : (const void *)p.o0), 0,
-        p.init ? (int)((((long)M - 1) * p.ldi + p.nvalid) * 4) : 0, 0x00020000);
+    const EpiBuffers eb = raft_epi_buffers<EPI>(p, M);
+    const __amdgpu_buffer_rsrc_t ri = raft_epi_init_buffer(p, M);
     // Addresses: one lane base per tensor (first pixel of the lane's groups, channel n; RAFT_OOB when the lane's channel
     // takes no part) + a wave-uniform element offset in the instruction's scalar operand; elements outside the image
     // (only in tiles cut by the border) get the out-of-range bit.  A null `init` has a zero-sized descriptor: loads give 0.
-    auto bstore = [](float v, __amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)voff, soff, 0);
-    };
-    auto bload = [](__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, soff, 0));
-    };
     const bool interior = (y0 + TILE_H <= p.H) & (x0 + TILE_W <= p.W);   // wave-uniform
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -107,10 +86,8 @@ __device__ __forceinline__ void wino1d_epilogue(const ConvArgs &p, f32x4 (&acc)[
 #pragma unroll
         for (int j = 0; j < TNW; ++j) {
             const int n = n0 + (cg * TNW + j) * 16 + LR;
-            const bool nok = n < p.nvalid;
+            const EpiChannel<EPI> ch(p, n);
             const float bias = p.bias[n];                         // bias has npad entries
-            const bool isz = n < p.hid;
-            const unsigned nh = (unsigned)((EPI == EPI_GRU_ZR && !isz) ? n - p.hid : n);
             f32x4 y[MO];                                          // A^T m
             if constexpr (MO == 2) {
                 y[0] = ((acc[i][0][j] + acc[i][1][j]) + (acc[i][2][j] + acc[i][3][j])) + acc[i][4][j];
@@ -124,12 +101,8 @@ __device__ __forceinline__ void wino1d_epilogue(const ConvArgs &p, f32x4 (&acc)[
                 y[2] = (s12 + 0.25f * s34) + 4.0f * s56;
                 y[3] = ((d12 + 0.125f * d34) + 8.0f * d56) + acc[i][7][j];
             }
-            const unsigned bi = nok ? (pix0 * p.ldi + n) * 4u : RAFT_OOB;                        // init
-            const unsigned bo0 = (EPI == EPI_GRU_ZR ? (nok & isz) : nok) ? (pix0 * p.ldo0 + nh) * 4u : RAFT_OOB;
-            const unsigned bo1 = (EPI == EPI_GRU_ZR && nok && !isz) ? (pix0 * p.ldo1 + nh) * 4u : RAFT_OOB;
-            const unsigned be0 = (EPI == EPI_GRU_ZR ? (nok & !isz) : (EPI == EPI_GRU_Q && nok)) ? (pix0 * p.lde0 + nh) * 4u : RAFT_OOB;
-            const unsigned be1 = (EPI == EPI_GRU_Q && nok) ? (pix0 * p.lde1 + n) * 4u : RAFT_OOB;
-            float iv[4][MO], hv[4][MO], zv[4][MO];
+            const EpiBases ba = raft_epi_bases<EPI>(p, ch, pix0);
+            float iv[4][MO] = {}, hv[4][MO] = {}, zv[4][MO] = {};
 #pragma unroll
             for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -138,9 +111,9 @@ __device__ __forceinline__ void wino1d_epilogue(const ConvArgs &p, f32x4 (&acc)[
                         iv[r][jx] = hv[r][jx] = zv[r][jx] = 0.5f;
                         continue;
                     }
-                    iv[r][jx] = bload(ri, bi | dead[r][jx], es(r, jx) * p.ldi * 4);
-                    if (EPI == EPI_GRU_ZR || EPI == EPI_GRU_Q) hv[r][jx] = bload(re0, be0 | dead[r][jx], es(r, jx) * p.lde0 * 4);
-                    if (EPI == EPI_GRU_Q) zv[r][jx] = bload(re1, be1 | dead[r][jx], es(r, jx) * p.lde1 * 4);
+                    iv[r][jx] = raft_buffer_load_f32(ri, ba.init | dead[r][jx], es(r, jx) * p.ldi * 4);
+                    if (EPI == EPI_GRU_ZR || EPI == EPI_GRU_Q) hv[r][jx] = raft_buffer_load_f32(eb.e0, ba.e0 | dead[r][jx], es(r, jx) * p.lde0 * 4);
+                    if (EPI == EPI_GRU_Q) zv[r][jx] = raft_buffer_load_f32(eb.e1, ba.e1 | dead[r][jx], es(r, jx) * p.lde1 * 4);
                 }
 #pragma unroll
             for (int r = 0; r < 4; ++r)
@@ -149,15 +122,13 @@ __device__ __forceinline__ void wino1d_epilogue(const ConvArgs &p, f32x4 (&acc)[
                     const float v = (y[jx][r] + iv[r][jx]) + bias;
                     const int so0 = es(r, jx) * p.ldo0 * 4;
                     if ((RAFT_WINO1D_ABL & 8) && v != 12345.678f) continue;
-                    if (EPI == EPI_LINEAR || EPI == EPI_RELU) {
-                        bstore((EPI == EPI_RELU ? fmaxf(v, 0.f) : v) * p.scale, ro0, bo0 | dead[r][jx], so0);
-                    } else if (EPI == EPI_GRU_ZR) {
-                        const float g = raft_sigmoid(v);
-                        bstore(g, ro0, bo0 | dead[r][jx], so0);
-                        bstore(g * hv[r][jx], ro1, bo1 | dead[r][jx], es(r, jx) * p.ldo1 * 4);
+                    if constexpr (EPI == EPI_GRU_ZR) {
+                        float z, rh;
+                        raft_epi_gate_zr(v, hv[r][jx], &z, &rh);
+                        raft_buffer_store_f32(z, eb.o0, ba.o0 | dead[r][jx], so0);
+                        raft_buffer_store_f32(rh, eb.o1, ba.o1 | dead[r][jx], es(r, jx) * p.ldo1 * 4);
                     } else {
-                        const float q = raft_tanh(v);
-                        bstore((1.0f - zv[r][jx]) * hv[r][jx] + zv[r][jx] * q, ro0, bo0 | dead[r][jx], so0);
+                        raft_buffer_store_f32(raft_epi_act<EPI>(v, hv[r][jx], zv[r][jx], p.scale), eb.o0, ba.o0 | dead[r][jx], so0);
                     }
                 }
         }

@@ -433,17 +433,7 @@ __global__ void __launch_bounds__(256, 1) conv_wino4_kernel(ConvArgs p) {
 
     // ---- epilogue: lane owns channel n; register r of an accumulator is tile 4G + r of the row block
     constexpr bool HAS_E0 = EPI == EPI_RES;
-    const __amdgpu_buffer_rsrc_t ro0 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.o0, 0, (int)((((long)M - 1) * p.ldo0 + p.nvalid) * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t re0 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(HAS_E0 ? (const void *)p.e0 : (const void *)p.o0), 0,
-        HAS_E0 ? (int)((((long)M - 1) * p.lde0 + p.nvalid) * 4) : 0, 0x00020000);
-    auto bstore = [](float v, __amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)voff, soff, 0);
-    };
-    auto bload = [](__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, soff, 0));
-    };
+    const EpiBuffers eb = raft_epi_buffers<EPI>(p, M);   // o0 and (EPI_RES) e0: this family has no gate epilogues
     const bool interior = (y0 + TH <= p.H) & (x0 + TW <= p.W);   // wave-uniform
     // the epilogue's lane indices are re-derived from an opaque copy of the thread id: otherwise hipcc evaluates the
     // epilogue's addresses before the K loop and carries them through it in registers the loop does not have (spills)
@@ -487,23 +477,17 @@ __global__ void __launch_bounds__(256, 1) conv_wino4_kernel(ConvArgs p) {
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr) {
             const int r = 2 * rh + rr;
-            float xv[4];
+            float xv[4] = {};
             if (HAS_E0) {
 #pragma unroll
                 for (int jx = 0; jx < 4; ++jx) {
                     const unsigned dead = (interior | (rowok[i] & (xb + 4 * r + jx < p.W))) ? 0u : RAFT_OOB;
-                    xv[jx] = bload(re0, ve | dead, (4 * r + jx) * p.lde0 * 4);
+                    xv[jx] = raft_buffer_load_f32(eb.e0, ve | dead, (4 * r + jx) * p.lde0 * 4);
                 }
             }
 #pragma unroll
             for (int jx = 0; jx < 4; ++jx) {
-                float v = Y[jx][rr] + bias;
-                if (EPI == EPI_RES) {
-                    v = fmaxf(xv[jx] + fmaxf(v, 0.f), 0.f);
-                } else {
-                    if (EPI == EPI_RELU) v = fmaxf(v, 0.f);
-                    v *= p.scale;
-                }
+                const float v = raft_epi_act<EPI>(Y[jx][rr] + bias, xv[jx], 0.f, p.scale);
                 if ((RAFT_WINO4_ABL & 8) && v != 12345.678f) continue;
                 const unsigned dead = (interior | (rowok[i] & (xb + 4 * r + jx < p.W))) ? 0u : RAFT_OOB;
                 if constexpr (STATS) {
@@ -515,7 +499,7 @@ __global__ void __launch_bounds__(256, 1) conv_wino4_kernel(ConvArgs p) {
                     st1[j] += vs;
                     st2[j] = fmaf(vs, vs, st2[j]);
                 }
-                bstore(v, ro0, vo | dead, (4 * r + jx) * p.ldo0 * 4);
+                raft_buffer_store_f32(v, eb.o0, vo | dead, (4 * r + jx) * p.ldo0 * 4);
             }
         }
     };

@@ -114,21 +114,10 @@ __global__ void __launch_bounds__(256) res_merge_kernel(const f32x4 *__restrict_
 // ---------------------------------------------------------------- convolution dispatch
 enum EncKind { ENC_3x3_S1, ENC_3x3_S2, ENC_1x1_S2, ENC_1x1_S1, ENC_STEM };
 
+// the direct kernel's tile switch (conv_halo.h) without the 4-row tiles, which enc_pick() never chooses
 template <int KH, int KW, int EPI, int STRIDE, int PRE, int STATS, int STEM>
 int launch_tile(const ConvArgs &a, int th, int tn, hipStream_t s) {
-    const int tiles = a.B * ((a.H + th - 1) / th) * ((a.W + 15) / 16);
-    const int grid = tiles * (a.npad / (64 * tn));
-    const int key = th * 10 + tn + (raft_conv_deep(a, th, tn, grid) ? 100 : 0);
-    switch (key) {
-        case 171: conv_halo_kernel<KH, KW, 7, 1, EPI, STRIDE, PRE, STATS, STEM, 1><<<grid, 256, 0, s>>>(a); break;
-        case 181: conv_halo_kernel<KH, KW, 8, 1, EPI, STRIDE, PRE, STATS, STEM, 1><<<grid, 256, 0, s>>>(a); break;
-        case 71: conv_halo_kernel<KH, KW, 7, 1, EPI, STRIDE, PRE, STATS, STEM><<<grid, 256, 0, s>>>(a); break;
-        case 72: conv_halo_kernel<KH, KW, 7, 2, EPI, STRIDE, PRE, STATS, STEM><<<grid, 256, 0, s>>>(a); break;
-        case 81: conv_halo_kernel<KH, KW, 8, 1, EPI, STRIDE, PRE, STATS, STEM><<<grid, 256, 0, s>>>(a); break;
-        case 82: conv_halo_kernel<KH, KW, 8, 2, EPI, STRIDE, PRE, STATS, STEM><<<grid, 256, 0, s>>>(a); break;
-        default: return RAFT_E_UNSUPPORTED;
-    }
-    return raft_launch_status();
+    return raft_launch_conv_halo_tile<KH, KW, EPI, STRIDE, PRE, STATS, STEM, false>(a, th, tn, s);
 }
 
 // epi: EPI_LINEAR (+stats when a.stats), EPI_RELU, EPI_RES; pre = a.pre_scale != nullptr
