@@ -273,6 +273,31 @@ int raft_flow_rad_max_f32(const float *flow, float *partial, int N, int Hs, int 
 int raft_flow_to_image_u8(const float *flow, const float *partial, uint8_t *image, int N, int Hs, int Ws, int Ht, int Wt,
                           float clip, int bgr, float fixed_rad_max, void *stream);
 
+/* Where a flow can be trusted (no reference counterpart): the backward warp of an image by a flow and the
+ * forward-backward consistency test of two flows.  Flows are (N, H, W, 2) floats, [..., 0] = u along x, [..., 1] = v along y.
+ * For the pixel at integer (x, y) with vector (u, v) the sample position is sx = float(x) + u, sy = float(y) + v, ONE float32
+ * addition each; the pixel is IN FRAME iff 0 <= sx <= W - 1 and 0 <= sy <= H - 1 (a NaN fails the comparison).  A map g is
+ * sampled there bilinearly: x0 = floor(sx), x1 = min(x0 + 1, W - 1), a = sx - x0, likewise y0, y1, b, and
+ *     (1 - b) * ((1 - a) * g[y0, x0] + a * g[y0, x1]) + b * ((1 - a) * g[y1, x0] + a * g[y1, x1])
+ * every operation rounded on its own.  This is ordinary bilinear interpolation, not the reference's bilinear_sampler
+ * (corr.py:28-69: its ceil / floor weights are both 0 at an integer coordinate).
+ *   raft_warp_f32 / raft_warp_u8_f32: dst[n, y, x, c] = src[n, :, :, c] sampled at the pixel's sample position, 0.0f in every
+ *     channel of a pixel out of frame; src (N, H, W, C) float or uint8 (cast in the same pass), C >= 1, dst (N, H, W, C) float.
+ *     inside: NULL, or uint8 (N, H, W), 1 where in frame.  warp(image2, flow_forward) reconstructs frame 1 from frame 2.
+ *   raft_flow_consistency_f32: with s = flow_b sampled at the pixel's sample position under flow_a (both components),
+ *         occluded_a = !(in frame && |flow_a + s|^2 <= alpha * (|flow_a|^2 + |s|^2) + beta)
+ *     (Meister et al. 2018, UnFlow: alpha 0.01, beta 0.5), so a non-finite vector marks its pixel.  occluded_b: NULL, or the
+ *     same test with the roles of the flows swapped, produced by the SAME launch as a second grid slice.  Masks are uint8
+ *     (N, H, W), 1 = occluded.
+ * One launch on `stream` each, no atomics, no memset, every output element written exactly once; tap indices are clamped into
+ * the frame whatever a flow holds.  RAFT_E_NULL for a NULL required pointer; RAFT_E_SHAPE for a non-positive size, a negative
+ * or non-finite alpha or beta, W * C beyond an int, or N * H * W * max(C, 2) of 2^31 elements or more; RAFT_E_ALIGN for a flow
+ * that is not 8-byte aligned (flows are read as float2).  All checks precede the launch. */
+int raft_warp_f32(const float *src, const float *flow, float *dst, uint8_t *inside, int N, int H, int W, int C, void *stream);
+int raft_warp_u8_f32(const uint8_t *src, const float *flow, float *dst, uint8_t *inside, int N, int H, int W, int C, void *stream);
+int raft_flow_consistency_f32(const float *flow_a, const float *flow_b, uint8_t *occluded_a, uint8_t *occluded_b, int N, int H, int W,
+                              float alpha, float beta, void *stream);
+
 /* ------------------------------------------------------------------ training augmentation */
 
 /* FlowAugmentor (reference tf_raft/datasets/augmentor.py:9-129, used at dataset.py:87-91) composed into one gather (the sparse

@@ -108,6 +108,9 @@ _SIGNATURES = {
     'raft_flow_to_image_workspace_floats': (C.c_int64, [_I]),
     'raft_flow_rad_max_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, C.c_float, _P]),
     'raft_flow_to_image_u8': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.c_float, _I, C.c_float, _P]),
+    'raft_warp_f32': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    'raft_warp_u8_f32': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    'raft_flow_consistency_f32': (_I, [_P, _P, _P, _P, _I, _I, _I, C.c_float, C.c_float, _P]),
     'raft_augment_params_bytes': (_I, []),
     'raft_augment_sums_u8': (_I, [_P, _P, _P, _I, _I, _I, _P]),
     'raft_augment_gather_u8': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),

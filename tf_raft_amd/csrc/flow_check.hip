@@ -1,0 +1,199 @@
+// Where a predicted vector can be trusted (no reference counterpart): the backward warp of an image by a
+// flow, and the forward-backward consistency test of two flows, one launch each.
+//
+//   raft_warp_f32 / raft_warp_u8_f32   dst[n, y, x, c] = src[n, :, :, c] sampled at (x + u, y + v), zero outside the frame
+//   raft_flow_consistency_f32          occluded = !(in frame && |f + s|^2 <= alpha * (|f|^2 + |s|^2) + beta), s the OTHER flow
+//                                      sampled at (x + u, y + v); both directions in one launch (Meister et al. 2018, UnFlow)
+//
+// Both share one definition of the sample.  For the pixel at integer (x, y) with vector (u, v): sx = float(x) + u and
+// sy = float(y) + v, ONE float32 addition each; the pixel is in frame iff 0 <= sx <= W - 1 and 0 <= sy <= H - 1 (a NaN fails);
+// x0 = floor(sx), x1 = min(x0 + 1, W - 1), a = sx - x0 (exact), likewise y0, y1, b, and the value is
+//     (1 - b) * ((1 - a) * g[y0, x0] + a * g[y0, x1]) + b * ((1 - a) * g[y1, x0] + a * g[y1, x1])
+// with every product and sum rounded on its own (contraction is switched off for this file).  This is ordinary bilinear
+// interpolation, NOT the reference's bilinear_sampler (corr.py:28-69), whose ceil / floor weights vanish at integer coordinates.
+//
+// Both kernels are gathers bound by memory with no reuse worth staging: one thread per pixel, pixels of an image numbered along
+// its rows, so a wave reads 64 consecutive flow vectors as one 512-byte run of float2 and writes its outputs as runs; the four
+// taps of neighbouring lanes under a smooth flow are neighbours too.  blockIdx.y walks the images (and, for the consistency
+// test, the two directions: slice n + N * d is image n of direction d).  No atomics, no memset, every output element is written
+// exactly once.  Tap indices are clamped into the frame whatever the flow holds.  Measured at (4, 1080, 1920) (docs/NOTEBOOK.md
+// section 21): a thread that owns four consecutive pixels and stores its mask bytes as one word is SLOWER (109 against 76 us: a
+// wave's gathers then span four times the addresses), so a thread owns one pixel; reading the two taps of a row as one 16-byte
+// load is faster (71 us) and is what the consistency test does.
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kFlowCheckThreads = 256;
+
+struct Taps {
+    int o00, o01, o10, o11;      // pixel offsets inside one image
+    float a, b;
+    bool in;
+};
+
+__device__ __forceinline__ Taps flow_taps(int x, int y, float2 f, int H, int W) {
+    const float sx = (float)x + f.x, sy = (float)y + f.y;
+    Taps t;
+    t.in = sx >= 0.f && sx <= (float)(W - 1) && sy >= 0.f && sy <= (float)(H - 1);
+    const float px = t.in ? sx : 0.f, py = t.in ? sy : 0.f;
+    const float fx = floorf(px), fy = floorf(py);
+    const int x0 = min(max((int)fx, 0), W - 1), y0 = min(max((int)fy, 0), H - 1);
+    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
+    t.a = px - fx, t.b = py - fy;
+    t.o00 = y0 * W + x0, t.o01 = y0 * W + x1, t.o10 = y1 * W + x0, t.o11 = y1 * W + x1;
+    return t;
+}
+
+__device__ __forceinline__ float bilinear(const Taps &t, float g00, float g01, float g10, float g11) {
+    const float na = 1.f - t.a, nb = 1.f - t.b;
+    return nb * (na * g00 + t.a * g01) + t.b * (na * g10 + t.a * g11);
+}
+
+// CT > 0: the channel count at compile time (the taps of all channels are issued together); CT == 0: any C
+template <typename S, int CT>
+__global__ void __launch_bounds__(kFlowCheckThreads) warp_kernel(const S *__restrict__ src, const float2 *__restrict__ flow,
+                                                                 float *__restrict__ dst, uint8_t *__restrict__ inside, int N, int H,
+                                                                 int W, int C) {
+    const int HW = H * W;
+    const int p = (int)blockIdx.x * kFlowCheckThreads + (int)threadIdx.x;
+    if (p >= HW) return;
+    const int y = p / W, x = p - y * W;
+    const int Cn = CT > 0 ? CT : C;
+    for (int n = blockIdx.y; n < N; n += gridDim.y) {
+        const int64_t base = (int64_t)n * HW;
+        const Taps t = flow_taps(x, y, flow[base + p], H, W);
+        const S *g = src + base * Cn;
+        float *out = dst + (base + p) * Cn;
+        if (CT > 0) {
+            float v[CT > 0 ? CT : 1][4];
+#pragma unroll
+            for (int c = 0; c < CT; ++c) {
+                v[c][0] = (float)g[(int64_t)t.o00 * CT + c];
+                v[c][1] = (float)g[(int64_t)t.o01 * CT + c];
+                v[c][2] = (float)g[(int64_t)t.o10 * CT + c];
+                v[c][3] = (float)g[(int64_t)t.o11 * CT + c];
+            }
+#pragma unroll
+            for (int c = 0; c < CT; ++c) out[c] = t.in ? bilinear(t, v[c][0], v[c][1], v[c][2], v[c][3]) : 0.f;
+        } else {
+            for (int c = 0; c < Cn; ++c) {
+                const float g00 = (float)g[(int64_t)t.o00 * Cn + c], g01 = (float)g[(int64_t)t.o01 * Cn + c];
+                const float g10 = (float)g[(int64_t)t.o10 * Cn + c], g11 = (float)g[(int64_t)t.o11 * Cn + c];
+                out[c] = t.in ? bilinear(t, g00, g01, g10, g11) : 0.f;
+            }
+        }
+        if (inside != nullptr) inside[base + p] = t.in ? 1 : 0;
+    }
+}
+
+struct alignas(8) FlowPair {
+    float2 lo, hi;               // two neighbouring vectors of a row, read as one 16-byte load
+};
+
+// One pixel of the test: the image's own flow vector f at (x, y) against `other` (the other direction's flow of the same image).
+// PAIR: the two taps of a row are neighbours in memory and come as ONE 16-byte load from the first of them (from the one before
+// where the first is the row's last pixel, whose right neighbour is itself); needs W >= 2.
+template <bool PAIR>
+__device__ __forceinline__ uint32_t occluded_at(const float2 *__restrict__ other, float2 f, int x, int y, int H, int W, float alpha,
+                                                 float beta) {
+    const Taps t = flow_taps(x, y, f, H, W);
+    float2 g00, g01, g10, g11;
+    if (PAIR) {
+        const int col = t.o01 - t.o00;               // 1, or 0 where x0 is the row's last pixel
+        const FlowPair r0 = *(const FlowPair *)(other + t.o00 + col - 1), r1 = *(const FlowPair *)(other + t.o10 + col - 1);
+        g00 = col ? r0.lo : r0.hi, g01 = r0.hi, g10 = col ? r1.lo : r1.hi, g11 = r1.hi;
+    } else {
+        g00 = other[t.o00], g01 = other[t.o01], g10 = other[t.o10], g11 = other[t.o11];
+    }
+    const float sx = bilinear(t, g00.x, g01.x, g10.x, g11.x), sy = bilinear(t, g00.y, g01.y, g10.y, g11.y);
+    const float dx = f.x + sx, dy = f.y + sy;
+    const float lhs = dx * dx + dy * dy;
+    const float rhs = alpha * ((f.x * f.x + f.y * f.y) + (sx * sx + sy * sy)) + beta;
+    return (t.in && lhs <= rhs) ? 0u : 1u;           // (a NaN anywhere: occluded)
+}
+
+template <bool PAIR>
+__global__ void __launch_bounds__(kFlowCheckThreads) flow_consistency_kernel(const float2 *__restrict__ flow_a,
+                                                                             const float2 *__restrict__ flow_b,
+                                                                             uint8_t *__restrict__ occluded_a,
+                                                                             uint8_t *__restrict__ occluded_b, int N, int H, int W,
+                                                                             int slices, float alpha, float beta) {
+    const int HW = H * W;
+    const int p = (int)blockIdx.x * kFlowCheckThreads + (int)threadIdx.x;
+    if (p >= HW) return;
+    const int y = p / W, x = p - y * W;
+    for (int s = blockIdx.y; s < slices; s += gridDim.y) {
+        const bool second = s >= N;                  // wave-uniform: direction b is the same test with the roles swapped
+        const int64_t base = (int64_t)(second ? s - N : s) * HW;
+        const float2 *own = (second ? flow_b : flow_a) + base;
+        const float2 *other = (second ? flow_a : flow_b) + base;
+        (second ? occluded_b : occluded_a)[base + p] = (uint8_t)occluded_at<PAIR>(other, own[p], x, y, H, W, alpha, beta);
+    }
+}
+
+// what both entries ask of their sizes: positive, W * C in an int, fewer than 2^31 elements in the largest tensor
+int flow_check_sizes(int N, int H, int W, int C) {
+    RAFT_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0, RAFT_E_SHAPE);
+    RAFT_REQUIRE((int64_t)W * C <= 0x7fffffff, RAFT_E_SHAPE);
+    const int64_t limit = ((int64_t)1 << 31) - 1, per = C > 2 ? C : 2;
+    RAFT_REQUIRE((int64_t)N <= limit / H && (int64_t)N * H <= limit / W && (int64_t)N * H * W <= limit / per, RAFT_E_SHAPE);
+    return RAFT_OK;
+}
+
+dim3 flow_check_grid(int H, int W, int64_t slices) {
+    return dim3((unsigned)(((int64_t)H * W + kFlowCheckThreads - 1) / kFlowCheckThreads), (unsigned)(slices < 65535 ? slices : 65535));
+}
+
+template <typename S>
+int warp(const S *src, const float *flow, float *dst, uint8_t *inside, int N, int H, int W, int C, void *stream) {
+    RAFT_REQUIRE_PTR(src);
+    RAFT_REQUIRE_PTR(flow);
+    RAFT_REQUIRE_PTR(dst);
+    RAFT_TRY(flow_check_sizes(N, H, W, C));
+    RAFT_REQUIRE((((uintptr_t)flow) & 7u) == 0, RAFT_E_ALIGN);      // read as float2
+    const dim3 grid = flow_check_grid(H, W, N);
+    const float2 *f = (const float2 *)flow;
+    hipStream_t s = (hipStream_t)stream;
+    switch (C) {
+        case 1: warp_kernel<S, 1><<<grid, kFlowCheckThreads, 0, s>>>(src, f, dst, inside, N, H, W, C); break;
+        case 2: warp_kernel<S, 2><<<grid, kFlowCheckThreads, 0, s>>>(src, f, dst, inside, N, H, W, C); break;
+        case 3: warp_kernel<S, 3><<<grid, kFlowCheckThreads, 0, s>>>(src, f, dst, inside, N, H, W, C); break;
+        case 4: warp_kernel<S, 4><<<grid, kFlowCheckThreads, 0, s>>>(src, f, dst, inside, N, H, W, C); break;
+        default: warp_kernel<S, 0><<<grid, kFlowCheckThreads, 0, s>>>(src, f, dst, inside, N, H, W, C); break;
+    }
+    return raft_launch_status();
+}
+
+}   // namespace
+
+extern "C" int raft_warp_f32(const float *src, const float *flow, float *dst, uint8_t *inside, int N, int H, int W, int C,
+                             void *stream) {
+    return warp<float>(src, flow, dst, inside, N, H, W, C, stream);
+}
+
+extern "C" int raft_warp_u8_f32(const uint8_t *src, const float *flow, float *dst, uint8_t *inside, int N, int H, int W, int C,
+                                void *stream) {
+    return warp<uint8_t>(src, flow, dst, inside, N, H, W, C, stream);
+}
+
+extern "C" int raft_flow_consistency_f32(const float *flow_a, const float *flow_b, uint8_t *occluded_a, uint8_t *occluded_b, int N,
+                                         int H, int W, float alpha, float beta, void *stream) {
+    RAFT_REQUIRE_PTR(flow_a);
+    RAFT_REQUIRE_PTR(flow_b);
+    RAFT_REQUIRE_PTR(occluded_a);
+    RAFT_TRY(flow_check_sizes(N, H, W, 2));
+    RAFT_REQUIRE(alpha >= 0.f && alpha <= 3.402823466e38f && beta >= 0.f && beta <= 3.402823466e38f, RAFT_E_SHAPE);   // (a NaN fails)
+    RAFT_REQUIRE(((((uintptr_t)flow_a) | ((uintptr_t)flow_b)) & 7u) == 0, RAFT_E_ALIGN);      // read as float2
+    const int slices = occluded_b != nullptr ? 2 * N : N;
+    const dim3 grid = flow_check_grid(H, W, slices);
+    hipStream_t s = (hipStream_t)stream;
+    const float2 *fa = (const float2 *)flow_a, *fb = (const float2 *)flow_b;
+    if (W >= 2)
+        flow_consistency_kernel<true><<<grid, kFlowCheckThreads, 0, s>>>(fa, fb, occluded_a, occluded_b, N, H, W, slices, alpha, beta);
+    else
+        flow_consistency_kernel<false><<<grid, kFlowCheckThreads, 0, s>>>(fa, fb, occluded_a, occluded_b, N, H, W, slices, alpha, beta);
+    return raft_launch_status();
+}

@@ -28,6 +28,10 @@ scaled.
 (``raft_flow_rad_max_f32`` / ``raft_flow_to_image_u8``, tf_raft_amd/csrc/flow_viz.hip), optionally seen
 through the same crop-or-pad window, so a prediction leaves the device as a 3-byte picture instead of an 8-byte flow.
 
+``warp`` / ``flow_consistency`` say where a prediction can be trusted: the backward warp of frames along a
+flow, and the forward-backward test of two flows that marks occluded and out-of-frame pixels, one launch each (``raft_warp_*`` /
+``raft_flow_consistency_f32``, tf_raft_amd/csrc/flow_check.hip).
+
 The model reaches the three ways through ONE object per call (``fit_route``: a ``CropOrPadRoute``, a ``ResizeRoute`` or a
 ``TilePlan``), which answers the same four questions whichever way it is: ``frames_in(t)`` (a frame batch -> the float32 batch
 the model runs on, one launch), ``result_size(B)`` (batch and size of the result for a model batch ``B``), ``flow_back(pred,
@@ -634,3 +638,103 @@ def flow_rad_max(flow, size=None, clip_flow=None) -> torch.Tensor:
     t, t4, h, w = _flow_4d(flow, size)
     m = flow_rad_max_launch(t4, h, w, clip).amax(dim=1)
     return _dev.wrap(m if t.dim() == 4 else m[0])
+
+
+# ------------------------------------------------------------------------------------------ warp and consistency check
+CONSISTENCY_ALPHA, CONSISTENCY_BETA = 0.01, 0.5      # Meister et al. 2018 (UnFlow)
+
+
+def check_consistency_args(alpha, beta):
+    """``alpha`` and ``beta`` of the forward-backward test as floats: numbers (no bool), finite in float32 and not negative."""
+    vals = []
+    for name, v in (('alpha', alpha), ('beta', beta)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f'{name} must be a number, got {v!r}')
+        if not 0.0 <= float(v) <= float(np.finfo(np.float32).max):
+            raise ValueError(f'{name} must be finite and >= 0, got {v!r}')
+        vals.append(float(v))
+    return tuple(vals)
+
+
+def _check_flow(f, what):
+    if not f.is_contiguous():
+        raise ValueError(f'{what}: the flow must be contiguous, got strides {tuple(f.stride())} for {tuple(f.shape)}')
+    if f.dtype != torch.float32:
+        raise TypeError(f'{what}: a flow is float32, got {f.dtype}')
+    if f.data_ptr() % 8:
+        raise ValueError(f'{what} reads whole flow vectors: the flow must be 8-byte aligned')
+
+
+def warp_launch(t: torch.Tensor, flow: torch.Tensor, out=None, inside=None) -> torch.Tensor:
+    """The launch itself: contiguous device ``(N, H, W, C)`` of uint8 / bool / float32 sampled along the contiguous float32 flow
+    ``(N, H, W, 2)`` -> float32 ``(N, H, W, C)`` on the CURRENT stream (plain ``torch.Tensor``), written into ``out`` when given;
+    ``inside``: a contiguous uint8 ``(N, H, W)`` tensor to receive the in-frame map."""
+    N, H, W, Cn = t.shape
+    if tuple(flow.shape) != (N, H, W, 2) or flow.device != t.device:
+        raise ValueError(f'frames {tuple(t.shape)} on {t.device} need a flow {(N, H, W, 2)}, got {tuple(flow.shape)} on {flow.device}')
+    _check_flow(flow, 'warp')
+    if not t.is_contiguous():
+        raise ValueError(f'warp: the frames must be contiguous, got strides {tuple(t.stride())} for {tuple(t.shape)}')
+    fn, src = _source_entry(t, 'warp')
+    out = _check_out(out, (N, H, W, Cn), torch.float32, t.device)
+    inside = _check_out(inside, (N, H, W), torch.uint8, t.device, alloc=False)
+    with torch.cuda.device(t.device):
+        check(fn(_dev.ptr(src), _dev.ptr(flow), _dev.ptr(out), _dev.ptr(inside) if inside is not None else None, N, H, W, Cn,
+                 _dev.stream_ptr()), 'warp')
+    return out
+
+
+def flow_consistency_launch(flow_a: torch.Tensor, flow_b: torch.Tensor, alpha: float = CONSISTENCY_ALPHA, beta: float = CONSISTENCY_BETA,
+                            both: bool = True):
+    """The launch itself: two contiguous float32 device flows ``(N, H, W, 2)`` -> the uint8 masks ``(occluded_a, occluded_b)``,
+    each ``(N, H, W)`` with 1 = occluded, by ONE launch on the CURRENT stream (plain tensors; ``both=False``: direction a alone,
+    ``occluded_b`` is None)."""
+    if flow_a.dim() != 4 or flow_a.shape[-1] != 2 or flow_a.shape != flow_b.shape or flow_a.device != flow_b.device:
+        raise ValueError(f'expected two flows (N, H, W, 2) of one shape and device, got {tuple(flow_a.shape)} on {flow_a.device} / '
+                         f'{tuple(flow_b.shape)} on {flow_b.device}')
+    _check_flow(flow_a, 'flow_consistency')
+    _check_flow(flow_b, 'flow_consistency')
+    N, H, W, _ = flow_a.shape
+    masks = torch.empty((2 if both else 1, N, H, W), device=flow_a.device, dtype=torch.uint8)
+    with torch.cuda.device(flow_a.device):
+        check(_dev.lib().raft_flow_consistency_f32(_dev.ptr(flow_a), _dev.ptr(flow_b), _dev.ptr(masks[0]), _dev.ptr(masks[1]) if both else None,
+                                                   N, H, W, alpha, beta, _dev.stream_ptr()), 'flow_consistency')
+    return masks[0], (masks[1] if both else None)
+
+
+def _flow_like(flow, lead_shape, what):
+    f = _on_device(flow)
+    if tuple(f.shape) != tuple(lead_shape) + (2,):
+        raise ValueError(f'{what} expects a flow {tuple(lead_shape) + (2,)}, got {tuple(f.shape)}')
+    if f.dtype != torch.float32:
+        raise TypeError(f'a flow is float32, got {f.dtype}')
+    return f
+
+
+def warp(x, flow, return_inside=False, out=None):
+    """Backward warp: ``(H, W, C)`` or ``(N, H, W, C)`` frames (NumPy or torch, host or device, uint8 / bool / float32; float64
+    narrows) sampled bilinearly at every pixel's end point under ``flow`` (same leading shape, 2 channels, float32) -> a contiguous
+    float32 device tensor of the frames' shape (``out`` when given): ``result[y, x] = frames[y + v, x + u]``, so ``warp(image2,
+    flow_forward)`` reconstructs frame 1 from frame 2.  A pixel whose end point ``(float32(x) + u, float32(y) + v)`` lies outside
+    ``[0, W - 1] x [0, H - 1]`` (or is NaN) is 0 in every channel; ``return_inside=True`` also returns the uint8 map of the
+    pixels that are not.  One launch on the current stream."""
+    t, t4 = _entry(x, 'warp')
+    f = _flow_like(flow, t.shape[:-1], 'warp')
+    out = _check_out(out, tuple(t.shape), torch.float32, t.device, alloc=False)
+    inside = torch.empty(tuple(t4.shape[:3]), device=t.device, dtype=torch.uint8) if return_inside else None
+    res = warp_launch(t4, f.reshape(t4.shape[:3] + (2,)), None if out is None else out.view(t4.shape), inside)
+    res = _dev.wrap(out if out is not None else res.view(t.shape))
+    return (res, _dev.wrap(inside.view(t.shape[:-1]))) if return_inside else res
+
+
+def flow_consistency(flow_forward, flow_backward, alpha=CONSISTENCY_ALPHA, beta=CONSISTENCY_BETA):
+    """Forward-backward consistency of two float32 flows ``(H, W, 2)`` or ``(N, H, W, 2)`` (NumPy or torch, host or device):
+    ``(occluded_forward, occluded_backward)``, uint8 device tensors ``(..., H, W)`` with 1 where a vector cannot be trusted.  With
+    ``s`` the other direction's flow sampled bilinearly at the vector's end point, a pixel is occluded unless the end point lies
+    in the frame and ``|f + s|^2 <= alpha * (|f|^2 + |s|^2) + beta`` (Meister et al. 2018, whose values the defaults are); a
+    non-finite vector marks its pixel.  Both masks come from ONE launch on the current stream."""
+    alpha, beta = check_consistency_args(alpha, beta)
+    t, f4, _, _ = _flow_4d(flow_forward, None)
+    b = _flow_like(flow_backward, t.shape[:-1], 'flow_consistency')
+    occ_f, occ_b = flow_consistency_launch(f4, b.reshape(f4.shape), alpha, beta)
+    return _dev.wrap(occ_f.view(t.shape[:-1])), _dev.wrap(occ_b.view(t.shape[:-1]))

@@ -72,6 +72,15 @@ class _LoopPlan(NamedTuple):
     loop_hint: int              # launch-shape hint of the loop
 
 
+class BidirectionalFlow(NamedTuple):
+    """What ``predict_step_bidirectional`` / ``predict_bidirectional`` return: both flows ``(N, H, W, 2)`` float32 and, per
+    direction, the uint8 mask ``(N, H, W)`` of the pixels whose vector fails the forward-backward test (1 = occluded or out of frame)."""
+    forward: object
+    backward: object
+    occluded_forward: object
+    occluded_backward: object
+
+
 def _hinted(hint):
     return _ffi.thread_concurrency(hint) if hint is not None else contextlib.nullcontext()
 
@@ -180,6 +189,12 @@ class RAFT:
                 raise ValueError(f"tile_overlap belongs to fit='tile', got fit={fit!r}")
             return None
         return image_ops._overlap_pair(cls.DEFAULT_TILE_OVERLAP if tile_overlap is None else tile_overlap, *target_size)
+
+    @classmethod
+    def _check_consistency(cls, alpha, beta):
+        """``alpha`` / ``beta`` of the forward-backward test (``image_ops.flow_consistency``) as floats; anything but finite
+        numbers >= 0 is a ``ValueError``."""
+        return image_ops.check_consistency_args(alpha, beta)
 
     def _model_size(self, H, W):
         """The size the model runs at for frames of H x W under ``target_size``."""
@@ -387,7 +402,9 @@ class RAFT:
             self._train_vars, self._dw = keep
             self._inference_stale = False
 
-    def _forward(self, inputs, training=False, final_only=False, pipelined=None):
+    def _forward(self, inputs, training=False, final_only=False, pipelined=None, mirror=False):
+        """``mirror`` (inference, serial schedule): ONE pass over the 2B pairs [(image1, image2) | (image2, image1)] with the
+        feature encoder run once per frame (``_forward_serial``); the result has batch 2B, the second half the backward direction."""
         self._sync_inference_weights()
         image1, image2 = inputs
         route = None
@@ -401,7 +418,7 @@ class RAFT:
         if H % 8 or W % 8:
             raise ValueError(f'H and W must be multiples of 8 (got {H}x{W})')   # model.py:35 uses h//8
         # model.py:70-71 (2 * (image / 255) - 1) is applied by the encoders while they stage the image
-        if (self.pipeline if pipelined is None else pipelined) and not training:
+        if (self.pipeline if pipelined is None else pipelined) and not training and not mirror:
             # several lanes (and their launch shapes) only for a model that asked for the pipelined schedule: predict() on a serial
             # model overlaps its calls on ONE lane with the serial schedule's kernels, so predict() == predict_step() bit for bit
             lanes = self.lanes if self.pipeline else 1
@@ -414,7 +431,7 @@ class RAFT:
         self._join_pipeline()                       # (a training-mode or serial call after pipelined ones)
         plan = self._plan(0, self.overlap, 1 if training else self.loop_concurrency)
         with _hinted(plan.pre_hint):
-            return self._forward_serial(image1, image2, training, final_only, plan, route)
+            return self._forward_serial(image1, image2, training, final_only, plan, route, mirror and not training)
 
     def _plan(self, lane, three_stream, hint):
         """The loop plan of one call.  ``hint`` is the number of loops that share the chip: the lanes of a pipelined call,
@@ -423,8 +440,16 @@ class RAFT:
         return _LoopPlan(lane, three_stream, hint if (hint > 1 and self._shape_hint == 'all') else None,
                          hint if self._shape_hint in ('loop', 'all') else 1)
 
-    def _forward_serial(self, image1, image2, training, final_only, plan, route=None):
+    def _forward_serial(self, image1, image2, training, final_only, plan, route=None, mirror=False):
         B, H, W, _ = image1.shape
+        if mirror:
+            # Both directions as one batch of 2B pairs.  The backward direction needs the same two feature maps with their roles
+            # swapped and the context of frame 2: fnet still runs on 2B frames (not 4B), cnet on [image1 | image2], and everything
+            # from the volume build on sees an ordinary batch of 2B.
+            B = 2 * B
+            context = lambda: self.cnet.forward_device(image1, input_affine=True, images_b=image2)
+        else:
+            context = lambda: self.cnet(image1, training=training, _raw_images=True)      # model.py:82
         if self.overlap and not training:
             # the context encoder does not depend on the feature encoder or the volume: it runs on a side stream
             # next to them (its one-workgroup-per-CU layers fill the tails of the feature encoder's launches)
@@ -434,11 +459,16 @@ class RAFT:
             st = self._get_state(B, H // 8, W // 8, image1.device)    # (allocated under the caller's stream, like its other users)
             self._enc_stream.wait_stream(cur)      # also orders this call's state preparation behind the previous call's loop
             with torch.cuda.stream(self._enc_stream):
-                cnet = self.cnet(image1, training=training, _raw_images=True)      # model.py:82
+                cnet = context()
                 # net / inp / the GRU's context rows depend on cnet only (model.py:84-89): prepared here, beside the feature
                 # encoder, instead of behind the volume build (0.1 ms of the step at 4 pairs)
                 self._prepare(cnet, st)
-        fmap1, fmap2 = self.fnet([image1, image2], training=training, _raw_images=True)   # model.py:74
+        if mirror:
+            # the encoder's output (B, h, w, C) over [image1 | image2] IS the first operand; the second is its halves swapped
+            fmap1 = self.fnet.forward_device(image1, input_affine=True, images_b=image2)
+            fmap2 = torch.cat([fmap1[B // 2:], fmap1[:B // 2]], dim=0)
+        else:
+            fmap1, fmap2 = self.fnet([image1, image2], training=training, _raw_images=True)   # model.py:74
         correlation = CorrBlock(fmap1, fmap2, num_levels=self.corr_levels, radius=self.corr_radius,
                                 alternate=self.alternate_corr)                  # model.py:77
         h, w = H // 8, W // 8
@@ -446,7 +476,7 @@ class RAFT:
             cur.wait_stream(self._enc_stream)
             cnet.as_subclass(torch.Tensor).record_stream(cur)
         else:
-            cnet = self.cnet(image1, training=training, _raw_images=True)      # model.py:82
+            cnet = context()
             st = self._get_state(B, h, w, image1.device)
             self._prepare(cnet, st)                                             # model.py:84-89
         iters = self.iters if training else self.iters_pred
@@ -561,6 +591,60 @@ class RAFT:
         if self.variant == 'raft' and self.overlap and not self.alternate_corr:
             return self._forward([image1, image2], training=False, final_only=True, pipelined=_pipelined)
         return self._forward([image1, image2], training=False, pipelined=_pipelined)[-1]
+
+    def predict_step_bidirectional(self, data, alpha=image_ops.CONSISTENCY_ALPHA, beta=image_ops.CONSISTENCY_BETA):
+        """The flow in both directions with occlusion masks: ``BidirectionalFlow(forward, backward, occluded_forward,
+        occluded_backward)`` of device tensors for ``data = (image1, image2)`` -- ``forward`` what ``predict_step((image1,
+        image2))`` predicts, ``backward`` what ``predict_step((image2, image1))`` does, both ``(N, H, W, 2)`` float32 at the
+        frames' own size, and per direction the uint8 mask ``(N, H, W)`` of ``image_ops.flow_consistency(forward, backward,
+        alpha, beta)``: 1 where the vector's end point leaves the frame or the two directions disagree there (occlusion).
+
+        ONE forward pass over the 2N pairs [(image1, image2) | (image2, image1)], final prediction only, on the serial schedule
+        on the caller's stream (a model with pipelined loops in flight joins them first, as a training-mode call does), then one
+        consistency launch on the flows that are returned: with a ``target_size`` the call's route takes the 2N predictions back
+        to the frames' size first (``fit='tile'``: 2N * K tiles blend to 2N frames).  Cost: the memory and time of ``__call__``
+        on 2N pairs (docs/NOTEBOOK.md section 21 has the measurement)."""
+        alpha, beta = self._check_consistency(alpha, beta)
+        image1, image2, *_ = data
+        if self.variant == 'raft' and self.overlap and not self.alternate_corr:
+            out = self._forward([image1, image2], training=False, final_only=True, pipelined=False, mirror=True)
+        else:
+            out = self._forward([image1, image2], training=False, pipelined=False, mirror=True)[-1]
+        flows = out.as_subclass(torch.Tensor)
+        N = flows.shape[0] // 2
+        occ_f, occ_b = image_ops.flow_consistency_launch(flows[:N], flows[N:], alpha, beta)
+        return BidirectionalFlow(_dev.wrap(flows[:N]), _dev.wrap(flows[N:]), _dev.wrap(occ_f), _dev.wrap(occ_b))
+
+    def predict_bidirectional(self, x, batch_size=None, steps=None, alpha=image_ops.CONSISTENCY_ALPHA, beta=image_ops.CONSISTENCY_BETA):
+        """``predict_step_bidirectional`` over all pairs of ``x`` (as for ``predict()``: ``[image1, image2]`` arrays split into
+        batches of ``batch_size``, Keras' default 32, or an iterable of ``(image1, image2, ...)`` batches; ``steps`` limits the
+        number of batches): the same named tuple as host arrays, flows ``(N, H, W, 2)`` float32 and masks ``(N, H, W)`` uint8.
+        Host batches are uploaded one batch ahead of the compute stream (``tf_raft_amd.prefetch``); every batch's results are
+        copied back synchronously."""
+        from .prefetch import prefetch_to_device
+        alpha, beta = self._check_consistency(alpha, beta)
+        dev = _dev.require_gpu()
+        if isinstance(x, (list, tuple)) and len(x) == 2 and all(getattr(a, 'ndim', 0) == 4 for a in x):
+            n = x[0].shape[0]
+            if x[1].shape[0] != n:
+                raise ValueError(f'image1 and image2 hold {n} and {x[1].shape[0]} images')
+            bs = int(batch_size) if batch_size else 32
+            if bs < 1:
+                raise ValueError(f'batch_size must be >= 1, got {batch_size}')
+            batches = ((x[0][i:i + bs], x[1][i:i + bs]) for i in range(0, n, bs))
+        else:
+            batches = iter(x)
+        if steps is not None:
+            import itertools
+            batches = itertools.islice(batches, int(steps))
+        batches = ((b[0], b[1]) for b in batches)
+        parts = [[], [], [], []]
+        for image1, image2 in prefetch_to_device(batches, buffer_size=1, device=dev):
+            for acc, t in zip(parts, self.predict_step_bidirectional((image1, image2), alpha, beta)):
+                acc.append(t.as_subclass(torch.Tensor).cpu().numpy())
+        if not parts[0]:
+            raise ValueError('predict_bidirectional() received no batches')
+        return BidirectionalFlow(*(np.concatenate(acc, axis=0) for acc in parts))
 
     def predict(self, x, batch_size=None, steps=None, output='flow', clip_flow=None, convert_to_bgr=False, rad_max=None, **kwargs):
         """``keras.Model.predict`` over ``predict_step`` (reference model.py:160-166): the final flow of every image
