@@ -846,6 +846,27 @@ def test_pending_results_join_whichever_stream_touches_them_first():
     assert _dev.join(out) is out
 
 
+def test_a_model_deleted_while_its_loops_run_leaves_their_results_whole():
+    """Two lanes with three-stream loops, so each lane owns a loop context; the model is dropped with three calls in flight and
+    their results untouched.  Closing a lane waits for the device before its context's events go, so every result still equals
+    the serial model's (same launch shapes: loop_concurrency=2) bit for bit."""
+    import gc
+    import tf_raft_amd
+    from tf_raft_amd import weights as wm
+    wts = wm.init_weights('raft', seed=21, perturb=True)
+    pipe = tf_raft_amd.RAFT(weights=wts, pipeline=True, lanes=2, overlap=True, iters_pred=2)
+    serial = tf_raft_amd.RAFT(weights=wts, pipeline=False, loop_concurrency=2, overlap=True, iters_pred=2)
+    inputs = [tuple(torch.as_tensor(a).cuda() for a in _images(90 + k, 1, 64, 96)) for k in range(3)]
+    outs = [pipe([a, b]) for a, b in inputs]
+    del pipe
+    gc.collect()
+    for out, (a, b) in zip(outs, inputs):
+        want = serial([a, b])
+        assert len(out) == len(want) == 2
+        for g, w_ in zip(out, want):
+            np.testing.assert_array_equal(_np(g), _np(w_))
+
+
 def test_three_stream_loop_is_bitwise_the_single_stream_loop():
     """raft_iterate_basic_overlap_f32 (flow / mask branches on side streams) must reproduce
     raft_iterate_basic_f32 bit for bit on every prediction, repeatedly (no races)."""

@@ -120,6 +120,12 @@ class CorrBlock:
                                           _dev.ptr(self._pyr), self._off, _dev.ptr(self._f2pyr),
                                           _dev.stream_ptr()), 'corr_build')
 
+    def tensors(self):
+        """The block's device buffers that a loop reads (the stored volume or, on demand, the pooled ``fmap2`` pyramid, and both
+        feature maps) together with the build's workspace: what a caller that runs the loop on another stream than the one the
+        block was built on records there."""
+        return [t for t in (self._pyr, self._f2pyr, self.fmap1, self.fmap2) if t is not None]
+
     @property
     def corr_pyramid(self):
         if self._pyr is None:

@@ -11,8 +11,10 @@ tensors, ``[-1]`` the finest, each answering ``.numpy()`` like a TF eager tensor
 
 Execution: everything runs on hand-written HIP kernels behind the C ABI (``include/raft_hip.h``): the two
 encoders (``raft_encoder_f32``), the correlation volume build, and the whole recurrent loop
-(lookup -> update block -> coords update -> upsampling) enqueued by ONE ``raft_iterate_*`` call on
-the current HIP stream with no host synchronisation.  There is no CPU fallback.
+(lookup -> update block -> coords update -> upsampling) enqueued by ONE ``raft_iterate_*`` call (``RAFT._iterate``
+picks which) with no host synchronisation.  There is no CPU fallback.  One body enqueues the forward pass for the serial
+schedule (the caller's stream) and the pipelined one (loops of consecutive calls on lanes of their own, results joined lazily):
+section "the forward schedule" below; what it keeps between calls is in ``tf_raft_amd.schedule``.
 
 Callers of the forward pass (reference model.py:111-170): ``compile``, ``test_step`` (EPE / u1 / u3 / u5 of the final
 prediction against ground truth, reduced on the device: ``tf_raft_amd.losses``), ``predict_step``, ``reset_metrics``,
@@ -25,6 +27,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import itertools
 import os
 from collections import OrderedDict
 from typing import Dict, NamedTuple, Optional
@@ -40,7 +43,7 @@ from ._ffi import check
 from .layers.corr import CorrBlock, coords_grid, upflow8
 from .layers.extractor import BasicEncoder, SmallEncoder
 from .layers.update import BasicUpdateBlock, SmallUpdateBlock, UpdateState
-
+from .schedule import Lane, LoopPlan, RingSlot
 
 
 def _rank_of_this_process() -> int:
@@ -62,14 +65,6 @@ def _dropout_seed(model_seed: int, rank: int, step: int) -> int:
 
 
 DEFAULT_LANES = 3          # profiles/r12b_lanes_ab_per_process.txt: 1 / 2 / 3 / 4 / 6 lanes = 332 / 352 / 362 / 347-352 / 353-362 pairs/s at 4 pairs
-
-
-class _LoopPlan(NamedTuple):
-    """How one forward call schedules its recurrent loop, fixed when the call starts and passed down to the launchers."""
-    lane: int                   # whose flow / mask streams and raft_loop_ctx the loop uses
-    three_stream: bool          # flow / mask branches on side streams; False = the single-stream schedule
-    pre_hint: Optional[int]     # launch-shape hint of the encoders and volume build; None = the calling thread's own
-    loop_hint: int              # launch-shape hint of the loop
 
 
 class BidirectionalFlow(NamedTuple):
@@ -126,7 +121,7 @@ class RAFT:
         env_ov = os.environ.get('RAFT_OVERLAP')
         self._overlap_given = overlap is not None or env_ov is not None
         self.overlap = (env_ov != '0') if overlap is None else bool(overlap)
-        # Consecutive inference calls overlap (section "pipelined forward" below).  OPT-IN (pipeline=True or RAFT_PIPELINE=1):
+        # Consecutive inference calls overlap (section "the forward schedule" below).  OPT-IN (pipeline=True or RAFT_PIPELINE=1):
         # a pipelined call returns before its loop has finished and its results join the consuming stream lazily, which
         # consumers that bypass torch's dispatch (C++ extensions taking at::Tensor, the legacy torch.utils.dlpack.to_dlpack)
         # cannot see -- the default is the serial schedule, where stream order alone makes every route to the bytes safe.
@@ -134,9 +129,8 @@ class RAFT:
         self.pipeline = (os.environ.get('RAFT_PIPELINE', '0') == '1') if pipeline is None else bool(pipeline)
         # Pipelined forward: how many recurrent loops may be in flight at once (each on streams of its own; RAFT_LANES).
         self.lanes = max(1, int(os.environ.get('RAFT_LANES', str(DEFAULT_LANES))) if lanes is None else int(lanes))
-        self._enc_stream = None
-        self._state = None
-        self._ring = []                          # pipelined forward: [UpdateState, loop-done event] per slot (lanes + 1 slots)
+        self._state = None                       # serial schedule: the one UpdateState, reused by stream order
+        self._ring = []                          # pipelined forward: one RingSlot per state in flight (lanes + 1 slots)
         self._calls = 0
         # which launches of a multi-lane call get the library's concurrency hint (launch shapes of a lanes-times larger batch):
         # 'loop' = the recurrent loop, 'all' = encoders and volume build as well, 'none'
@@ -144,7 +138,7 @@ class RAFT:
         # serial schedule: the hint its loops are launched with (1 = latency shapes; tests give a serial model the lanes of a
         # pipelined one to obtain the same kernels, hence the same bits)
         self.loop_concurrency = 1 if loop_concurrency is None else max(1, int(loop_concurrency))
-        self._lane_res = {}                      # lane -> (device, (flow stream, mask stream), raft_loop_ctx handle)
+        self._open_lanes = {}                    # lane index -> Lane, made at the lane's first loop
         _dev.reserve_streams(_dev.require_gpu())
         _dev.lib()
         if weights is None:
@@ -152,6 +146,8 @@ class RAFT:
         weights_mod.check_weights(self.variant, weights)
         self._weights = dict(weights)
         self._dw, self._host_stale, self._train_vars = None, False, None     # device master copies of train_step
+        self._inference_stale = False            # train_step updated them: the inference kernels' packed copies are behind
+        self._last_correlation = None
         self._build(weights)
 
     MIN_SIDE = 64      # the four-level pyramid pools an H/8 x W/8 map three times: below 8 rows or columns its last level is empty
@@ -254,7 +250,7 @@ class RAFT:
     def _sync_host(self):
         """``train_step`` keeps the master weights (and the batch-norm moving statistics) on the device and updates them in
         place; the NumPy dictionary is refreshed from them only when somebody asks for it (checkpoint, inference re-pack)."""
-        if getattr(self, '_host_stale', False) and self._dw is not None:
+        if self._host_stale and self._dw is not None:
             self._weights = {k: v.detach().cpu().numpy() for k, v in self._dw.items()}
             self._host_stale = False
 
@@ -304,84 +300,51 @@ class RAFT:
                                                 _dev.stream_ptr()), 'prepare_state')
         self.update_block.prepare(st)          # GRU terms of `inp`: constant over the loop (model.py:86)
 
-    @staticmethod
-    def _lane_role(role, lane):
-        return role if lane == 0 else f'{role}{lane}'
-
-    def _lane_entry(self, dev, lane):
-        """(device, (flow stream, mask stream), loop-context handle or None) of ``lane``."""
-        ent = self._lane_res.get(lane)
-        if ent is None or ent[0] != dev:
-            if ent is not None:
-                self._free_lane(lane)
-            aux = (_dev.side_stream(dev, self._lane_role('flow', lane)), _dev.side_stream(dev, self._lane_role('mask', lane)))
-            ent = self._lane_res[lane] = [dev, aux, None]
-        return ent
-
-    def _aux_streams(self, dev, lane):
-        return self._lane_entry(dev, lane)[1]
-
-    def _loop_context(self, dev, lane):
-        """The caller-owned ``raft_loop_ctx`` (cross-stream events) of the three-stream loops: one per lane (loops of different
-        lanes run concurrently; loops of one lane follow each other in stream order and share it)."""
-        ent = self._lane_entry(dev, lane)
-        if ent[2] is None:
-            handle = C.c_void_p()
-            with torch.cuda.device(dev):
-                check(_dev.lib().raft_loop_ctx_create(C.byref(handle)), 'loop_ctx_create')
-            ent[2] = handle
-        return ent[2]
-
-    def _free_lane(self, lane):
-        ent = self._lane_res.pop(lane, None)
-        if ent is not None and ent[2] is not None:
-            try:
-                torch.cuda.synchronize(ent[0])
-                _dev.lib().raft_loop_ctx_destroy(ent[2])
-            except Exception:   # noqa: BLE001  (interpreter shutdown)
-                pass
-
-    def _free_loop_context(self):
-        for lane in list(getattr(self, '_lane_res', {})):
-            self._free_lane(lane)
+    def _lane(self, dev, index) -> Lane:
+        lane = self._open_lanes.get(index)
+        if lane is None or lane.device != dev:
+            if lane is not None:
+                lane.close()
+            lane = self._open_lanes[index] = Lane(dev, index)
+        return lane
 
     def __del__(self):
-        self._free_loop_context()
+        for lane in getattr(self, '_open_lanes', {}).values():      # (an object made without __init__ has none)
+            lane.close()
 
-    def _loop_streams(self, dev, plan, need_ctx=True):
-        """``(s0, s1, s2, ctx)`` of a loop: the current stream and, on the three-stream schedule, the lane's flow and mask
-        streams (events inside the library); otherwise the current stream three times = the single-stream schedule of a lane.
-        ``ctx`` is the lane's loop context; ``need_ctx=False``: only where the streams differ (else None, none is created)."""
-        s0 = _dev.stream_ptr()
-        s1, s2 = ((a.cuda_stream for a in self._aux_streams(dev, plan.lane)) if plan.three_stream else (s0, s0))
-        return s0, s1, s2, (self._loop_context(dev, plan.lane) if need_ctx or plan.three_stream else None)
-
-    def _iterate(self, corr: CorrBlock, st, iters, flow_up, plan=None):
+    def _iterate(self, corr: CorrBlock, st, iters, out, plan=None, final_only=False):
+        """model.py:93-109 on the CURRENT stream (+ the lane's flow / mask streams on the three-stream schedule): the ONE place
+        that picks the loop's entry point.  ``out`` takes all ``iters`` predictions, ``final_only`` the last one alone."""
         if plan is None:                            # called on its own: lane 0 of the serial schedule
             plan = self._plan(0, self.overlap, 1)
-        s0, s1, s2, ctx = self._loop_streams(flow_up.device, plan, need_ctx=False)
-        if plan.three_stream:
-            # flow branch and mask branch of every iteration on two side streams
-            check(_dev.lib().raft_iterate_basic_overlap_f32(
-                C.byref(self.update_block.c), _dev.ptr(corr._pyr), corr._off, st.B, st.h, st.w, iters, C.byref(st.c),
-                _dev.ptr(flow_up), s0, s1, s2, ctx), 'iterate_basic_overlap')
-            return
-        check(_dev.lib().raft_iterate_basic_f32(C.byref(self.update_block.c), _dev.ptr(corr._pyr), corr._off,
-                                                st.B, st.h, st.w, iters, C.byref(st.c), _dev.ptr(flow_up), s0), 'iterate_basic')
-
-    def _iterate_alternate(self, corr: CorrBlock, st, iters, flow_up, plan):
-        if self.variant == 'raft' and self.overlap:
+        lib, wts = _dev.lib(), C.byref(self.update_block.c)
+        loop_args = lambda: self._lane(out.device, plan.lane).loop_args(plan)      # (s0, s1, s2, ctx) of the entry points that take them
+        if final_only:
+            # mask head and convex upsampling in the last iteration only (_predict_final says which models take it)
+            check(lib.raft_iterate_basic_final_f32(wts, _dev.ptr(corr._pyr), corr._off, st.B, st.h, st.w, iters, C.byref(st.c),
+                                                   _dev.ptr(out), *loop_args()), 'iterate_basic_final')
+        elif self.alternate_corr and self.variant == 'raft' and self.overlap:
             # the same C loop, lookups computed on demand from fmap1 and the pooled fmap2 pyramid; overlap=False keeps the loop below
-            check(_dev.lib().raft_iterate_basic_ondemand_f32(
-                C.byref(self.update_block.c), _dev.ptr(corr.fmap1), _dev.ptr(corr._f2pyr), corr.fmap1.shape[-1],
-                st.B, st.h, st.w, iters, C.byref(st.c), _dev.ptr(flow_up), *self._loop_streams(flow_up.device, plan)),
-                'iterate_basic_ondemand')
-            return
-        g = st.g
-        for i in range(iters):
-            corr.retrieve(st.coords1, out=st.corr, ld_out=g['corr_ld'])
-            self.update_block.step(st)
-            self._upsample_into(st, flow_up[i])
+            check(lib.raft_iterate_basic_ondemand_f32(wts, _dev.ptr(corr.fmap1), _dev.ptr(corr._f2pyr), corr.fmap1.shape[-1],
+                                                      st.B, st.h, st.w, iters, C.byref(st.c), _dev.ptr(out), *loop_args()),
+                  'iterate_basic_ondemand')
+        elif self.alternate_corr:
+            for i in range(iters):
+                corr.retrieve(st.coords1, out=st.corr, ld_out=st.g['corr_ld'])
+                self.update_block.step(st)
+                self._upsample_into(st, out[i])
+        elif self.variant == 'small':
+            check(lib.raft_iterate_small_f32(wts, _dev.ptr(corr._pyr), corr._off, st.B, st.h, st.w, iters, C.byref(st.c),
+                                             _dev.ptr(out), _dev.stream_ptr()), 'iterate_small')
+        elif plan.three_stream:
+            # flow branch and mask branch of every iteration on two side streams
+            check(lib.raft_iterate_basic_overlap_f32(wts, _dev.ptr(corr._pyr), corr._off, st.B, st.h, st.w, iters, C.byref(st.c),
+                                                     _dev.ptr(out), *loop_args()), 'iterate_basic_overlap')
+        else:
+            # (takes no loop context: none is created for a model that only ever runs this one)
+            check(lib.raft_iterate_basic_f32(wts, _dev.ptr(corr._pyr), corr._off, st.B, st.h, st.w, iters, C.byref(st.c),
+                                             _dev.ptr(out), _dev.stream_ptr()), 'iterate_basic')
+        self._last_correlation = corr               # keep buffers alive until the stream drains
 
     def _upsample_into(self, st, out):
         check(_dev.lib().raft_upsample_convex_f32(_dev.ptr(st.flow), _dev.ptr(st.mask), st.B, st.h, st.w,
@@ -395,16 +358,35 @@ class RAFT:
         return self._forward(inputs, training)
 
     def _sync_inference_weights(self):
-        if getattr(self, '_inference_stale', False):
+        if self._inference_stale:
             self._sync_host()
             keep = (self._train_vars, self._dw)
             self.set_weights(self._weights)
             self._train_vars, self._dw = keep
             self._inference_stale = False
 
+    # ---- the forward schedule: serial and pipelined forward ---------------------------------------------------------------
+    # One inference call = encoders + volume build (2.96 of 12.3 ms at 4 pairs, kernels that fill the chip) followed by the 24
+    # iterations of a DEPENDENT chain whose launches leave 32 .. 88 of the 256 CUs idle.  _forward picks the call's plan and the
+    # streams of three roles, and ONE body (_run) enqueues the pass on them: the context stream (cnet and the state preparation),
+    # the pre-loop stream (fnet and the volume build: always the caller's) and the loop stream.  For a role that has the caller's
+    # stream the body does nothing -- no event, no wait, no record_stream, no stream context: the serial schedule does not pay for
+    # the pipelined one's plumbing.  Every ordering rule is a comment at the line in _run that enforces it.
+    # Serial schedule: all on the caller's stream, with `overlap` the context encoder beside the feature encoder on the 'encoder'
+    # side stream.  Stream order alone makes every route to the result's bytes safe.
+    # Pipelined schedule: back-to-back calls are independent of each other, so call n + 1's pre-loop work can run under call n's
+    # loop.  The loop is enqueued on the loop stream of lane n % lanes, the pre-loop work stays on the caller's stream, and the
+    # returned tensors carry a `_dev.Pending`: whichever stream first touches their data waits for the loop then (a caller that
+    # consumes the result at once sees the serial schedule).  Why several lanes: the loop's kernels are launched for ONE batch,
+    # 7 * 2^k workgroups on 256 CUs, a ~3 us boundary between dependent kernels, one event gap per iteration -- which is why 8
+    # pairs per call run 9 % and 16 pairs 17 % faster per pair than 4.  With `lanes` = D > 1 up to D loops of consecutive calls
+    # are resident together (schedule.Lane) and each fills the other's gaps and idle CUs; the loop state, which call n + 1 would
+    # overwrite, exists D + 1 times (schedule.RingSlot).  Each call still runs exactly the kernels of the serial schedule in the
+    # same order on its own buffers: results are bit-identical per call
+    # (tests/test_gpu_model.py::test_pipelined_calls_are_bitwise_the_serial_calls).
     def _forward(self, inputs, training=False, final_only=False, pipelined=None, mirror=False):
         """``mirror`` (inference, serial schedule): ONE pass over the 2B pairs [(image1, image2) | (image2, image1)] with the
-        feature encoder run once per frame (``_forward_serial``); the result has batch 2B, the second half the backward direction."""
+        feature encoder run once per frame; the result has batch 2B, the second half the backward direction."""
         self._sync_inference_weights()
         image1, image2 = inputs
         route = None
@@ -418,6 +400,8 @@ class RAFT:
         if H % 8 or W % 8:
             raise ValueError(f'H and W must be multiples of 8 (got {H}x{W})')   # model.py:35 uses h//8
         # model.py:70-71 (2 * (image / 255) - 1) is applied by the encoders while they stage the image
+        dev = image1.device
+        slot = context_stream = loop_stream = None          # None = the caller's stream
         if (self.pipeline if pipelined is None else pipelined) and not training and not mirror:
             # several lanes (and their launch shapes) only for a model that asked for the pipelined schedule: predict() on a serial
             # model overlaps its calls on ONE lane with the serial schedule's kernels, so predict() == predict_step() bit for bit
@@ -426,43 +410,63 @@ class RAFT:
             self._calls += 1
             # with several lanes the loops are single-stream unless overlap was asked for: the lanes are each other's side branches
             plan = self._plan(n % lanes, self.overlap and not (lanes > 1 and not self._overlap_given), lanes)
-            with _hinted(plan.pre_hint):
-                return self._forward_lane(image1, image2, final_only, n, lanes, plan, route)
-        self._join_pipeline()                       # (a training-mode or serial call after pipelined ones)
-        plan = self._plan(0, self.overlap, 1 if training else self.loop_concurrency)
-        with _hinted(plan.pre_hint):
-            return self._forward_serial(image1, image2, training, final_only, plan, route, mirror and not training)
+            while len(self._ring) <= lanes:
+                self._ring.append(RingSlot())
+            slot, loop_stream = self._ring[n % (lanes + 1)], self._lane(dev, plan.lane).stream('loop')
+        else:
+            self._join_pipeline()                       # (a training-mode or serial call after pipelined ones)
+            plan = self._plan(0, self.overlap, 1 if training else self.loop_concurrency)
+            if self.overlap and not training:
+                # the context encoder does not depend on the feature encoder or the volume: it runs on a side stream
+                # next to them (its one-workgroup-per-CU layers fill the tails of the feature encoder's launches)
+                context_stream = _dev.side_stream(dev, 'encoder')
+        with _hinted(plan.pre_hint):                    # (the loop's own hint inside; the thread's is restored on the way out)
+            return self._run(image1, image2, training, final_only, mirror and not training, plan, route, slot, context_stream, loop_stream)
 
     def _plan(self, lane, three_stream, hint):
         """The loop plan of one call.  ``hint`` is the number of loops that share the chip: the lanes of a pipelined call,
         loop_concurrency of a serial inference call, 1 in training.  RAFT_LANE_SHAPES says whether the loop ('loop', 'all') and the
         pre-loop work ('all') are launched with it; with a hint of 1 the pre-loop work keeps the calling thread's own."""
-        return _LoopPlan(lane, three_stream, hint if (hint > 1 and self._shape_hint == 'all') else None,
-                         hint if self._shape_hint in ('loop', 'all') else 1)
+        return LoopPlan(lane, three_stream, hint if (hint > 1 and self._shape_hint == 'all') else None,
+                        hint if self._shape_hint in ('loop', 'all') else 1)
 
-    def _forward_serial(self, image1, image2, training, final_only, plan, route=None, mirror=False):
+    def _run(self, image1, image2, training, final_only, mirror, plan, route, slot, context_stream, loop_stream):
+        """The forward pass of both schedules.  ``slot`` / ``loop_stream``: the ring slot and the lane's loop stream of a pipelined
+        call; ``context_stream``: the side stream of the context encoder; None = the caller's stream, the serial state."""
         B, H, W, _ = image1.shape
+        dev = image1.device
+        cur = torch.cuda.current_stream(dev)
         if mirror:
             # Both directions as one batch of 2B pairs.  The backward direction needs the same two feature maps with their roles
             # swapped and the context of frame 2: fnet still runs on 2B frames (not 4B), cnet on [image1 | image2], and everything
             # from the volume build on sees an ordinary batch of 2B.
             B = 2 * B
-            context = lambda: self.cnet.forward_device(image1, input_affine=True, images_b=image2)
+        if slot is None:
+            st = self._get_state(B, H // 8, W // 8, dev)     # (allocated under the caller's stream, like its other users)
         else:
-            context = lambda: self.cnet(image1, training=training, _raw_images=True)      # model.py:82
-        if self.overlap and not training:
-            # the context encoder does not depend on the feature encoder or the volume: it runs on a side stream
-            # next to them (its one-workgroup-per-CU layers fill the tails of the feature encoder's launches)
-            cur = torch.cuda.current_stream(image1.device)
-            if self._enc_stream is None or self._enc_stream.device != image1.device:
-                self._enc_stream = _dev.side_stream(image1.device, 'encoder')
-            st = self._get_state(B, H // 8, W // 8, image1.device)    # (allocated under the caller's stream, like its other users)
-            self._enc_stream.wait_stream(cur)      # also orders this call's state preparation behind the previous call's loop
-            with torch.cuda.stream(self._enc_stream):
+            st = slot.fit(self.variant, B, H // 8, W // 8, dev)
+            if slot.done is not None:
+                # a pipelined call never makes the caller's stream wait for a loop, except for the one that read the state this
+                # call is about to overwrite (call n - lanes - 1), and that in front of the state preparation
+                cur.wait_event(slot.done)
+
+        def context():
+            if mirror:
+                cnet = self.cnet.forward_device(image1, input_affine=True, images_b=image2)
+            else:
+                cnet = self.cnet(image1, training=training, _raw_images=True)             # model.py:82
+            self._prepare(cnet, st)                                                       # model.py:84-89
+            return cnet
+
+        if context_stream is not None:
+            # net / inp / the GRU's context rows depend on cnet only: prepared there too, beside the feature encoder, instead
+            # of behind the volume build (0.1 ms of the step at 4 pairs).  The encoder stream follows the caller's first, which
+            # also orders this call's state preparation behind the previous call's loop
+            context_stream.wait_stream(cur)
+            with torch.cuda.stream(context_stream):
                 cnet = context()
-                # net / inp / the GRU's context rows depend on cnet only (model.py:84-89): prepared here, beside the feature
-                # encoder, instead of behind the volume build (0.1 ms of the step at 4 pairs)
-                self._prepare(cnet, st)
+        elif not training:
+            cnet = context()       # (kept to the end of the call, as the other pre-loop buffers are: one allocation pattern per call)
         if mirror:
             # the encoder's output (B, h, w, C) over [image1 | image2] IS the first operand; the second is its halves swapped
             fmap1 = self.fnet.forward_device(image1, input_affine=True, images_b=image2)
@@ -471,126 +475,56 @@ class RAFT:
             fmap1, fmap2 = self.fnet([image1, image2], training=training, _raw_images=True)   # model.py:74
         correlation = CorrBlock(fmap1, fmap2, num_levels=self.corr_levels, radius=self.corr_radius,
                                 alternate=self.alternate_corr)                  # model.py:77
-        h, w = H // 8, W // 8
-        if self.overlap and not training:
-            cur.wait_stream(self._enc_stream)
-            cnet.as_subclass(torch.Tensor).record_stream(cur)
-        else:
-            cnet = context()
-            st = self._get_state(B, h, w, image1.device)
-            self._prepare(cnet, st)                                             # model.py:84-89
+        if context_stream is not None:
+            cur.wait_stream(context_stream)             # the loop reads what the encoder stream prepared ...
+            cnet.as_subclass(torch.Tensor).record_stream(cur)       # ... and cnet, allocated there, is the caller's stream's to reuse
+        elif training:
+            cnet = context()       # the reference's order: the encoders' dropout draws from one generator, fnet's mask first
         iters = self.iters if training else self.iters_pred
-        with _ffi.thread_concurrency(plan.loop_hint):
-            out = self._run_loop(correlation, st, iters, self._alloc_out(iters, B, H, W, image1.device, final_only), final_only, plan)
-        if route is not None:
-            out = route.flow_back(out)              # to the frames' own size: follows the loop on the current stream
-        return _dev.wrap(out) if final_only else [_dev.wrap(out[i]) for i in range(iters)]   # model.py:109
+        shape = (B, H, W, 2)
+        # from the caller's stream's pool, like every other buffer; the result has the frames' batch and size (the tiles of
+        # fit='tile' are a batch of N * K)
+        out = torch.empty(shape if final_only else (iters,) + shape, device=dev, dtype=torch.float32)
+        res = out if route is None else torch.empty(out.shape[:-4] + route.result_size(B) + (2,), device=dev, dtype=torch.float32)
+        if loop_stream is not None:
+            # the loop stream waits for ONE event of the caller's stream, behind the volume build and the allocations above
+            ready = torch.cuda.Event()
+            ready.record(cur)
+            loop_stream.wait_event(ready)
+        with (torch.cuda.stream(loop_stream) if loop_stream is not None else contextlib.nullcontext()), _ffi.thread_concurrency(plan.loop_hint):
+            self._iterate(correlation, st, iters, out, plan, final_only)
+            if route is not None:
+                # to the frames' own size on the LOOP's stream, in front of `done`: the caller's stream never waits for the loop
+                route.flow_back(out, into=res)
+            if loop_stream is not None:
+                slot.done = torch.cuda.Event()
+                slot.done.record(loop_stream)
+        pending = None
+        if loop_stream is not None:
+            for t in (out, res, *correlation.tensors(), *(route.tensors() if route is not None else ())):
+                t.record_stream(loop_stream)             # allocated under the caller's stream, in use on the loop stream
+            pending = _dev.Pending(slot.done, dev)
+        return _dev.wrap(res, pending) if final_only else [_dev.wrap(res[i], pending) for i in range(iters)]   # model.py:109
 
-    @staticmethod
-    def _alloc_out(iters, B, H, W, dev, final_only):
-        return torch.empty((B, H, W, 2) if final_only else (iters, B, H, W, 2), device=dev, dtype=torch.float32)
-
-    def _run_loop(self, correlation, st, iters, out, final_only, plan):
-        """model.py:93-109 on the CURRENT stream (+ the two aux streams of the three-stream schedule) into ``out``."""
-        B, h, w = st.B, st.h, st.w
-        if final_only:
-            last = out
-            check(_dev.lib().raft_iterate_basic_final_f32(
-                C.byref(self.update_block.c), _dev.ptr(correlation._pyr), correlation._off, B, h, w, iters, C.byref(st.c),
-                _dev.ptr(last), *self._loop_streams(last.device, plan)), 'iterate_basic_final')
-            self._last_correlation = correlation
-            return last
-        flow_up = out
-        if self.alternate_corr:
-            self._iterate_alternate(correlation, st, iters, flow_up, plan)
-        else:
-            self._iterate(correlation, st, iters, flow_up, plan)                # model.py:93-106
-        self._last_correlation = correlation                                    # keep buffers alive until the stream drains
-        return flow_up
-
-    # ---- pipelined forward ------------------------------------------------------------------------------------------------
-    # One inference call = encoders + volume build (2.96 of 12.3 ms at 4 pairs, kernels that fill the chip) followed by the 24
-    # iterations of a DEPENDENT chain whose launches leave 32 .. 88 of the 256 CUs idle.  Back-to-back calls are independent of
-    # each other, so call n + 1's pre-loop work can run under call n's loop: the loop is enqueued on the process-wide 'loop'
-    # stream (its flow / mask branches on the aux streams, as before), the pre-loop work stays on the caller's stream, and the
-    # caller's stream is NOT made to wait for the loop -- the returned tensors carry a `_dev.Pending` and whichever stream first
-    # touches their data waits for the loop then (a caller that consumes the result at once sees the serial schedule).  What
-    # makes this safe: the loop's inputs that the next call would overwrite exist twice (UpdateState ring; call n + 2's
-    # pre-loop waits for loop n's event before it touches slot n & 1), per-call allocations read or written by the loop
-    # (volume, feature maps of the on-demand lookup, the predictions) are recorded on the loop stream so the caching allocator
-    # cannot hand them out before the loop has finished, and loops of consecutive calls follow each other in stream order.
-    # Per-call results are bit-identical to the serial schedule (same kernels, same order per call):
-    # tests/test_gpu_model.py::test_pipelined_calls_are_bitwise_the_serial_calls.
     def _join_pipeline(self):
         """Make the current stream wait for every loop this model still has in flight: called before anything that frees or
         rewrites buffers a loop reads (weight blobs, training's in-place optimizer updates) -- in the serial schedule stream order
         gave that for free."""
-        for ent in getattr(self, '_ring', ()):
-            if ent is not None and ent[1] is not None:
-                torch.cuda.current_stream(ent[0].net.device).wait_event(ent[1])
+        for slot in self._ring:
+            slot.join()
 
-    def _ring_state(self, slot, B, h, w, device):
-        while len(self._ring) <= slot:
-            self._ring.append(None)
-        ent = self._ring[slot]
-        if ent is None or (ent[0].B, ent[0].h, ent[0].w) != (B, h, w) or ent[0].net.device != device:
-            if ent is not None and ent[1] is not None:
-                ent[1].synchronize()                     # the old buffers are about to be freed: their last loop must be done
-            ent = self._ring[slot] = [UpdateState(self.variant, B, h, w, device), None]
-        return ent
-
-    # Several loops in flight (round 6).  The loop's kernels are launched for ONE batch: 7 * 2^k workgroups on 256 CUs, a
-    # ~3 us boundary between dependent kernels, one event gap per iteration -- which is why 8 pairs per call run 9 % and 16 pairs
-    # 17 % faster per pair than 4.  With `lanes` = D > 1 call n's loop runs on lane n % D (loop / flow / mask streams and a
-    # raft_loop_ctx of its own), so up to D loops of consecutive calls are resident together and each fills the other's gaps and
-    # idle CUs; the UpdateState ring has D + 1 slots (call n + D + 1's pre-loop waits for loop n).  Each call still runs exactly
-    # the kernels of the serial schedule in the same order on its own buffers: results stay bit-identical per call.
-    def _forward_lane(self, image1, image2, final_only, n, lanes, plan, route=None):
-        B, H, W, _ = image1.shape
-        h, w = H // 8, W // 8
-        dev = image1.device
-        cur = torch.cuda.current_stream(dev)
-        loop = _dev.side_stream(dev, self._lane_role('loop', plan.lane))
-        ent = self._ring_state(n % (lanes + 1), B, h, w, dev)
-        st = ent[0]
-        if ent[1] is not None:
-            cur.wait_event(ent[1])                       # slot's previous user (call n - lanes - 1): its loop read this state
-        cnet = self.cnet(image1, training=False, _raw_images=True)                      # model.py:82
-        self._prepare(cnet, st)                                                          # model.py:84-89
-        fmap1, fmap2 = self.fnet([image1, image2], training=False, _raw_images=True)    # model.py:74
-        correlation = CorrBlock(fmap1, fmap2, num_levels=self.corr_levels, radius=self.corr_radius,
-                                alternate=self.alternate_corr)                           # model.py:77
-        out = self._alloc_out(self.iters_pred, B, H, W, dev, final_only)      # from the caller's stream's pool, like every other buffer
-        # (the result has the frames' batch and size: the tiles of fit='tile' are a batch of N * K)
-        res = out if route is None else self._alloc_out(self.iters_pred, *route.result_size(B), dev, final_only)
-        ready = torch.cuda.Event()
-        ready.record(cur)
-        loop.wait_event(ready)
-        with torch.cuda.stream(loop), _ffi.thread_concurrency(plan.loop_hint):
-            self._run_loop(correlation, st, self.iters_pred, out, final_only, plan)
-            if route is not None:
-                # back to the frames' own size on the LOOP's stream, in front of `done`: the caller's stream never waits for the loop
-                route.flow_back(out, into=res)
-            done = torch.cuda.Event()
-            done.record(loop)
-        tables = route.tensors() if route is not None else []
-        for t in (out, res, getattr(correlation, '_pyr', None), getattr(correlation, '_f2pyr', None), correlation.fmap1, correlation.fmap2, *tables):
-            if isinstance(t, torch.Tensor) and t.is_cuda:
-                t.as_subclass(torch.Tensor).record_stream(loop)      # allocated under `cur`, in use on `loop`
-        ent[1] = done
-        pending = _dev.Pending(done, dev)
-        if final_only:
-            return _dev.wrap(res, pending)
-        return [_dev.wrap(res[i], pending) for i in range(self.iters_pred)]             # model.py:109
+    def _predict_final(self, image1, image2, **how):
+        """``flow_predictions[-1]`` of an inference call.  RAFT with overlap and a stored volume computes it with the mask head and
+        the convex upsampling in the last iteration only (``raft_iterate_basic_final_f32``: the recurrence itself is unchanged, so
+        the result equals ``self(...)[-1]``)."""
+        if self.variant == 'raft' and self.overlap and not self.alternate_corr:
+            return self._forward([image1, image2], final_only=True, **how)
+        return self._forward([image1, image2], **how)[-1]
 
     def predict_step(self, data, _pipelined=None):
-        """reference model.py:160-166: ``flow_predictions[-1]`` of the forward pass.  RAFT computes it with the mask head
-        and the convex upsampling in the last iteration only (``raft_iterate_basic_final_f32``: the recurrence itself
-        is unchanged, so the result equals ``self(...)[-1]``)."""
+        """reference model.py:160-166: ``flow_predictions[-1]`` of the forward pass (``_predict_final``)."""
         image1, image2, *_ = data
-        if self.variant == 'raft' and self.overlap and not self.alternate_corr:
-            return self._forward([image1, image2], training=False, final_only=True, pipelined=_pipelined)
-        return self._forward([image1, image2], training=False, pipelined=_pipelined)[-1]
+        return self._predict_final(image1, image2, pipelined=_pipelined)
 
     def predict_step_bidirectional(self, data, alpha=image_ops.CONSISTENCY_ALPHA, beta=image_ops.CONSISTENCY_BETA):
         """The flow in both directions with occlusion masks: ``BidirectionalFlow(forward, backward, occluded_forward,
@@ -606,24 +540,17 @@ class RAFT:
         on 2N pairs (docs/NOTEBOOK.md section 21 has the measurement)."""
         alpha, beta = self._check_consistency(alpha, beta)
         image1, image2, *_ = data
-        if self.variant == 'raft' and self.overlap and not self.alternate_corr:
-            out = self._forward([image1, image2], training=False, final_only=True, pipelined=False, mirror=True)
-        else:
-            out = self._forward([image1, image2], training=False, pipelined=False, mirror=True)[-1]
-        flows = out.as_subclass(torch.Tensor)
+        flows = self._predict_final(image1, image2, pipelined=False, mirror=True).as_subclass(torch.Tensor)
         N = flows.shape[0] // 2
         occ_f, occ_b = image_ops.flow_consistency_launch(flows[:N], flows[N:], alpha, beta)
         return BidirectionalFlow(_dev.wrap(flows[:N]), _dev.wrap(flows[N:]), _dev.wrap(occ_f), _dev.wrap(occ_b))
 
-    def predict_bidirectional(self, x, batch_size=None, steps=None, alpha=image_ops.CONSISTENCY_ALPHA, beta=image_ops.CONSISTENCY_BETA):
-        """``predict_step_bidirectional`` over all pairs of ``x`` (as for ``predict()``: ``[image1, image2]`` arrays split into
-        batches of ``batch_size``, Keras' default 32, or an iterable of ``(image1, image2, ...)`` batches; ``steps`` limits the
-        number of batches): the same named tuple as host arrays, flows ``(N, H, W, 2)`` float32 and masks ``(N, H, W)`` uint8.
-        Host batches are uploaded one batch ahead of the compute stream (``tf_raft_amd.prefetch``); every batch's results are
-        copied back synchronously."""
-        from .prefetch import prefetch_to_device
-        alpha, beta = self._check_consistency(alpha, beta)
-        dev = _dev.require_gpu()
+    @staticmethod
+    def _pair_batches(x, batch_size, steps):
+        """The ``(image1, image2)`` batches of ``predict`` / ``predict_bidirectional`` as one generator, and the number of pairs
+        they hold where it is known beforehand (else None): ``x`` is ``[image1, image2]`` arrays, split into batches of
+        ``batch_size`` (Keras' default 32), or an iterable of ``(image1, image2, ...)`` batches; ``steps`` limits their number."""
+        n = None
         if isinstance(x, (list, tuple)) and len(x) == 2 and all(getattr(a, 'ndim', 0) == 4 for a in x):
             n = x[0].shape[0]
             if x[1].shape[0] != n:
@@ -635,9 +562,19 @@ class RAFT:
         else:
             batches = iter(x)
         if steps is not None:
-            import itertools
             batches = itertools.islice(batches, int(steps))
-        batches = ((b[0], b[1]) for b in batches)
+        return ((b[0], b[1]) for b in batches), (n if steps is None else None)
+
+    def predict_bidirectional(self, x, batch_size=None, steps=None, alpha=image_ops.CONSISTENCY_ALPHA, beta=image_ops.CONSISTENCY_BETA):
+        """``predict_step_bidirectional`` over all pairs of ``x`` (as for ``predict()``: ``[image1, image2]`` arrays split into
+        batches of ``batch_size``, Keras' default 32, or an iterable of ``(image1, image2, ...)`` batches; ``steps`` limits the
+        number of batches): the same named tuple as host arrays, flows ``(N, H, W, 2)`` float32 and masks ``(N, H, W)`` uint8.
+        Host batches are uploaded one batch ahead of the compute stream (``tf_raft_amd.prefetch``); every batch's results are
+        copied back synchronously."""
+        from .prefetch import prefetch_to_device
+        alpha, beta = self._check_consistency(alpha, beta)
+        dev = _dev.require_gpu()
+        batches, _ = self._pair_batches(x, batch_size, steps)
         parts = [[], [], [], []]
         for image1, image2 in prefetch_to_device(batches, buffer_size=1, device=dev):
             for acc, t in zip(parts, self.predict_step_bidirectional((image1, image2), alpha, beta)):
@@ -664,24 +601,9 @@ class RAFT:
             raise ValueError(f"output must be 'flow' or 'image', got {output!r}")
         viz = image_ops._viz_args(clip_flow, rad_max) if output == 'image' else None
         dev = _dev.require_gpu()
-        arrays = isinstance(x, (list, tuple)) and len(x) == 2 and all(getattr(a, 'ndim', 0) == 4 for a in x)
-        if arrays:
-            n = x[0].shape[0]
-            if x[1].shape[0] != n:
-                raise ValueError(f'image1 and image2 hold {n} and {x[1].shape[0]} images')
-            bs = int(batch_size) if batch_size else 32
-            if bs < 1:
-                raise ValueError(f'batch_size must be >= 1, got {batch_size}')
-            batches = ((x[0][i:i + bs], x[1][i:i + bs]) for i in range(0, n, bs))
-        else:
-            batches = iter(x)
-        if steps is not None:
-            import itertools
-            batches = itertools.islice(batches, int(steps))
-        batches = ((b[0], b[1]) for b in batches)
+        batches, total = self._pair_batches(x, batch_size, steps)
         down = torch.cuda.Stream(device=dev)
         pins, landing, results = {}, [], []
-        total = n if (arrays and steps is None) else None
         whole, filled = None, 0                  # one preallocated host array when the number of pairs is known
 
         def collect():
@@ -907,11 +829,6 @@ class SmallRAFT(RAFT):
     def _prepare(self, cnet, st):
         check(_dev.lib().raft_prepare_state_small_f32(_dev.ptr(cnet), st.B, st.h, st.w, C.byref(st.c),
                                                       _dev.stream_ptr()), 'prepare_state_small')
-
-    def _iterate(self, corr, st, iters, flow_up, plan=None):
-        check(_dev.lib().raft_iterate_small_f32(C.byref(self.update_block.c), _dev.ptr(corr._pyr), corr._off,
-                                                st.B, st.h, st.w, iters, C.byref(st.c), _dev.ptr(flow_up),
-                                                _dev.stream_ptr()), 'iterate_small')
 
     def _upsample_into(self, st, out):
         check(_dev.lib().raft_upflow8_f32(_dev.ptr(st.flow), st.B, st.h, st.w, _dev.ptr(out),
