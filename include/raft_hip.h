@@ -614,6 +614,26 @@ int raft_iterate_small_f32(const raft_small_update_weights *wts, const float *py
                            const int64_t *level_offsets, int B, int h, int w, int iters,
                            const raft_state *st, float *flow_up, void *stream);
 
+/* ------------------------------------------------------------------ a recurrence that does not start from zero */
+
+/* RAFT's video protocol: the loop of pair t + 1 starts from the low-resolution flow of pair t projected
+ * forward along itself.  flow, out: (B, h, w, 2) floats, [..., 0] = u along x, [..., 1] = v along y, each image on its own.
+ *   raft_forward_interpolate_f32: source j = y0 * w + x0 with vector (dx, dy) ends at x1 = float(x0) + dx, y1 = float(y0) + dy,
+ *     ONE float32 addition each, and is valid iff 0 < x1 < w and 0 < y1 < h (strict; a NaN fails).  out[b, ty, tx] is the vector
+ *     of the valid source that minimises d = (tx - x1) * (tx - x1) + (ty - y1) * (ty - y1), every float32 operation rounded on
+ *     its own (no fused multiply-add), ties to the lowest j; an image without a valid source gives zeros.  Exhaustive search, one
+ *     launch on `stream`, every output element written exactly once.  out must not overlap flow (RAFT_E_UNSUPPORTED).
+ *   raft_warm_start_f32 / raft_warm_start_small_f32: after raft_prepare_state_f32 / raft_prepare_state_small_f32 (and in front of
+ *     the loop), on the state of that variant: coords1 = grid + flow_init (one float32 addition per component), flow =
+ *     flow_init, and the flow channels of the GRU input x (the last two of the 256; channels 144 and 145 of the 160) =
+ *     flow_init -- the three places the loop's first iteration reads a flow from.  One launch; nothing else is written.
+ * RAFT_E_NULL for a NULL pointer (st, st->x, st->coords1, st->flow included); RAFT_E_SHAPE for a non-positive size or B * h * w * 2
+ * of 2^31 or more; RAFT_E_ALIGN for a flow, out, coords1, flow or x that is not 8-byte aligned (float2 accesses).  All checks
+ * precede the launch. */
+int raft_forward_interpolate_f32(const float *flow, int B, int h, int w, float *out, void *stream);
+int raft_warm_start_f32(const float *flow_init, int B, int h, int w, const raft_state *st, void *stream);
+int raft_warm_start_small_f32(const float *flow_init, int B, int h, int w, const raft_state *st, void *stream);
+
 /* ------------------------------------------------------------------ evaluation metrics / loss */
 
 /* Reductions over flow predictions (reference tf_raft/losses/losses.py; the caller side of the forward pass:

@@ -184,6 +184,9 @@ _SIGNATURES = {
     'raft_update_small_f32': (_I, [C.POINTER(SmallUpdateWeights), _I, _I, _I, C.POINTER(State), _P]),
     'raft_iterate_small_f32': (_I, [C.POINTER(SmallUpdateWeights), _P, c_i64_p, _I, _I, _I, _I,
                                     C.POINTER(State), _P, _P]),
+    'raft_forward_interpolate_f32': (_I, [_P, _I, _I, _I, _P, _P]),
+    'raft_warm_start_f32': (_I, [_P, _I, _I, _I, C.POINTER(State), _P]),
+    'raft_warm_start_small_f32': (_I, [_P, _I, _I, _I, C.POINTER(State), _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

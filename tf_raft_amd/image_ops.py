@@ -32,6 +32,9 @@ through the same crop-or-pad window, so a prediction leaves the device as a 3-by
 flow, and the forward-backward test of two flows that marks occluded and out-of-frame pixels, one launch each (``raft_warp_*`` /
 ``raft_flow_consistency_f32``, tf_raft_amd/csrc/flow_check.hip).
 
+``forward_interpolate`` projects a low-resolution flow forward along itself: the start of the next pair's
+recurrence in a video stream (``raft_forward_interpolate_f32``, tf_raft_amd/csrc/flow_init.hip; ``tf_raft_amd.video``).
+
 The model reaches the three ways through ONE object per call (``fit_route``: a ``CropOrPadRoute``, a ``ResizeRoute`` or a
 ``TilePlan``), which answers the same four questions whichever way it is: ``frames_in(t)`` (a frame batch -> the float32 batch
 the model runs on, one launch), ``result_size(B)`` (batch and size of the result for a model batch ``B``), ``flow_back(pred,
@@ -738,3 +741,37 @@ def flow_consistency(flow_forward, flow_backward, alpha=CONSISTENCY_ALPHA, beta=
     b = _flow_like(flow_backward, t.shape[:-1], 'flow_consistency')
     occ_f, occ_b = flow_consistency_launch(f4, b.reshape(f4.shape), alpha, beta)
     return _dev.wrap(occ_f.view(t.shape[:-1])), _dev.wrap(occ_b.view(t.shape[:-1]))
+
+
+# ------------------------------------------------------------------------------------------ forward projection of a flow
+def forward_interpolate_launch(t: torch.Tensor, out=None) -> torch.Tensor:
+    """The launch itself: contiguous float32 device ``(B, h, w, 2)`` -> its forward projection, a new tensor of the same shape
+    (``out`` when given; it must not overlap ``t``) on the CURRENT stream (plain ``torch.Tensor``)."""
+    if t.dim() != 4 or t.shape[-1] != 2:
+        raise ValueError(f'expected a flow (B, h, w, 2), got {tuple(t.shape)}')
+    _check_flow(t, 'forward_interpolate')
+    B, h, w, _ = t.shape
+    out = _check_out(out, (B, h, w, 2), torch.float32, t.device)
+    with torch.cuda.device(t.device):
+        check(_dev.lib().raft_forward_interpolate_f32(_dev.ptr(t), B, h, w, _dev.ptr(out), _dev.stream_ptr()), 'forward_interpolate')
+    return out
+
+
+def forward_interpolate(flow) -> torch.Tensor:
+    """A flow projected forward along itself (the authors' ``forward_interpolate``, the warm start of RAFT's video protocol;
+    DESIGN.md section 16): ``(..., h, w, 2)`` float32 (NumPy or torch, host or device; float64 narrows) -> a contiguous float32
+    device tensor of the same shape.  Per image, the vector at ``(x0, y0)`` travels to ``(x0 + u, y0 + v)``; every cell takes the
+    vector of the nearest end point that lies strictly inside ``(0, w) x (0, h)``, ties to the first source in row-major order,
+    zeros where an image has none.  Float32 throughout, bit for bit the rule in ``include/raft_hip.h``.  One launch on the current
+    stream.  Meant for low-resolution flows: the search is exhaustive, ``(h * w)^2`` candidates per image."""
+    shape = tuple(flow.shape) if hasattr(flow, 'shape') else np.shape(flow)
+    dtype = flow.dtype if hasattr(flow, 'dtype') else np.asarray(flow).dtype
+    if len(shape) < 3 or shape[-1] != 2:
+        raise ValueError(f'forward_interpolate expects a flow (..., h, w, 2), got {shape}')
+    if 0 in shape:
+        raise ValueError(f'empty input {shape}')
+    floats = (torch.float32, torch.float64) if isinstance(dtype, torch.dtype) else (np.dtype(np.float32), np.dtype(np.float64))
+    if dtype not in floats:
+        raise TypeError(f'a flow is float32, got {dtype}')
+    t = _on_device(flow)
+    return _dev.wrap(forward_interpolate_launch(t.reshape((-1,) + shape[-3:])).view(shape))

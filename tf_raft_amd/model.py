@@ -198,25 +198,27 @@ class RAFT:
             return max(self.MIN_SIDE, -(-H // 8) * 8), max(self.MIN_SIDE, -(-W // 8) * 8)
         return self.target_size
 
-    def _fit_frames(self, image1, image2):
-        """``target_size`` set: both frames as float32 device tensors of the model's size, and the call's route between the frames'
-        own size and the model's (``image_ops.fit_route``: crop-or-pad, resize or tiles behind one interface; None when the sizes
-        are equal and nothing was launched).  uint8 frames are cast on their way in, in the same pass; with ``fit='tile'`` each
-        frame becomes its K tiles (batch N * K).  The route's ``flow_back`` takes the predictions to the frames' own size."""
-        image1, image2 = image_ops._on_device(image1), image_ops._on_device(image2)
-        if image1.dim() != 4 or image1.shape[-1] != 3 or image1.shape != image2.shape or image1.dtype != image2.dtype or 0 in image1.shape:
-            raise ValueError(f'images must both be (bs, H, W, 3) of one type, got {tuple(image1.shape)} {image1.dtype} / '
-                             f'{tuple(image2.shape)} {image2.dtype}')
-        H, W = image1.shape[1:3]
+    def _fit_frames(self, *images):
+        """``target_size`` set: the frames of a call (both of a pair; the one new batch of a video stream) as float32 device tensors
+        of the model's size, and the call's route between the frames' own size and the model's (``image_ops.fit_route``:
+        crop-or-pad, resize or tiles behind one interface; None when the sizes are equal and nothing was launched).  uint8 frames
+        are cast on their way in, in the same pass; with ``fit='tile'`` each frame becomes its K tiles (batch N * K).  The route's
+        ``flow_back`` takes the predictions to the frames' own size."""
+        images = [image_ops._on_device(i) for i in images]
+        first = images[0]
+        if first.dim() != 4 or first.shape[-1] != 3 or 0 in first.shape or any(i.shape != first.shape or i.dtype != first.dtype for i in images):
+            raise ValueError('images must %sbe (bs, H, W, 3) of one type, got %s' % ('both ' if len(images) > 1 else '',
+                             ' / '.join(f'{tuple(i.shape)} {i.dtype}' for i in images)))
+        H, W = first.shape[1:3]
         th, tw = self._model_size(H, W)
         if (H, W) == (th, tw):
-            return _dev.to_device(image1), _dev.to_device(image2), None
-        if image1.dtype not in (torch.uint8, torch.float32):
-            image1, image2 = image1.to(torch.float32), image2.to(torch.float32)
+            return (*(_dev.to_device(i) for i in images), None)
+        if first.dtype not in (torch.uint8, torch.float32):
+            images = [i.to(torch.float32) for i in images]
         # both directions' tables are made (the first time: uploaded) here, on the caller's stream: the launch that takes the
         # predictions back, on the loop's stream of a pipelined call, finds everything in place
-        route = image_ops.fit_route(self.fit, image1.device, H, W, th, tw, self.antialias, self.tile_overlap)
-        return route.frames_in(image1), route.frames_in(image2), route
+        route = image_ops.fit_route(self.fit, first.device, H, W, th, tw, self.antialias, self.tile_overlap)
+        return (*(route.frames_in(i) for i in images), route)
 
     def _build(self, weights):
         self.fnet = BasicEncoder(output_dim=256, norm_type='instance', drop_rate=self.drop_rate,
@@ -299,6 +301,9 @@ class RAFT:
         check(_dev.lib().raft_prepare_state_f32(_dev.ptr(cnet), st.B, st.h, st.w, C.byref(st.c),
                                                 _dev.stream_ptr()), 'prepare_state')
         self.update_block.prepare(st)          # GRU terms of `inp`: constant over the loop (model.py:86)
+
+    def _warm_start(self, flow_init, st):
+        check(_dev.lib().raft_warm_start_f32(_dev.ptr(flow_init), st.B, st.h, st.w, C.byref(st.c), _dev.stream_ptr()), 'warm_start')
 
     def _lane(self, dev, index) -> Lane:
         lane = self._open_lanes.get(index)
@@ -384,13 +389,17 @@ class RAFT:
     # overwrite, exists D + 1 times (schedule.RingSlot).  Each call still runs exactly the kernels of the serial schedule in the
     # same order on its own buffers: results are bit-identical per call
     # (tests/test_gpu_model.py::test_pipelined_calls_are_bitwise_the_serial_calls).
-    def _forward(self, inputs, training=False, final_only=False, pipelined=None, mirror=False):
+    def _forward(self, inputs, training=False, final_only=False, pipelined=None, mirror=False, video=None):
         """``mirror`` (inference, serial schedule): ONE pass over the 2B pairs [(image1, image2) | (image2, image1)] with the
-        feature encoder run once per frame; the result has batch 2B, the second half the backward direction."""
+        feature encoder run once per frame; the result has batch 2B, the second half the backward direction.  ``video`` (inference,
+        serial schedule): the call of a ``tf_raft_amd.video.FlowVideo``, whose frames arrive fitted (``video.route``), whose first
+        feature map is carried from the stream's previous call and whose loop may start from ``video.flow_init``."""
         self._sync_inference_weights()
         image1, image2 = inputs
         route = None
-        if self.target_size is not None and not training:
+        if video is not None:
+            route = video.route                         # (the stream fitted each frame once, when it arrived)
+        elif self.target_size is not None and not training:
             image1, image2, route = self._fit_frames(image1, image2)
         image1 = _dev.to_device(image1)
         image2 = _dev.to_device(image2)
@@ -421,7 +430,8 @@ class RAFT:
                 # next to them (its one-workgroup-per-CU layers fill the tails of the feature encoder's launches)
                 context_stream = _dev.side_stream(dev, 'encoder')
         with _hinted(plan.pre_hint):                    # (the loop's own hint inside; the thread's is restored on the way out)
-            return self._run(image1, image2, training, final_only, mirror and not training, plan, route, slot, context_stream, loop_stream)
+            return self._run(image1, image2, training, final_only, mirror and not training, plan, route, slot, context_stream, loop_stream,
+                             video)
 
     def _plan(self, lane, three_stream, hint):
         """The loop plan of one call.  ``hint`` is the number of loops that share the chip: the lanes of a pipelined call,
@@ -430,9 +440,10 @@ class RAFT:
         return LoopPlan(lane, three_stream, hint if (hint > 1 and self._shape_hint == 'all') else None,
                         hint if self._shape_hint in ('loop', 'all') else 1)
 
-    def _run(self, image1, image2, training, final_only, mirror, plan, route, slot, context_stream, loop_stream):
+    def _run(self, image1, image2, training, final_only, mirror, plan, route, slot, context_stream, loop_stream, video=None):
         """The forward pass of both schedules.  ``slot`` / ``loop_stream``: the ring slot and the lane's loop stream of a pipelined
-        call; ``context_stream``: the side stream of the context encoder; None = the caller's stream, the serial state."""
+        call; ``context_stream``: the side stream of the context encoder; None = the caller's stream, the serial state.
+        ``video``: the stream whose call this is (None: a call on a pair)."""
         B, H, W, _ = image1.shape
         dev = image1.device
         cur = torch.cuda.current_stream(dev)
@@ -456,6 +467,8 @@ class RAFT:
             else:
                 cnet = self.cnet(image1, training=training, _raw_images=True)             # model.py:82
             self._prepare(cnet, st)                                                       # model.py:84-89
+            if video is not None and video.flow_init is not None:
+                self._warm_start(video.flow_init, st)      # coords1 = grid + init: behind the preparation, on its stream
             return cnet
 
         if context_stream is not None:
@@ -471,6 +484,10 @@ class RAFT:
             # the encoder's output (B, h, w, C) over [image1 | image2] IS the first operand; the second is its halves swapped
             fmap1 = self.fnet.forward_device(image1, input_affine=True, images_b=image2)
             fmap2 = torch.cat([fmap1[B // 2:], fmap1[:B // 2]], dim=0)
+        elif video is not None:
+            # fnet on the NEW frames alone (image2), beside the context encoder as ever; the first operand is what the stream
+            # carried from its previous call, and the new map is what it carries on
+            fmap1, fmap2 = video.feature_maps(self.fnet.forward_device(image2, input_affine=True))
         else:
             fmap1, fmap2 = self.fnet([image1, image2], training=training, _raw_images=True)   # model.py:74
         correlation = CorrBlock(fmap1, fmap2, num_levels=self.corr_levels, radius=self.corr_radius,
@@ -582,6 +599,19 @@ class RAFT:
         if not parts[0]:
             raise ValueError('predict_bidirectional() received no batches')
         return BidirectionalFlow(*(np.concatenate(acc, axis=0) for acc in parts))
+
+    def video(self, warm_start=False):
+        """A stream of consecutive frames (``tf_raft_amd.video.FlowVideo``): ``push(frames)`` returns the flow from the previous
+        frames to these, with the feature encoder run once per frame; ``warm_start=True`` starts every pair's recurrence from the
+        previous pair's flow projected forward (RAFT's video protocol).  Serial schedule, on the caller's stream."""
+        from .video import FlowVideo
+        return FlowVideo(self, warm_start)
+
+    def predict_video(self, frames, warm_start=False, batch_size=None, steps=None):
+        """The flows between the consecutive frames of one video ``(T, H, W, 3)`` as a host array ``(T - 1, H, W, 2)``
+        (``tf_raft_amd.video.predict_video``)."""
+        from .video import predict_video
+        return predict_video(self, frames, warm_start, batch_size, steps)
 
     def predict(self, x, batch_size=None, steps=None, output='flow', clip_flow=None, convert_to_bgr=False, rad_max=None, **kwargs):
         """``keras.Model.predict`` over ``predict_step`` (reference model.py:160-166): the final flow of every image
@@ -829,6 +859,9 @@ class SmallRAFT(RAFT):
     def _prepare(self, cnet, st):
         check(_dev.lib().raft_prepare_state_small_f32(_dev.ptr(cnet), st.B, st.h, st.w, C.byref(st.c),
                                                       _dev.stream_ptr()), 'prepare_state_small')
+
+    def _warm_start(self, flow_init, st):
+        check(_dev.lib().raft_warm_start_small_f32(_dev.ptr(flow_init), st.B, st.h, st.w, C.byref(st.c), _dev.stream_ptr()), 'warm_start_small')
 
     def _upsample_into(self, st, out):
         check(_dev.lib().raft_upflow8_f32(_dev.ptr(st.flow), st.B, st.h, st.w, _dev.ptr(out),

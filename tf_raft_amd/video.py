@@ -1,0 +1,138 @@
+"""Flow over frame sequences: every frame encoded once, and RAFT's warm start.
+
+In footage frame ``t`` is ``image2`` of one pair and ``image1`` of the next.  A ``FlowVideo`` (``model.video()``) keeps, between
+its calls, what the next pair needs of the previous frame: the frame itself at the model's size (the context encoder reads it)
+and its feature map (the first operand of the correlation volume), so the feature encoder runs on the new frames alone.  With
+``warm_start=True`` it also keeps the low-resolution flow the loop ended on and starts the next pair's recurrence from its forward
+projection (``image_ops.forward_interpolate``, the authors' video protocol) instead of from zero.
+
+A call is the final-prediction forward pass of ``predict_step`` on the serial schedule on the caller's stream; the stream object
+is the ``video`` argument of ``RAFT._run``, which asks it for the two feature maps and the initial flow and leaves everything from
+the correlation volume on as it is.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _dev
+from . import image_ops
+
+
+class FlowVideo:
+    """``model.video(warm_start=False)``: ``push(frames)`` takes one frame ``(N, H, W, 3)`` of each of N independent videos (uint8
+    or float, host or device) and returns the flow from the previous frames to these, ``(N, H, W, 2)`` at the frames' own size
+    (None after the first push).  ``flow_low`` is the model-space 1/8 flow the last loop ended on, ``(N', h, w, 2)`` with
+    ``N' = N * tiles`` under ``fit='tile'``; ``reset()`` forgets the stream (and accepts another frame shape)."""
+
+    def __init__(self, model, warm_start=False):
+        self.model = model
+        self.warm_start = bool(warm_start)
+        self.reset()
+
+    def reset(self):
+        self._signature = None                  # (N, H, W, dtype) of a time step
+        self._frame = self._fmap = None         # the carry: the last time step at the model's size, and its feature map
+        self.flow_low = None
+        self.route = self.flow_init = None      # of the call in flight (read by RAFT._forward / _run)
+
+    def push(self, frames, flow_init=None):
+        """The next frame of every video.  ``flow_init``: an explicit model-space start of the recurrence ``(N', h, w, 2)`` in
+        place of the propagated one (also without ``warm_start``)."""
+        return self._step(frames, 1, flow_init)
+
+    # ---- what RAFT._run asks
+    def feature_maps(self, new):
+        """``(fmap1, fmap2)`` of the call from the feature map of its new frames, which holds ``steps`` time steps of ``k`` maps:
+        the first operand is the carried map followed by all but the last step, and the last step is carried on."""
+        k = self._fmap.shape[0]
+        fmap1 = self._fmap if new.shape[0] == k else torch.cat([self._fmap, new[:-k]], dim=0)
+        self._fmap = new[-k:]
+        return fmap1, new
+
+    # ---- one call: `steps` consecutive time steps of N frames each (push: one; the chunks of predict_video: N = 1)
+    def _step(self, frames, steps, flow_init=None):
+        m = self.model
+        shape = tuple(frames.shape) if hasattr(frames, 'shape') else np.shape(frames)
+        dtype = frames.dtype if hasattr(frames, 'dtype') else np.asarray(frames).dtype
+        if len(shape) != 4 or shape[-1] != 3 or 0 in shape or shape[0] % steps:
+            raise ValueError(f'frames must be (N, H, W, 3), got {shape}')
+        signature = (shape[0] // steps,) + shape[1:3] + (str(dtype).replace('torch.', ''),)
+        if self._signature is not None and signature != self._signature:
+            raise ValueError(f'this stream holds frames (N, H, W, type) = {self._signature}, got {signature}: reset() it first')
+        if m.target_size is not None:
+            frame, route = m._fit_frames(frames)
+        else:
+            frame, route = _dev.to_device(frames), None
+            if frame.shape[1] % 8 or frame.shape[2] % 8:
+                raise ValueError(f'H and W must be multiples of 8 (got {frame.shape[1]}x{frame.shape[2]})')
+        k = frame.shape[0] // steps                      # model-space rows of a time step (N, or N * tiles)
+        if self._frame is None:
+            # the first time step: nothing to pair it with.  Encoded here, as a later call encodes its new frames
+            if steps != 1:
+                raise ValueError('the first call of a stream takes one time step')
+            if flow_init is not None:
+                raise ValueError('flow_init belongs to a pair: the first push has none')
+            m._sync_inference_weights()
+            m._join_pipeline()
+            self._signature, self._frame = signature, frame
+            self._fmap = m.fnet.forward_device(frame, input_affine=True)
+            return None
+        if flow_init is not None:
+            init = self._check_init(flow_init, frame)
+        elif self.warm_start and self.flow_low is not None:
+            # into a buffer of its own, in front of the state preparation that overwrites the state
+            init = image_ops.forward_interpolate_launch(self.flow_low)
+        else:
+            init = None
+        image1 = self._frame if steps == 1 else torch.cat([self._frame, frame[:-k]], dim=0)
+        self.route, self.flow_init = route, init
+        try:
+            flow = m._predict_final(image1, frame, pipelined=False, video=self)
+        finally:
+            self.route = self.flow_init = None
+        self._frame = frame[-k:]
+        # (a copy: the state is the model's, and its next call of any kind overwrites it)
+        self.flow_low = m._state.flow.clone()
+        return flow
+
+    @staticmethod
+    def _check_init(flow_init, frame):
+        t = image_ops._on_device(flow_init)
+        want = (frame.shape[0], frame.shape[1] // 8, frame.shape[2] // 8, 2)
+        if tuple(t.shape) != want or t.dtype != torch.float32 or t.device != frame.device:
+            raise ValueError(f'flow_init must be a float32 flow {want} in model space, got {tuple(t.shape)} {t.dtype}')
+        return t
+
+
+def predict_video(model, frames, warm_start=False, batch_size=None, steps=None):
+    """``RAFT.predict_video``: the flows between the consecutive frames of ONE video ``(T, H, W, 3)``, host or device, as a host
+    array ``(T - 1, H, W, 2)``.  ``warm_start=True`` pushes frame by frame (pair t + 1 starts from pair t's flow: the dependency
+    is real); otherwise ``batch_size`` consecutive pairs (default 4) run per call, the feature encoder on the ``batch_size`` new
+    frames of the chunk.  ``steps`` limits the number of calls.  Host frames are uploaded one chunk ahead of the compute stream
+    (``tf_raft_amd.prefetch``); every call's flows are copied back synchronously."""
+    from .prefetch import prefetch_to_device
+    shape = tuple(frames.shape) if hasattr(frames, 'shape') else np.shape(frames)
+    if len(shape) != 4 or shape[-1] != 3:
+        raise ValueError(f'frames must be one video (T, H, W, 3), got {shape}')
+    T = shape[0]
+    if T < 2:
+        raise ValueError(f'a video needs at least two frames, got T = {T}')
+    bs = 1 if warm_start else (int(batch_size) if batch_size else 4)
+    if bs < 1:
+        raise ValueError(f'batch_size must be >= 1, got {batch_size}')
+    dev = _dev.require_gpu()
+    starts = list(range(1, T, bs))
+    if steps is not None:
+        starts = starts[:int(steps)]
+    # (prefetch_to_device takes batches that are tuples of arrays)
+    chunks = ((frames[a:b],) for a, b in [(0, 1)] + [(s, min(s + bs, T)) for s in starts])
+    video = FlowVideo(model, warm_start)
+    flows = []
+    for (chunk,) in prefetch_to_device(chunks, buffer_size=1, device=dev):
+        flow = video._step(chunk, chunk.shape[0])
+        if flow is not None:
+            flows.append(flow.as_subclass(torch.Tensor).cpu().numpy())
+    if not flows:
+        raise ValueError('predict_video() ran no pair')
+    return np.concatenate(flows, axis=0)
