@@ -665,6 +665,32 @@ int raft_sequence_loss_grad_f32(const float *flow_gt, const unsigned char *valid
                                 int64_t pred_stride, int n_predictions, int64_t npix, double gamma, float max_flow,
                                 float upstream, float *d_preds, void *stream);
 
+/* Self-supervised sequence loss and its gradient in ONE launch (no reference counterpart).
+ *   image1, image2 (B, H, W, 3) float in 0..255; mask NULL (all ones) or uint8 (B, H, W), nonzero = use the pixel;
+ *   preds: n_predictions flows (B, H, W, 2), prediction i at preds + i * pred_stride (floats).
+ * With s = 1/255, rho(d) = sqrtf(d*d + eps*eps) (eps*eps rounded once to float32), w_i = (float)gamma^(n-i-1) built on the host
+ * as raft_sequence_loss_f32 builds it, W2 = image2 sampled at the pixel's sample position under p_i exactly as raft_warp_f32
+ * samples (same position, in-frame test `inside`, taps and weights a, b):
+ *   ph_i = sum mask * inside * rho(s * (W2_c - image1_c)) / (B*H*W*3)          (the divisor counts ALL elements)
+ *   wx(x,y) = expf(-edge_weight * mean_c |s * (image1(x+1,y)_c - image1(x,y)_c)|) for x < W-1, wy likewise along y
+ *   sm_i = [sum wx * rho(p(x+1,y)_k - p(x,y)_k) + sum wy * rho(p(x,y+1)_k - p(x,y)_k)] / (B*H*W*2), k in {u, v}
+ *   loss = sum_i w_i * (ph_i + smooth_weight * sm_i);      out3 = {loss, ph_{n-1}, sm_{n-1}}
+ * d_preds: NULL (value only), or the layout of preds; d_preds_i = upstream * w_i * (d ph_i + smooth_weight * d sm_i), every
+ * element written exactly once (gaps of a pred_stride larger than 2*B*H*W are not touched).  mask and inside are constants of
+ * the gradient; dW2_c/du = (1-b)*(g01-g00) + b*(g11-g10), dW2_c/dv = (1-a)*(g10-g00) + a*(g11-g01), the one-sided derivative of
+ * the cell the taps come from; the smoothness gradient is the adjoint as a gather, missing neighbours dropped.
+ * Deterministic (no atomics, no memset): float64 partial records in `workspace` (raft_photometric_loss_workspace_doubles()
+ * doubles), added in index order by a second one-workgroup launch.
+ * RAFT_E_NULL: image1, image2, preds, out3 or workspace NULL.  RAFT_E_SHAPE: a non-positive size, pred_stride < 2*B*H*W,
+ * B*H*W*3 of 2^31 or more, eps or eps*eps (in float32) not positive and finite, gamma / smooth_weight / edge_weight negative or not finite, upstream
+ * not finite.  RAFT_E_UNSUPPORTED: n_predictions > 64 or an odd pred_stride.  RAFT_E_ALIGN: preds, d_preds or workspace not
+ * 8-byte aligned.  All checks precede the first launch. */
+int64_t raft_photometric_loss_workspace_doubles(void);
+int raft_photometric_loss_f32(const float *image1, const float *image2, const uint8_t *mask, const float *preds,
+                              int64_t pred_stride, int n_predictions, int B, int H, int W, double gamma, float smooth_weight,
+                              float edge_weight, float eps, float upstream, float *out3, float *d_preds, double *workspace,
+                              void *stream);
+
 /* Backward of raft_corr_lookup_f32 (CorrBlock.retrieve + bilinear_sampler, corr.py:116-152, 28-69), with TensorFlow's
  * gradient conventions: floor / ceil contribute nothing, clip_by_value passes the gradient on [0, size - 1].
  * d_out: (B, h, w, ld_out) upstream gradient of the lookup output (first levels*(2r+1)^2 channels used).

@@ -120,6 +120,9 @@ _SIGNATURES = {
     'raft_flow_metrics_f32': (_I, [_P, _P, _P, C.c_int64, C.c_float, _P, _P, _P]),
     'raft_sequence_loss_f32': (_I, [_P, _P, _P, C.c_int64, _I, C.c_int64, C.c_double, C.c_float, _P, _P, _P]),
     'raft_sequence_loss_grad_f32': (_I, [_P, _P, _P, C.c_int64, _I, C.c_int64, C.c_double, C.c_float, C.c_float, _P, _P]),
+    'raft_photometric_loss_workspace_doubles': (C.c_int64, []),
+    'raft_photometric_loss_f32': (_I, [_P, _P, _P, _P, C.c_int64, _I, _I, _I, _I, C.c_double, C.c_float, C.c_float, C.c_float,
+                                       C.c_float, _P, _P, _P, _P]),
     'raft_corr_lookup_backward_f32': (_I, [_P, c_i64_p, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     'raft_relu_backward_f32': (_I, [_P, _P, _P, C.c_int64, _P]),
     'raft_pack_train_conv_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_double), _I, _I, _I, _P, _P, _P]),

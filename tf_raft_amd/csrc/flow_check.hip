@@ -24,33 +24,11 @@
 
 #pragma clang fp contract(off)
 
+#include "flow_sample.h"      // Taps, flow_taps, bilinear: shared with photometric_loss.hip
+
 namespace {
 
 constexpr int kFlowCheckThreads = 256;
-
-struct Taps {
-    int o00, o01, o10, o11;      // pixel offsets inside one image
-    float a, b;
-    bool in;
-};
-
-__device__ __forceinline__ Taps flow_taps(int x, int y, float2 f, int H, int W) {
-    const float sx = (float)x + f.x, sy = (float)y + f.y;
-    Taps t;
-    t.in = sx >= 0.f && sx <= (float)(W - 1) && sy >= 0.f && sy <= (float)(H - 1);
-    const float px = t.in ? sx : 0.f, py = t.in ? sy : 0.f;
-    const float fx = floorf(px), fy = floorf(py);
-    const int x0 = min(max((int)fx, 0), W - 1), y0 = min(max((int)fy, 0), H - 1);
-    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-    t.a = px - fx, t.b = py - fy;
-    t.o00 = y0 * W + x0, t.o01 = y0 * W + x1, t.o10 = y1 * W + x0, t.o11 = y1 * W + x1;
-    return t;
-}
-
-__device__ __forceinline__ float bilinear(const Taps &t, float g00, float g01, float g10, float g11) {
-    const float na = 1.f - t.a, nb = 1.f - t.b;
-    return nb * (na * g00 + t.a * g01) + t.b * (na * g10 + t.a * g11);
-}
 
 // CT > 0: the channel count at compile time (the taps of all channels are issued together); CT == 0: any C
 template <typename S, int CT>

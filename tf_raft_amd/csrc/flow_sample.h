@@ -1,0 +1,43 @@
+// The one definition of "the sample of a map under a flow vector" (DESIGN.md sections 15 and 17), shared by flow_check.hip (warp,
+// forward-backward consistency) and photometric_loss.hip (the self-supervised loss and its gradient).
+//
+// For the pixel at integer (x, y) with vector (u, v): sx = float(x) + u and sy = float(y) + v, ONE float32 addition each; the
+// pixel is in frame iff 0 <= sx <= W - 1 and 0 <= sy <= H - 1 (a NaN fails); x0 = floor(sx), x1 = min(x0 + 1, W - 1),
+// a = sx - x0 (exact), likewise y0, y1, b, and the value is
+//     (1 - b) * ((1 - a) * g[y0, x0] + a * g[y0, x1]) + b * ((1 - a) * g[y1, x0] + a * g[y1, x1])
+// with every product and sum rounded on its own: a file that includes this header switches contraction off
+// (#pragma clang fp contract(off) at file scope, before its first function).  Tap indices are clamped into the frame whatever
+// the flow holds.
+#pragma once
+
+#include "common.h"
+
+namespace {
+
+struct Taps {
+    int o00, o01, o10, o11;      // pixel offsets inside one image
+    float a, b;
+    bool in;
+};
+
+__device__ __forceinline__ Taps flow_taps(int x, int y, float2 f, int H, int W) {
+#pragma clang fp contract(off)
+    const float sx = (float)x + f.x, sy = (float)y + f.y;
+    Taps t;
+    t.in = sx >= 0.f && sx <= (float)(W - 1) && sy >= 0.f && sy <= (float)(H - 1);
+    const float px = t.in ? sx : 0.f, py = t.in ? sy : 0.f;
+    const float fx = floorf(px), fy = floorf(py);
+    const int x0 = min(max((int)fx, 0), W - 1), y0 = min(max((int)fy, 0), H - 1);
+    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
+    t.a = px - fx, t.b = py - fy;
+    t.o00 = y0 * W + x0, t.o01 = y0 * W + x1, t.o10 = y1 * W + x0, t.o11 = y1 * W + x1;
+    return t;
+}
+
+__device__ __forceinline__ float bilinear(const Taps &t, float g00, float g01, float g10, float g11) {
+#pragma clang fp contract(off)
+    const float na = 1.f - t.a, nb = 1.f - t.b;
+    return nb * (na * g00 + t.a * g01) + t.b * (na * g10 + t.a * g11);
+}
+
+}   // namespace

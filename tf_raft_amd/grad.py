@@ -228,6 +228,21 @@ def sequence_loss_grad(y_true, y_pred, gamma=0.8, max_flow=400, upstream=1.0):
     return [_dev.wrap(out[i]) for i in range(n)]
 
 
+def photometric_sequence_loss_value_and_grad(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, upstream=1.0):
+    """``(terms, grads)`` of ``losses.PhotometricSequenceLoss`` from ONE launch: ``terms`` is
+    ``{'loss', 'photometric', 'smoothness'}`` and ``grads[i]`` = ``upstream * d loss / d y_pred[i]``, shaped like the predictions.
+    ``y_true = (image1, image2)`` or ``(image1, image2, mask)``."""
+    from . import losses
+    out, d = losses._photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, upstream=upstream, want_grad=True)
+    return losses._photometric_terms(out), [] if d is None else [_dev.wrap(d[i]) for i in range(d.shape[0])]
+
+
+def photometric_sequence_loss_grad(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, upstream=1.0):
+    """``upstream * d PhotometricSequenceLoss(...)(y_true, y_pred) / d y_pred[i]`` for every i: list of tensors shaped like the
+    predictions."""
+    return photometric_sequence_loss_value_and_grad(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, upstream)[1]
+
+
 def corr_lookup_backward(corr_block, coords, d_out, d_pyramid=None, want_pyramid_grad=True):
     """Backward of ``corr_block.retrieve(coords)`` (reference corr.py:116-152) for the upstream gradient ``d_out``
     (bs, h, w, levels*(2r+1)^2).  Returns ``(d_coords, d_pyramid)``: ``d_coords`` (bs, h, w, 2) and the gradient w.r.t.

@@ -4,6 +4,11 @@
     end_point_error(y_true, y_pred, max_flow=400)                 losses.py:24-43
     EndPointError(max_flow=400)                                   losses.py:46-90
 
+and the self-supervised loss the reference does not have (csrc/photometric_loss.hip):
+
+    PhotometricSequenceLoss(gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01)
+    photometric_sequence_loss(y_true, y_pred, ...)                y_true = (image1, image2) or (image1, image2, mask)
+
 ``y_true = (flow_gt, valid)`` with ``flow_gt`` (bs, H, W, 2) float and ``valid`` (bs, H, W) bool; ``y_pred`` is the list
 of flow predictions the model returns (``sequence_loss``) or one prediction (``end_point_error``).  Arrays may be
 NumPy or torch, host or device.  The reductions run as single-pass HIP kernels (csrc/metrics.hip) on the current
@@ -11,6 +16,8 @@ stream; results are 0-d fp32 device tensors that answer ``.numpy()`` / ``float()
 CPU fallback.
 """
 from __future__ import annotations
+
+import math
 
 import torch
 
@@ -71,6 +78,153 @@ def sequence_loss(y_true, y_pred, gamma=0.8, max_flow=400):
                                             float(gamma), float(max_flow), _dev.ptr(out), _dev.ptr(_workspace(out.device)),
                                             _dev.stream_ptr()), 'sequence_loss')
     return _dev.wrap(out)
+
+
+# ---------------------------------------------------------------- self-supervised: photometric + smoothness
+_F32_MAX = 3.402823466e38
+_PHOTOMETRIC_WS = {}
+
+
+def _photometric_workspace(device):
+    key = (device.type, device.index)
+    ws = _PHOTOMETRIC_WS.get(key)
+    if ws is None:
+        ws = torch.empty((int(_dev.lib().raft_photometric_loss_workspace_doubles()),), dtype=torch.float64, device=device)
+        _PHOTOMETRIC_WS[key] = ws
+    return ws
+
+
+def _real(name, v):
+    if isinstance(v, bool) or isinstance(v, (str, bytes, complex)):
+        raise ValueError(f'{name} must be a real number, got {v!r}')
+    try:
+        return float(v)
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f'{name} must be a real number, got {v!r}') from exc
+
+
+def _photometric_params(gamma, smooth_weight, edge_weight, eps, upstream=1.0):
+    """The checks raft_photometric_loss_f32 makes on its parameters: finite non-negative weights, ``eps > 0``, finite upstream."""
+    out = []
+    for name, v in (('gamma', gamma), ('smooth_weight', smooth_weight), ('edge_weight', edge_weight)):
+        v = _real(name, v)
+        if not 0.0 <= v <= _F32_MAX:
+            raise ValueError(f'{name} must be finite and >= 0, got {v!r}')
+        out.append(v)
+    eps = _real('eps', eps)
+    eps2 = float(torch.tensor(eps, dtype=torch.float32) ** 2) if 0.0 < eps <= _F32_MAX else 0.0
+    if not 0.0 < eps2 <= _F32_MAX:
+        raise ValueError(f'eps and eps * eps must be finite and > 0 in float32, got {eps!r}')
+    upstream = _real('upstream', upstream)
+    if not math.isfinite(upstream) or abs(upstream) > _F32_MAX:
+        raise ValueError(f'upstream must be finite, got {upstream!r}')
+    return (*out, eps, upstream)
+
+
+def _shape_of(x):
+    shape = getattr(x, 'shape', None)
+    if shape is None:
+        import numpy as np
+        shape = np.shape(x)
+    return tuple(int(d) for d in shape)
+
+
+def _check_unlabelled(y_true, y_pred):
+    """Shapes of ``(image1, image2[, mask])`` and of the predictions, checked BEFORE anything moves to the device.  Returns
+    ``(image1, image2, mask or None, (B, H, W))``."""
+    try:
+        items = tuple(y_true)
+    except TypeError as exc:
+        raise ValueError('y_true must be (image1, image2) or (image1, image2, mask)') from exc
+    if len(items) not in (2, 3):
+        raise ValueError(f'y_true must be (image1, image2) or (image1, image2, mask), got {len(items)} items')
+    image1, image2 = items[0], items[1]
+    mask = items[2] if len(items) == 3 else None
+    s1 = _shape_of(image1)
+    if len(s1) != 4 or s1[-1] != 3 or min(s1) < 1:
+        raise ValueError(f'image1 must be (B, H, W, 3), got {s1}')
+    if _shape_of(image2) != s1:
+        raise ValueError(f'image2 must be {s1}, got {_shape_of(image2)}')
+    if mask is not None and _shape_of(mask) != s1[:3]:
+        raise ValueError(f'mask must be {s1[:3]}, got {_shape_of(mask)}')
+    if s1[0] * s1[1] * s1[2] * 3 >= 2 ** 31:
+        raise ValueError(f'B*H*W*3 must stay below 2^31, got {s1}')
+    preds = list(y_pred)
+    if len(preds) > 64:
+        raise ValueError(f'at most 64 predictions, got {len(preds)}')
+    want = s1[:3] + (2,)
+    for p in preds:
+        if _shape_of(p) != want:
+            raise ValueError(f'prediction must be {want}, got {_shape_of(p)}')
+    return image1, image2, mask, preds, s1[:3]
+
+
+def _mask_to_device(mask, device):
+    """nonzero = use the pixel -> contiguous uint8 0/1 on ``device``."""
+    mask = mask.as_subclass(torch.Tensor) if isinstance(mask, torch.Tensor) else torch.as_tensor(mask)
+    if mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous():
+        return mask                                 # the kernel tests != 0 itself
+    return (mask != 0).to(device=device, dtype=torch.uint8).contiguous()
+
+
+def _photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, upstream=1.0, want_grad=False):
+    """One raft_photometric_loss_f32 call: ``(out3, d_preds)`` -- out3 = device ``[loss, photometric, smoothness]`` (the last
+    two of the LAST prediction), d_preds the stacked gradients ``(n, B, H, W, 2)`` or None."""
+    gamma, smooth_weight, edge_weight, eps, upstream = _photometric_params(gamma, smooth_weight, edge_weight, eps, upstream)
+    image1, image2, mask, preds, (B, H, W) = _check_unlabelled(y_true, y_pred)
+    image1 = _dev.to_device(image1).as_subclass(torch.Tensor)
+    image2 = _dev.to_device(image2).as_subclass(torch.Tensor)
+    if mask is not None:
+        mask = _mask_to_device(mask, image1.device)
+    n = len(preds)
+    out = torch.zeros((3,), dtype=torch.float32, device=image1.device)
+    if n == 0:
+        return out, None
+    preds = [_dev.to_device(p).as_subclass(torch.Tensor).to(torch.float32) for p in preds]
+    # the model returns views of one (iters, bs, H, W, 2) buffer: use it in place, otherwise gather the list once
+    stride = B * H * W * 2
+    base = preds[0]
+    in_place = all(p.is_contiguous() and p.data_ptr() == base.data_ptr() + 4 * stride * i for i, p in enumerate(preds))
+    stacked = base if in_place else torch.stack([p.contiguous() for p in preds])
+    d_preds = torch.empty((n, B, H, W, 2), dtype=torch.float32, device=image1.device) if want_grad else None
+    check(_dev.lib().raft_photometric_loss_f32(_dev.ptr(image1), _dev.ptr(image2), _dev.ptr(mask) if mask is not None else None,
+                                               _dev.ptr(stacked), stride, n, B, H, W, gamma, smooth_weight, edge_weight, eps,
+                                               upstream, _dev.ptr(out), _dev.ptr(d_preds) if want_grad else None,
+                                               _dev.ptr(_photometric_workspace(out.device)), _dev.stream_ptr()),
+          'photometric_loss')
+    return out, d_preds
+
+
+def _photometric_terms(out):
+    return {k: _dev.wrap(out[i]) for i, k in enumerate(('loss', 'photometric', 'smoothness'))}
+
+
+class PhotometricSequenceLoss:
+    """Self-supervised sequence loss: ``sum_i gamma**(n-i-1) * (ph_i + smooth_weight * sm_i)`` with
+    ``ph_i`` the Charbonnier difference between frame 1 and frame 2 sampled under prediction i (over the pixels that are in
+    frame and, if given, in ``mask``) and ``sm_i`` the edge-aware first-order smoothness of prediction i.
+    ``y_true = (image1, image2)`` or ``(image1, image2, mask)``: images ``(B, H, W, 3)`` in 0..255, ``mask`` ``(B, H, W)``,
+    nonzero = use the pixel (e.g. ``predict_step_bidirectional(...).occluded_forward == 0``).
+    ``smooth_weight``, ``edge_weight`` and ``eps`` are choices, not tuned values.  ``RAFT.compile(loss=PhotometricSequenceLoss())``
+    makes ``train_step`` take unlabelled pairs."""
+
+    def __init__(self, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01):
+        self.gamma, self.smooth_weight, self.edge_weight, self.eps, _ = _photometric_params(gamma, smooth_weight, edge_weight, eps)
+
+    def _params(self):
+        return dict(gamma=self.gamma, smooth_weight=self.smooth_weight, edge_weight=self.edge_weight, eps=self.eps)
+
+    def terms(self, y_true, y_pred):
+        """``{'loss', 'photometric', 'smoothness'}``: the loss, and the two terms of the LAST prediction (0-d device scalars)."""
+        return _photometric_terms(_photometric_launch(y_true, y_pred, **self._params())[0])
+
+    def __call__(self, y_true, y_pred):
+        return self.terms(y_true, y_pred)['loss']
+
+
+def photometric_sequence_loss(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01):
+    """``PhotometricSequenceLoss(gamma, smooth_weight, edge_weight, eps)(y_true, y_pred)``."""
+    return PhotometricSequenceLoss(gamma, smooth_weight, edge_weight, eps)(y_true, y_pred)
 
 
 def _metrics(y_true, y_pred, max_flow):

@@ -679,8 +679,11 @@ class RAFT:
     # ---- evaluation plumbing (reference model.py:111-170)
     def compile(self, optimizer=None, clip_norm=None, loss=None, epe=None, trainable='all', tape_dtype='f32', **kwargs):
         """reference model.py:111-124.  ``loss`` / ``epe`` default to ``tf_raft_amd.losses.sequence_loss`` /
-        ``end_point_error``.  ``trainable``: which weights ``train_step`` updates -- ``'all'`` (the reference's behaviour:
-        encoders, norms and update block) or ``'update_block'`` (encoders frozen, run by the inference kernels)."""
+        ``end_point_error``; ``loss=losses.PhotometricSequenceLoss(...)`` makes ``train_step`` take unlabelled pairs
+        ``(image1, image2)`` or ``(image1, image2, mask)`` and report ``loss`` / ``photometric`` / ``smoothness`` (DESIGN.md
+        section 17; ``test_step`` still wants ground truth).  ``trainable``: which weights ``train_step`` updates -- ``'all'``
+        (the reference's behaviour: encoders, norms and update block) or ``'update_block'`` (encoders frozen, run by the
+        inference kernels)."""
         from . import losses
         if kwargs:
             raise TypeError(f'unexpected keyword arguments {sorted(kwargs)}')
@@ -696,6 +699,8 @@ class RAFT:
         self._train_vars = None
         self.tape_dtype = tape_dtype
         self.flow_metrics = OrderedDict((k, losses.Mean(name=k)) for k in ('loss', 'epe', 'u1', 'u3', 'u5'))
+        if isinstance(self.loss, losses.PhotometricSequenceLoss):       # (the EPE means stay: test_step feeds them)
+            self.flow_metrics.update((k, losses.Mean(name=k)) for k in ('photometric', 'smoothness'))
 
     BN_MOMENTUM = 0.99      # Keras BatchNormalization default (extractor.py:10 passes none)
 
@@ -711,19 +716,33 @@ class RAFT:
         from . import grad, losses
         if not hasattr(self, 'flow_metrics'):
             raise RuntimeError('call compile() before train_step()')
-        if self.loss is not losses.sequence_loss:
-            raise NotImplementedError('train_step differentiates tf_raft_amd.losses.sequence_loss only')
+        photometric = isinstance(self.loss, losses.PhotometricSequenceLoss)
+        if not photometric and self.loss is not losses.sequence_loss:
+            raise NotImplementedError('train_step differentiates tf_raft_amd.losses.sequence_loss and '
+                                      'tf_raft_amd.losses.PhotometricSequenceLoss only')
+        if photometric and len(data) not in (2, 3):
+            raise ValueError(f'train_step with PhotometricSequenceLoss expects (image1, image2) or (image1, image2, mask), '
+                             f'got {len(data)} items')
+        if not photometric and len(data) != 4:
+            raise ValueError(f'train_step with sequence_loss expects (image1, image2, flow, valid), got {len(data)} items')
         self._join_pipeline()                       # inference loops still in flight read the weights this step updates in place
         if self.optimizer is None or not hasattr(self.optimizer, 'apply_gradients'):
             raise RuntimeError('compile() needs an optimizer with apply_gradients(grads, variables, clip_norm) '
                                '(tf_raft_amd.training.AdamW)')
-        image1, image2, flow, valid = data
+        if photometric:
+            image1, image2, flow, valid = data[0], data[1], None, None
+            unlabelled = losses._check_unlabelled(data, ())[:3]       # shapes, before anything is enqueued
+        else:
+            image1, image2, flow, valid = data
         image1 = _dev.to_device(image1).as_subclass(torch.Tensor).to(torch.float32)
         image2 = _dev.to_device(image2).as_subclass(torch.Tensor).to(torch.float32)
         # the ground truth goes to the device NOW: an upload from pageable host memory waits for everything already queued on
         # the stream, and in front of the loss that is the whole forward pass (the host would enqueue the backward only after
         # the GPU had drained: 20 ms of a 85 ms step)
-        flow, valid = losses._truth((flow, valid))
+        if photometric:                             # (the mask is uploaded now for the same reason)
+            y_true = (image1, image2) if unlabelled[2] is None else (image1, image2, losses._mask_to_device(unlabelled[2], image1.device))
+        else:
+            flow, valid = losses._truth((flow, valid))
         B, H, W, _ = image1.shape
         if H % 8 or W % 8:
             raise ValueError(f'H and W must be multiples of 8 (got {H}x{W})')
@@ -773,8 +792,11 @@ class RAFT:
         prefix = 'update_block'
         ub = {k: v for k, v in wts.items() if k.startswith(prefix)}
         preds, tape = grad.loop_forward(ub, correlation, net0, inp, self.iters, prefix, self.variant, tape_dtype=self.tape_dtype)
-        loss = self.loss([flow, valid], preds)
-        d_preds = grad.sequence_loss_grad((flow, valid), preds)
+        if photometric:                             # value and gradient share the gathers: one launch
+            terms, d_preds = grad.photometric_sequence_loss_value_and_grad(y_true, preds, **self.loss._params())
+        else:
+            loss = self.loss([flow, valid], preds)
+            d_preds = grad.sequence_loss_grad((flow, valid), preds)
         d_net0, d_inp, d_pyr, grads = grad.loop_backward(ub, correlation, tape, d_preds, prefix)
         stats = {}
         if full:
@@ -812,6 +834,10 @@ class RAFT:
         # lazily: by get_weights_dict / save_weights, and by the next forward call
         self._host_stale = True
         self._inference_stale = True
+        if photometric:
+            for k in ('loss', 'photometric', 'smoothness'):
+                self.flow_metrics[k].update_state(terms[k])
+            return {k: self.flow_metrics[k].result() for k in ('loss', 'photometric', 'smoothness')}
         info = self.epe([flow, valid], preds[-1])
         self.flow_metrics['loss'].update_state(loss)
         for k in ('epe', 'u1', 'u3', 'u5'):
