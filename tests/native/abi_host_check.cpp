@@ -4,7 +4,8 @@
 // argument validation, geometry / workspace arithmetic, the option table, error strings.  Every launching entry point is
 // called with arguments it must reject (null pointers, bad shapes, misaligned buffers) and has to return an error code
 // without touching memory; the pure-host helpers are called with valid arguments; the launch plans (which kernel family and
-// workgroup shape every update-block layer and encoder stage runs) are checked against a table; four threads then hammer the
+// workgroup shape every update-block layer and encoder stage runs) are checked against a table and the kernels' workgroup remap
+// is checked to be a permutation for every grid size; four threads then hammer the
 // option table, the helpers and the plans concurrently (the only process-global state of the library).
 // Test infrastructure: built and run by tests/test_abi_sanitizers.py, never shipped.
 #include <atomic>
@@ -394,6 +395,23 @@ static void plans_once(bool check_fused) {
     for (const EncRow &r : kEnc) check_enc(r);
 }
 
+// The XCD-aware workgroup remap of the convolution kernels (raft_xcd_remap, launch_plan.h), for every grid size 1 .. 4096: the
+// images of 0 .. n-1 are a permutation of 0 .. n-1, and the logical tiles of one XCD (the workgroups with equal bid & 7) are
+// contiguous -- consecutive workgroups of an XCD get consecutive tiles, and XCD x + 1 starts where XCD x ends.
+// Walking the workgroups XCD by XCD must therefore visit the tiles 0, 1, .. n-1 in order.
+static void xcd_remap() {
+    for (int n = 1; n <= 4096; ++n) {
+        int next = 0;   // the tile the next workgroup in (XCD, bid) order must get
+        bool ok = true;
+        for (int xcd = 0; xcd < 8; ++xcd)
+            for (int bid = xcd; bid < n; bid += 8) ok = ok && raft_xcd_remap(bid, n) == next++;
+        if (!ok || next != n) {
+            std::fprintf(stderr, "FAILED %s:%d: raft_xcd_remap is no contiguous-per-XCD permutation for a grid of %d\n", __FILE__, __LINE__, n);
+            ++failures;
+        }
+    }
+}
+
 static void switched_plans() {   // single-threaded: the switches are process-global
     for (const SwitchRows &sr : kSwitched) {
         EXPECT(raft_set_option(sr.name, sr.value) == 0);
@@ -411,6 +429,7 @@ int main() {
     for (const char *name : plan_switches) EXPECT(raft_set_option(name, "") == 0);
     plans_once(true);
     switched_plans();
+    xcd_remap();
     helpers_once(0);
     options_once(0);
     rejects();

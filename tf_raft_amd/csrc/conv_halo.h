@@ -66,13 +66,7 @@ __global__ void __launch_bounds__(256) conv_halo_kernel(ConvArgs p) {
     const int Hi = p.Hi, Wi = p.Wi;
     const int Min = p.B * Hi * Wi;                     // input pixels
 
-    // XCD-aware remap (bijective for any grid size): logical tiles of one XCD are contiguous, and the
-    // N tiles of one pixel tile are neighbours, so they share the halo tile in that XCD's L2
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int bid = raft_xcd_remap(blockIdx.x, gridDim.x);   // XCD-aware (launch_plan.h): one XCD's logical tiles are contiguous
     const int mt = bid / ntn, nt = bid - mt * ntn;
     const int tx = mt % tiles_x, ty = (mt / tiles_x) % tiles_y, b = mt / (tiles_x * tiles_y);
     const int y0 = ty * TH, x0 = tx * TW;
@@ -80,15 +74,14 @@ __global__ void __launch_bounds__(256) conv_halo_kernel(ConvArgs p) {
     const int cin = p.c0 + p.c1;
     const int nch = cin >> 5;
 
-    const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.a0, 0, (int)((((long)Min - 1) * p.lda0 + (STEM ? 4 : p.c0)) * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(p.c1 ? p.a1 : p.a0), 0, p.c1 ? (int)((((long)Min - 1) * p.lda1 + p.c1) * 4) : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.wp, 0, (int)((long)TAPS * cin * p.npad * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs0 = raft_stage_src0(p, Min, STEM ? 4 : p.c0), rs1 = raft_stage_src1(p, Min);
+    const __amdgpu_buffer_rsrc_t rsw = raft_stage_weights(p, TAPS, cin);
 
-    // ---- halo staging assignment: item = (halo pixel, 16-byte channel quad)
-    int pix[NA];          // input pixel index of the item's halo pixel, or -1 (outside the image / padding item)
+    // ---- halo staging assignment: item = (halo pixel, 16-byte channel quad).  Descriptors, the chunk load and the weight-fragment
+    // fetch are the shared ones of conv_stage.h; the item table (STEM addressing, offsets in floats) and the LDS store stay written
+    // out here: built from raft_stage_items / raft_stage_lstore dozens of the direct instances change register or spill counts,
+    // with the shared store alone still one encoder instance (docs/NOTEBOOK.md 25)
+    int pix[NA];         // input pixel index of the item's halo pixel, or -1 (outside the image / padding item)
     int lds_off[NA];
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
@@ -119,23 +112,8 @@ __global__ void __launch_bounds__(256) conv_halo_kernel(ConvArgs p) {
             }
             return;
         }
-        const int ch = c * 32;
-        const bool first = ch < p.c0;
-        const int ld = first ? p.lda0 : p.lda1;
-        const int chl = (first ? ch : ch - p.c0) + (tid & 7) * 4;
-        if (first) {
-#pragma unroll
-            for (int i = 0; i < NA; ++i)
-                ra[i] = raft_buffer_load_f4(rs0, pix[i] >= 0 ? (unsigned)((pix[i] * ld + chl) * 4) : RAFT_OOB);
-        } else {
-#pragma unroll
-            for (int i = 0; i < NA; ++i)
-                ra[i] = raft_buffer_load_f4(rs1, pix[i] >= 0 ? (unsigned)((pix[i] * ld + chl) * 4) : RAFT_OOB);
-        }
-        if (PRE) {
-            pre_sc = *(const f32x4 *)(p.pre_scale + (long)b * cin + ch + (tid & 7) * 4);
-            pre_sh = *(const f32x4 *)(p.pre_shift + (long)b * cin + ch + (tid & 7) * 4);
-        }
+        raft_stage_gload(p, rs0, rs1, pix, c * 32, tid & 7, ra);
+        if (PRE) raft_stage_pre_load(p, b, cin, c * 32, tid & 7, pre_sc, pre_sh);
     };
     auto lstore = [&](int buf) {
 #pragma unroll
@@ -152,7 +130,7 @@ __global__ void __launch_bounds__(256) conv_halo_kernel(ConvArgs p) {
     // ---- fragment fetch
     f32x4 fa[2][TH], fb[DEEP ? 4 : 2][TN];
     const int a_lane = LR * FSTEP * LDA + G * 4;                          // + window shift + kk*16
-    const unsigned b_lane = (unsigned)(((G * p.npad) + n0 + wn * 16 * TN + LR) * 16);   // bytes
+    const unsigned b_lane = raft_stage_b_lane(p, G, n0, wn * 16 * TN, LR);
     auto frag_a = [&](int buf, int q, f32x4 *a) {
         const int t = q / NKK, kk = q - t * NKK;
         const float *base = smem + buf * A_BUF + a_lane + ((t / KW) * HWP + (t % KW)) * LDA + kk * 16;
@@ -161,10 +139,7 @@ __global__ void __launch_bounds__(256) conv_halo_kernel(ConvArgs p) {
     };
     auto frag_b = [&](int c, int q, f32x4 *bf) {
         const int t = q / NKK, kk = q - t * NKK;
-        const unsigned row = (unsigned)((t * (cin >> 2) + c * 8 + kk * 4) * p.npad) * 16u;   // wave-uniform bytes
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-            bf[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, (int)(b_lane + j * 256), (int)row, 0));
+        raft_stage_frag_b<TN>(p, rsw, b_lane, cin, t, c * 8 + kk * 4, bf);
     };
 
     f32x4 acc[TH][TN];

@@ -1,6 +1,7 @@
 // Shared definitions of the fp32-MFMA convolution kernels for gfx950 (conv_halo.h, conv_wino.h, conv_wino1d.h, conv_wino4.h):
-// the argument block, the epilogue codes, gate activations, buffer-load helper, and -- in conv_epilogue.h, included below --
-// the ONE epilogue all four families share (descriptors, channel bookkeeping, value formulas, STATS tail).
+// the argument block, the epilogue codes, gate activations, buffer-load helper, and -- in conv_epilogue.h and conv_stage.h,
+// included below -- the ONE epilogue all four families share (descriptors, channel bookkeeping, value formulas, STATS tail) and
+// their ONE prologue (source / weight descriptors, halo staging, weight-fragment fetch; the workgroup remap is in launch_plan.h).
 //
 // GEMM view of every kernel: M = B*H*W output pixels, N = output channels, K = taps x input channels; NHWC activations, weights
 // packed by tf_raft_amd/packing.py into fragment-shaped k-quads (include/raft_hip.h).  Two rules shape all of them:
@@ -64,6 +65,7 @@ __device__ __forceinline__ f32x4 raft_buffer_load_f4(__amdgpu_buffer_rsrc_t rsrc
 constexpr unsigned RAFT_OOB = 0x80000000u;   // >= any buffer extent we accept (< 2 GiB): load returns 0
 
 #include "conv_epilogue.h"
+#include "conv_stage.h"
 
 // (The first version of the direct kernel -- a (tap, chunk)-stepped LDS pipeline with 32x32 / 16x16 MFMA tiles, tile codes 0..5 of
 // RAFT_CONV_TILE -- was kept for A/B through round 3 and removed in round 4: the halo-tiled kernel of conv_halo.h replaced it

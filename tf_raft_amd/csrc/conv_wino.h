@@ -78,11 +78,7 @@ __global__ void __launch_bounds__(256 * KS, KS == 2 ? 1 : ((TNW == 1 && !SB && !
     const int ntn = p.npad / BN;
     const int M = p.B * p.H * p.W;
 
-    int bid = blockIdx.x;   // XCD-aware remap (see conv_halo.h)
-    {
-        const int nwg = gridDim.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int bid = raft_xcd_remap(blockIdx.x, gridDim.x);   // XCD-aware (launch_plan.h)
     const int mt = bid / ntn, nt = bid - mt * ntn;
     const int tx0 = mt % tiles_x, ty0 = (mt / tiles_x) % tiles_y, b = mt / (tiles_x * tiles_y);
     const int y0 = ty0 * TH, x0 = tx0 * TW;
@@ -90,60 +86,23 @@ __global__ void __launch_bounds__(256 * KS, KS == 2 ? 1 : ((TNW == 1 && !SB && !
     const int cin = p.c0 + p.c1;
     const int nst = cin / (16 * CK);                   // stages (barriers)
 
-    const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.a0, 0, (int)((((long)M - 1) * p.lda0 + p.c0) * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(p.c1 ? p.a1 : p.a0), 0, p.c1 ? (int)((((long)M - 1) * p.lda1 + p.c1) * 4) : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.wp, 0, (int)((long)16 * cin * p.npad * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs0 = raft_stage_src0(p, M, p.c0), rs1 = raft_stage_src1(p, M);
+    const __amdgpu_buffer_rsrc_t rsw = raft_stage_weights(p, 16, cin);
 
-    // ---- halo staging: item = (halo pixel, 16-byte channel quad of the chunk)
+    // ---- halo staging (conv_stage.h): item = (halo pixel, 16-byte channel quad of the chunk); lds_off in 16-byte units
     int pix[NA], lds_off[NA];
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-        const int item = tid + NTHR * i;
-        const int hp = item / QS, c4 = item % QS;
-        const int hy = hp / HWP, hx = hp - hy * HWP;
-        const int yy = y0 - 1 + hy, xx = x0 - 1 + hx;
-        const bool ok = (hp < HP) & ((unsigned)yy < (unsigned)p.H) & ((unsigned)xx < (unsigned)p.W);
-        pix[i] = ok ? (b * p.H + yy) * p.W + xx : -1;
-        lds_off[i] = hp < HP ? hp * (LDA / 4) + c4 : HP * (LDA / 4);   // 16-byte units
-    }
+    raft_stage_items<NTHR, QS, HWP, HP>(tid, b, p.H, p.W, y0 - 1, x0 - 1, 1, [](int hp, int, int) { return hp * (LDA / 4); },
+                                        HP * (LDA / 4), pix, lds_off);
     f32x4 ra[NA], pre_sc, pre_sh;
     auto gload = [&](int c) {
-        const int ch = c * 16 * CK;
-        if (PRE) {
-            pre_sc = *(const f32x4 *)(p.pre_scale + (long)b * cin + ch + (tid % QS) * 4);
-            pre_sh = *(const f32x4 *)(p.pre_shift + (long)b * cin + ch + (tid % QS) * 4);
-        }
-        const bool first = ch < p.c0;
-        const int ld = first ? p.lda0 : p.lda1;
-        const int chl = (first ? ch : ch - p.c0) + (tid % QS) * 4;
-        if (first) {
-#pragma unroll
-            for (int i = 0; i < NA; ++i)
-                ra[i] = raft_buffer_load_f4(rs0, pix[i] >= 0 ? (unsigned)((pix[i] * ld + chl) * 4) : RAFT_OOB);
-        } else {
-#pragma unroll
-            for (int i = 0; i < NA; ++i)
-                ra[i] = raft_buffer_load_f4(rs1, pix[i] >= 0 ? (unsigned)((pix[i] * ld + chl) * 4) : RAFT_OOB);
-        }
+        if (PRE) raft_stage_pre_load(p, b, cin, c * 16 * CK, tid % QS, pre_sc, pre_sh);
+        raft_stage_gload(p, rs0, rs1, pix, c * 16 * CK, tid % QS, ra);
     };
-    auto lstore = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            f32x4 v = ra[i];
-            if (PRE) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = pix[i] >= 0 ? fmaxf(fmaf(v[e], pre_sc[e], pre_sh[e]), 0.f) : 0.f;
-            }
-            *(f32x4 *)(smem + buf * A_BUF + lds_off[i] * 4) = v;
-        }
-    };
+    auto lstore = [&](int buf) { raft_stage_lstore<PRE>(smem + buf * A_BUF, lds_off, pix, ra, pre_sc, pre_sh); };
 
     // ---- fragments
     const int a_lane = ((2 * rb) * HWP + 2 * LR) * LDA + G * 4;          // patch origin of tile LR in row block rb
-    const unsigned b_lane = (unsigned)(((G * p.npad) + n0 + cg * 16 * TNW + LR) * 16);   // bytes
+    const unsigned b_lane = raft_stage_b_lane(p, G, n0, cg * 16 * TNW, LR);
     auto patch_row = [&](int buf, int sub, int r, f32x4 *d) {              // d[j] = patch(r, j), j = 0..3, 16-ch chunk `sub`
         if ((RAFT_WINO_ABL & 2) && !(buf == 0 && sub == 0 && r != 1 && r != 3)) return;
         const float *base = smem + buf * A_BUF + a_lane + r * HWP * LDA + sub * 16;
@@ -151,12 +110,7 @@ __global__ void __launch_bounds__(256 * KS, KS == 2 ? 1 : ((TNW == 1 && !SB && !
         for (int j = 0; j < 4; ++j) d[j] = *(const f32x4 *)(base + j * LDA);
     };
     f32x4 fb[NR][TNW];
-    auto frag_b = [&](int c, int t, f32x4 *bf) {
-        const unsigned row = (unsigned)((t * (cin >> 2) + c * 4) * p.npad) * 16u;   // wave-uniform bytes
-#pragma unroll
-        for (int j = 0; j < TNW; ++j)
-            bf[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, (int)(b_lane + j * 256), (int)row, 0));
-    };
+    auto frag_b = [&](int c, int t, f32x4 *bf) { raft_stage_frag_b<TNW>(p, rsw, b_lane, cin, t, c * 4, bf); };
 
     f32x4 acc[16][TNW];
 #pragma unroll

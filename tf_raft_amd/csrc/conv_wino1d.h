@@ -165,11 +165,7 @@ __global__ void __launch_bounds__(256, 2) conv_wino1d_kernel(ConvArgs p) {
     const int ntn = p.npad / BN;
     const int M = p.B * p.H * p.W;
 
-    int bid = blockIdx.x;   // XCD-aware remap (see conv_halo.h)
-    {
-        const int nwg = gridDim.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int bid = raft_xcd_remap(blockIdx.x, gridDim.x);   // XCD-aware (launch_plan.h)
     const int mt = bid / ntn, nt = bid - mt * ntn;
     const int tx0 = mt % tiles_x, ty0 = (mt / tiles_x) % tiles_y, b = mt / (tiles_x * tiles_y);
     const int y0 = ty0 * TILE_H, x0 = tx0 * TILE_W;
@@ -177,45 +173,17 @@ __global__ void __launch_bounds__(256, 2) conv_wino1d_kernel(ConvArgs p) {
     const int cin = p.c0 + p.c1;
     const int nst = cin / (16 * CK);                            // stages (barriers)
 
-    const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.a0, 0, (int)((((long)M - 1) * p.lda0 + p.c0) * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(p.c1 ? p.a1 : p.a0), 0, p.c1 ? (int)((((long)M - 1) * p.lda1 + p.c1) * 4) : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.wp, 0, (int)((long)NT * cin * p.npad * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs0 = raft_stage_src0(p, M, p.c0), rs1 = raft_stage_src1(p, M);
+    const __amdgpu_buffer_rsrc_t rsw = raft_stage_weights(p, NT, cin);
 
-    // ---- halo staging: item = (halo pixel, 16-byte channel quad of the chunk)
+    // ---- halo staging (conv_stage.h): item = (halo pixel, 16-byte channel quad of the chunk); lds_off in 16-byte units
     int pix[NA], lds_off[NA];
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-        const int item = tid + 256 * i;
-        const int hp = item / QS, c4 = item % QS;
-        const int hy = hp / HWP, hx = hp - hy * HWP;
-        const int yy = y0 + hy - (AXIS == 1 ? 2 : 0), xx = x0 + hx - (AXIS == 0 ? 2 : 0);
-        const bool ok = (hp < HP) & ((unsigned)yy < (unsigned)p.H) & ((unsigned)xx < (unsigned)p.W);
-        pix[i] = ok ? (b * p.H + yy) * p.W + xx : -1;
-        lds_off[i] = hp < HP ? (hy * ROW + hx * LDA) / 4 + (SWZ ? (hx >> 2) * 2 : 0) + c4 : HH * ROW / 4;   // 16-byte units
-    }
+    raft_stage_items<256, QS, HWP, HP>(tid, b, p.H, p.W, y0 - (AXIS == 1 ? 2 : 0), x0 - (AXIS == 0 ? 2 : 0), 1,
+                                       [](int, int hy, int hx) { return (hy * ROW + hx * LDA) / 4 + (SWZ ? (hx >> 2) * 2 : 0); },
+                                       HH * ROW / 4, pix, lds_off);
     f32x4 ra[NA];
-    auto gload = [&](int c) {
-        const int ch = c * 16 * CK;
-        const bool first = ch < p.c0;
-        const int ld = first ? p.lda0 : p.lda1;
-        const int chl = (first ? ch : ch - p.c0) + (tid % QS) * 4;
-        if (first) {
-#pragma unroll
-            for (int i = 0; i < NA; ++i)
-                ra[i] = raft_buffer_load_f4(rs0, pix[i] >= 0 ? (unsigned)((pix[i] * ld + chl) * 4) : RAFT_OOB);
-        } else {
-#pragma unroll
-            for (int i = 0; i < NA; ++i)
-                ra[i] = raft_buffer_load_f4(rs1, pix[i] >= 0 ? (unsigned)((pix[i] * ld + chl) * 4) : RAFT_OOB);
-        }
-    };
-    auto lstore = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < NA; ++i) *(f32x4 *)(smem + buf * A_BUF + lds_off[i] * 4) = ra[i];
-    };
+    auto gload = [&](int c) { raft_stage_gload(p, rs0, rs1, pix, c * 16 * CK, tid % QS, ra); };
+    auto lstore = [&](int buf) { raft_stage_lstore(smem + buf * A_BUF, lds_off, ra); };
 
     // ---- fragments.  Row block i of this wave: rb = TM rbp + i.
     //   AXIS 0: group LR of image row y0 + rb: inputs at halo (rb, MO LR + k)     AXIS 1: group = rows MO rb .. MO rb +
@@ -225,14 +193,9 @@ __global__ void __launch_bounds__(256, 2) conv_wino1d_kernel(ConvArgs p) {
         return (AXIS == 0 ? rb * ROW + MO * LR * LDA + (SWZ ? LR * 8 : 0) : (MO * rb * HWP + LR) * LDA) + G * 4;
     };
     auto koff = [](int k) { return AXIS == 0 ? k * LDA + (SWZ ? (k >> 2) * 8 : 0) : k * HWP * LDA; };
-    const unsigned b_lane = (unsigned)(((G * p.npad) + n0 + cg * 16 * TNW + LR) * 16);   // bytes
+    const unsigned b_lane = raft_stage_b_lane(p, G, n0, cg * 16 * TNW, LR);
     f32x4 fb[RING][TNW];
-    auto frag_b = [&](int c, int t, f32x4 *bf) {
-        const unsigned row = (unsigned)((t * (cin >> 2) + c * 4) * p.npad) * 16u;   // wave-uniform bytes
-#pragma unroll
-        for (int j = 0; j < TNW; ++j)
-            bf[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, (int)(b_lane + j * 256), (int)row, 0));
-    };
+    auto frag_b = [&](int c, int t, f32x4 *bf) { raft_stage_frag_b<TNW>(p, rsw, b_lane, cin, t, c * 4, bf); };
     // B'^T d for one output group, four channels at a time
     auto transform = [&](int buf, int sub, int i, f32x4 *V) {
         const float *base = smem + buf * A_BUF + a_lane(i) + sub * 16;

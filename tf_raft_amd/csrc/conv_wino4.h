@@ -145,11 +145,7 @@ __global__ void __launch_bounds__(256, 1) conv_wino4_kernel(ConvArgs p) {
     const int ntn = p.npad / 64;
     const int M = p.B * p.H * p.W;
 
-    int bid = blockIdx.x;   // XCD-aware remap (see conv_halo.h)
-    {
-        const int nwg = gridDim.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int bid = raft_xcd_remap(blockIdx.x, gridDim.x);   // XCD-aware (launch_plan.h)
     int mt = bid / ntn, nt = bid - mt * ntn;
 #ifdef RAFT_WINO4_XCD
     // experiment: one channel group (or a set of them) per XCD, so that an XCD's L2 holds 1/8 of the transformed weights and
@@ -174,10 +170,7 @@ __global__ void __launch_bounds__(256, 1) conv_wino4_kernel(ConvArgs p) {
     const int nch = cin >> 4;        // 16-channel chunks
     const int nst = nch / KS;        // stages (KS = 2: nch is even and so is c0 / 16 -- the launcher checks)
 
-    const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.a0, 0, (int)((((long)M - 1) * p.lda0 + p.c0) * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.wp, 0, (int)((long)36 * cin * p.npad * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs0 = raft_stage_src0(p, M, p.c0), rsw = raft_stage_weights(p, 36, cin);
 
     // ---- halo staging: item = (halo pixel, 16-byte channel quad of the chunk).  The byte offset of an item inside its source
     // tensor is kept per thread (out-of-image items: an offset beyond any extent, the bounds check returns 0); the chunk's
@@ -208,9 +201,9 @@ __global__ void __launch_bounds__(256, 1) conv_wino4_kernel(ConvArgs p) {
     auto next_source = [&](int st) {   // st = stage index (KS chunks of 16 channels each, all from one source)
         const int ch = st * 16 * KS;
         const bool first = ch < p.c0, live = st < nst && !(RAFT_WINO4_ABL & 4);
-        const float *base = first ? p.a0 : (p.c1 ? p.a1 : p.a0);
-        const int ext = first ? (int)((((long)M - 1) * p.lda0 + p.c0) * 4) : (p.c1 ? (int)((((long)M - 1) * p.lda1 + p.c1) * 4) : 0);
-        rsn = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, live ? ext : 0, 0x00020000);   // past the last chunk: empty
+        const float *base = first ? p.a0 : raft_stage_src1_base(p);
+        const int ext = first ? raft_stage_src0_bytes(p, M, p.c0) : raft_stage_src1_bytes(p, M);
+        rsn = raft_stage_rsrc(base, live ? ext : 0);   // past the last chunk: empty
         soff_n = (first ? ch : ch - p.c0) * 4;
         if constexpr (PRE) {        // one source (the launcher checks): channel ch + 4 (tid & 3) of image b; past the last chunk: unused
             const int cq = (st < nst ? ch : 0) + (tid & 3) * 4;

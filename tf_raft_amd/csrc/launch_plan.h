@@ -24,6 +24,20 @@ bool raft_opt_is_set(int id);
 // RAFT_CONV_TILE ("<code>" or "<npad>:<taps>:<code>,..."): the tile code forced for a convolution, or -1
 int raft_opt_conv_tile(int npad, int taps, bool (*valid)(int code, int npad));
 
+#ifdef __HIP__
+#define RAFT_HOST_DEVICE __host__ __device__
+#else
+#define RAFT_HOST_DEVICE
+#endif
+// XCD-aware workgroup remap of the MFMA convolution kernels and the fused mask + upsampling kernel: the hardware places workgroup
+// bid on XCD bid & 7; the logical tile it works on is chosen so that the tiles of one XCD are contiguous (the N tiles of one pixel
+// tile are neighbours and share the halo tile in that XCD's L2).  A permutation of 0 .. nwg-1 for every grid size
+// (tests/native/abi_host_check.cpp checks both properties).
+RAFT_HOST_DEVICE static inline int raft_xcd_remap(int bid, int nwg) {
+    const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
 // direct halo-tiled kernel (conv_halo.h), F(2x2, 3x3) (conv_wino.h), F(2, 5) / F(4, 5) by Wino1dPlan::mo (conv_wino1d.h), F(4x4, 3x3)
 enum RaftConvFamily { RAFT_FAM_HALO, RAFT_FAM_WINO, RAFT_FAM_WINO1D, RAFT_FAM_WINO4 };
 struct HaloPlan { int th, tn; };                // TH x 16-pixel x 64*TN-channel workgroups

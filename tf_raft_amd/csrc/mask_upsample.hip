@@ -42,11 +42,7 @@ __global__ void __launch_bounds__(512) mask_upsample_kernel(MaskUpArgs p) {
     // A launch may have FEWER workgroups than tiles (background mode, see raft_launch_mask_upsample): workgroup g walks the tiles
     // g, g + gridDim.x, ...
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    int bid = tile;   // XCD-aware remap (see conv_halo.h)
-    {
-        const int nwg = ntiles, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int bid = raft_xcd_remap(tile, ntiles);   // XCD-aware (launch_plan.h)
     const int tx = bid % tiles_x, ty = (bid / tiles_x) % tiles_y, b = bid / (tiles_x * tiles_y);
     const int y0 = ty * MU_TH, x0 = tx * MU_TW;
     const int M = p.B * p.h * p.w;
