@@ -166,22 +166,11 @@ def test_bad_arguments_raise_value_error_before_any_launch():
 
 
 # ------------------------------------------------------------------ C ABI
-NEW_ENTRIES = {'raft_augment_params_bytes': 0, 'raft_augment_sums_u8': 7, 'raft_augment_gather_u8': 15}
-
-
 def test_augment_entries_are_declared_exported_and_mirrored():
+    """The record: same fields in the same order, same size (the prototypes: tests/test_host_logic.py test_the_binding_is_the_header)."""
     with open(os.path.join(ROOT, 'include', 'raft_hip.h')) as f:
         header = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
     lib = _ffi.load_library()
-    for name, nargs in NEW_ENTRIES.items():
-        decl = re.search(r'\bint\s+' + name + r'\s*\(([^)]*)\)', header)
-        assert decl, f'{name} is not declared in include/raft_hip.h'
-        declared = 0 if decl.group(1).strip() == 'void' else len(decl.group(1).split(','))
-        assert declared == nargs == len(_ffi._SIGNATURES[name][1])
-        assert name in _ffi.EXPORTED_SYMBOLS and hasattr(lib, name)
-    assert lib.raft_version() == _ffi.ABI_VERSION == 222
-    assert int(re.search(r'#define RAFT_HIP_VERSION (\d+)', header).group(1)) == 222
-    # the record: same fields in the same order, same size
     body = re.search(r'typedef struct \{(.*?)\} RaftAugmentParams;', header, flags=re.S).group(1)
     fields = [re.sub(r'\[.*', '', n.strip()) for line in body.split(';') if line.strip()
               for n in line.strip().split(None, 1)[1].split(',')]

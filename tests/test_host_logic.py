@@ -291,6 +291,103 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert typed.raft_error_string(0) == b'ok'
 
 
+_P, _I, _F, _PP = C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_void_p)
+# Written out by hand, one entry per item of the parser's vocabulary: every scalar type, const char *, a struct by value, structs by
+# host pointer, int64_t *, pointer to pointer, plain device pointers.  (lh / lw of raft_corr_pyramid_layout are host int arrays
+# that travel as void*: ctypes arrays and None pass.)
+LITERAL_SIGNATURES = {
+    'raft_crc32c': (C.c_uint32, [C.c_uint32, _P, C.c_size_t]),
+    'raft_error_string': (C.c_char_p, [_I]),
+    'raft_set_option': (_I, [C.c_char_p, C.c_char_p]),
+    'raft_dropout_f32': (_I, [_P, C.c_int64, _F, C.c_uint64, _P, _P, _P]),
+    'raft_sequence_loss_f32': (_I, [_P, _P, _P, C.c_int64, _I, C.c_int64, C.c_double, _F, _P, _P, _P]),
+    'raft_tile_gather_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _ffi.TileOrigins, _P]),
+    'raft_corr_pyramid_layout': (_I, [_I, _I, _I, _I, C.POINTER(C.c_int64), _P, _P]),
+    'raft_adamw_step_multi_f32': (_I, [_PP, _PP, _PP, _PP, C.POINTER(C.c_int64), _I, _F, _F, _F, _F, _F, _P, _F, _P]),
+    'raft_loop_ctx_create': (_I, [_PP]),
+    'raft_update_basic_f32': (_I, [C.POINTER(_ffi.BasicUpdateWeights), _I, _I, _I, C.POINTER(_ffi.State), _P]),
+    'raft_encoder_workspace_floats': (C.c_int64, [C.POINTER(_ffi.EncoderWeights), _I, _I, _I]),
+    'raft_photometric_loss_f32': (_I, [_P, _P, _P, _P, C.c_int64, _I, _I, _I, _I, C.c_double, _F, _F, _F, _F, _P, _P, _P, _P]),
+}
+# Parameter counts of the entries that the feature pull requests since ABI 221 added, as each of them wrote them down.
+ENTRY_PARAMETER_COUNTS = {
+    'raft_crop_or_pad_f32': 9, 'raft_crop_or_pad_u8_f32': 9, 'raft_crop_or_pad_u8': 9,
+    'raft_augment_params_bytes': 0, 'raft_augment_sums_u8': 7, 'raft_augment_gather_u8': 15, 'raft_augment_gather_sparse_u8': 16,
+    'raft_resize_f32': 18, 'raft_resize_u8_f32': 18,
+    'raft_tile_gather_f32': 10, 'raft_tile_gather_u8_f32': 10, 'raft_tile_blend_f32': 18,
+    'raft_flow_to_image_workspace_floats': 1, 'raft_flow_rad_max_f32': 9, 'raft_flow_to_image_u8': 12,
+    'raft_warp_f32': 9, 'raft_warp_u8_f32': 9, 'raft_flow_consistency_f32': 10,
+    'raft_forward_interpolate_f32': 6, 'raft_warm_start_f32': 6, 'raft_warm_start_small_f32': 6,
+    'raft_photometric_loss_workspace_doubles': 0, 'raft_photometric_loss_f32': 18,
+}
+
+
+def test_the_binding_is_the_header():
+    """tf_raft_amd/_ffi.py derives its prototype table from include/raft_hip.h.  (a) The parser skips nothing; (b) it types a
+    hand-written sample as the hand-written table did; (c) the entries of the feature pull requests have the parameter counts
+    those wrote down, in the table and on the loaded library; (d) the parser reads what C allows and refuses what it cannot map."""
+    with open(os.path.join(ROOT, 'include', 'raft_hip.h')) as f:
+        header = f.read()
+    parsed = _ffi.header_signatures(header)
+    assert parsed == _ffi._SIGNATURES and tuple(parsed) == _ffi.EXPORTED_SYMBOLS
+    assert sorted(parsed) == _declared_functions()                                                  # (a)
+    for name, want in LITERAL_SIGNATURES.items():                                                   # (b)
+        assert parsed[name] == want, name
+    lib = _ffi.load_library()                                                                       # (c)
+    for name, nargs in ENTRY_PARAMETER_COUNTS.items():
+        res, args = parsed[name]
+        assert len(args) == nargs == len(getattr(lib, name).argtypes or ()), name
+        assert res is (C.c_int64 if 'workspace' in name else C.c_int) and getattr(lib, name).restype is res, name
+    assert lib.raft_version() == _ffi.ABI_VERSION == 222 == _ffi.header_constants(header)['RAFT_HIP_VERSION']
+    text = ('/* int raft_hidden(int a); */\n'                                                       # (d)
+            'int64_t\n    raft_a(const float *x,   /* a device pointer, */\n'
+            '           int64_t n,            // a count; and (void *)\n'
+            '           const raft_state *st,\n'
+            '           RaftTileOrigins o);\n'
+            'int raft_b(void);\n')
+    assert _ffi.header_signatures(text) == {'raft_a': (C.c_int64, [_P, C.c_int64, C.POINTER(_ffi.State), _ffi.TileOrigins]),
+                                            'raft_b': (_I, [])}
+    for bad in ('int raft_x(short v);', 'int raft_y(raft_unknown_t s);', 'int raft_z(int);', 'int raft_w(int a', 'raft_v(int a);',
+                'int raft_u(RaftAugmentParams p);', 'short raft_t(int a);'):
+        with pytest.raises(ValueError, match=r'raft_[t-z]'):
+            _ffi.header_signatures(bad)
+
+
+STRUCT_MIRRORS = [('raft_conv_weights', 'ConvWeights'), ('raft_basic_update_weights', 'BasicUpdateWeights'),
+                  ('raft_small_update_weights', 'SmallUpdateWeights'), ('raft_encoder_weights', 'EncoderWeights'),
+                  ('raft_state', 'State'), ('RaftTileOrigins', 'TileOrigins'), ('RaftAugmentParams', 'AugmentParams')]
+
+
+def test_ctypes_structs_have_the_layout_the_c_compiler_gives_the_header(tmp_path):
+    """sizeof of every mirrored struct and offsetof / sizeof of every field, printed by a C11 program generated from the mirrors'
+    ``_fields_`` and compiled against include/raft_hip.h, against what ctypes lays out.  A new struct joins STRUCT_MIRRORS."""
+    import shutil
+    import subprocess
+    cc = shutil.which('cc')
+    if cc is None:
+        pytest.skip('no C compiler (cc): the layout program cannot be built here')
+    lines, want = [], []
+    for c_name, py_name in STRUCT_MIRRORS:
+        mirror = getattr(_ffi, py_name)
+        lines.append(f'    printf("%zu\\n", sizeof({c_name}));')
+        want.append((c_name, C.sizeof(mirror)))
+        for field, _ in mirror._fields_:
+            lines.append(f'    printf("%zu %zu\\n", offsetof({c_name}, {field}), sizeof((({c_name} *)0)->{field}));')
+            want.append((f'{c_name}.{field}', getattr(mirror, field).offset, getattr(mirror, field).size))
+    src, exe = str(tmp_path / 'layout.c'), str(tmp_path / 'layout')
+    with open(src, 'w') as f:
+        f.write('#include <stdio.h>\n#include <stddef.h>\n#include "raft_hip.h"\nint main(void) {\n' + '\n'.join(lines)
+                + '\n    return 0;\n}\n')
+    subprocess.run([cc, '-std=c11', '-Wall', '-Werror', '-I', os.path.join(ROOT, 'include'), src, '-o', exe],
+                   check=True, capture_output=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()
+    got = [tuple(int(v) for v in line.split()) for line in out]
+    assert len(got) == len(want) == 7 + sum(len(getattr(_ffi, p)._fields_) for _, p in STRUCT_MIRRORS)
+    for (what, *w), g in zip(want, got):
+        assert tuple(w) == g, f'{what}: ctypes {tuple(w)}, C {g}'
+    assert C.sizeof(_ffi.TileOrigins) == 264 and C.sizeof(_ffi.AugmentParams) == 168
+
+
 def test_tuning_switches_are_a_table_not_getenv():
     """raft_set_option / raft_get_option (host-only): unknown names are rejected, values round-trip, NULL returns to
     the load-time state; and no launch path calls getenv (only the one-time table initialiser in host_util.hip may)."""
@@ -363,11 +460,7 @@ def _header_struct_fields(name):
     return fields
 
 
-@pytest.mark.parametrize('c_name,py_name', [('raft_conv_weights', 'ConvWeights'),
-                                            ('raft_basic_update_weights', 'BasicUpdateWeights'),
-                                            ('raft_small_update_weights', 'SmallUpdateWeights'),
-                                            ('raft_encoder_weights', 'EncoderWeights'),
-                                            ('raft_state', 'State')])
+@pytest.mark.parametrize('c_name,py_name', STRUCT_MIRRORS[:6])       # (RaftAugmentParams has no tag: tests/test_augment.py)
 def test_ctypes_structs_mirror_the_header_field_for_field(c_name, py_name):
     """The ctypes mirrors in tf_raft_amd/_ffi.py declare the same fields in the same order as include/raft_hip.h
     (appending a field to one side only would silently shift every later pointer)."""

@@ -19,15 +19,11 @@ where it agrees to 1e-13, and ``test_fused_and_written_evaluations_are_one_rule`
 rounding of one coordinate.  The rule as written (``fused=False``) is what the product's ``resize_taps`` and the kernels are held to.
 """
 import ctypes as C
-import os
 from fractions import Fraction
-import re
 
 import numpy as np
 import pytest
 import torch
-
-from conftest import ROOT
 
 from tf_raft_amd import _ffi
 
@@ -149,18 +145,6 @@ def test_resize_taps_equal_the_restatement():
 
 
 NEW_ENTRIES = ('raft_resize_f32', 'raft_resize_u8_f32')
-
-
-def test_resize_entries_are_declared_exported_and_mirrored():
-    with open(os.path.join(ROOT, 'include', 'raft_hip.h')) as f:
-        header = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
-    lib = _ffi.load_library()
-    for name in NEW_ENTRIES:
-        decl = re.search(r'\bint\s+' + name + r'\s*\(([^)]*)\)', header)
-        assert decl, f'{name} is not declared in include/raft_hip.h'
-        assert len(decl.group(1).split(',')) == 18 == len(_ffi._SIGNATURES[name][1])
-        assert name in _ffi.EXPORTED_SYMBOLS and hasattr(lib, name)
-    assert lib.raft_version() == _ffi.ABI_VERSION == 222
 
 
 def test_resize_argument_errors_are_returned_before_any_device_work():

@@ -222,22 +222,13 @@ def test_the_tile_option_is_validated_at_construction():
 
 
 # ------------------------------------------------------------------ the C entries
-NEW_ENTRIES = {'raft_tile_gather_f32': 10, 'raft_tile_gather_u8_f32': 10, 'raft_tile_blend_f32': 18}
-
-
 def test_tile_entries_are_declared_exported_and_mirrored():
+    """The constants and the by-value struct (the prototypes: tests/test_host_logic.py test_the_binding_is_the_header)."""
     with open(os.path.join(ROOT, 'include', 'raft_hip.h')) as f:
-        header = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
-    lib = _ffi.load_library()
-    for name, nargs in NEW_ENTRIES.items():
-        decl = re.search(r'\bint\s+' + name + r'\s*\(([^)]*)\)', header)
-        assert decl, f'{name} is not declared in include/raft_hip.h'
-        assert len(decl.group(1).split(',')) == nargs == len(_ffi._SIGNATURES[name][1])
-        assert name in _ffi.EXPORTED_SYMBOLS and hasattr(lib, name)
+        header = f.read()
     assert int(re.search(r'#define RAFT_TILE_MAX_PER_AXIS (\d+)', header).group(1)) == _ffi.TILE_MAX_PER_AXIS == 32
     assert int(re.search(r'#define RAFT_TILE_MAX_TAPS (\d+)', header).group(1)) == _ffi.TILE_MAX_TAPS == 4
     assert C.sizeof(_ffi.TileOrigins) == 4 * (2 + 2 * 32)
-    assert lib.raft_version() == _ffi.ABI_VERSION == 222                    # a pure addition
 
 
 def _origins(oy, ox, ny=None, nx=None):

@@ -1,5 +1,8 @@
 """ctypes binding of ``libraft_hip.so`` (C ABI: include/raft_hip.h).
 
+The prototypes and the integer constants are read from the header when this module is imported (``header_signatures``,
+``header_constants``); only the struct mirrors are written out here, because Python code names their fields.
+
 There is no CPU fallback: if the shared library cannot be loaded (and cannot be built
 because hipcc is absent) importing the device path raises ``RuntimeError``.
 """
@@ -7,15 +10,28 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import threading
 
 _LOCK = threading.Lock()
 _LIB = None
 ABI_VERSION = 222     # include/raft_hip.h RAFT_HIP_VERSION: the ctypes mirrors below describe THIS revision of the structs
 
-c_float_p = C.c_void_p      # raw device pointers travel as void*
-c_i64_p = C.POINTER(C.c_int64)
-c_int_p = C.POINTER(C.c_int)
+_COMMENT = re.compile(r'/\*.*?\*/|//[^\n]*', re.S)
+
+
+def header_constants(text: str) -> dict:
+    """``{name: value}`` of the integer ``#define``s and of the enumerators with a written value in the header ``text``."""
+    text = _COMMENT.sub(' ', text)
+    out = {m[1]: int(m[2]) for m in re.finditer(r'^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(-?\d+)[ \t]*$', text, re.M)}
+    for body in re.findall(r'\benum\s*\{([^{}]*)\}', text):
+        out.update((m[1], int(m[2])) for m in re.finditer(r'(\w+)\s*=\s*(-?\d+)', body))
+    return out
+
+
+with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'raft_hip.h')) as _f:
+    _HEADER = _f.read()
+_CONSTANTS = header_constants(_HEADER)
 
 
 class ConvWeights(C.Structure):
@@ -45,7 +61,7 @@ class EncoderWeights(C.Structure):
                 ('in_gamma', C.c_void_p * 19), ('in_beta', C.c_void_p * 19), ('block_w', (ConvWeights * 2) * 6), ('block_w44', (ConvWeights * 2) * 6)]
 
 
-NORM_NONE, NORM_INSTANCE, NORM_FOLDED = 0, 1, 2
+NORM_NONE, NORM_INSTANCE, NORM_FOLDED = (_CONSTANTS['RAFT_NORM_' + n] for n in ('NONE', 'INSTANCE', 'FOLDED'))
 
 
 class State(C.Structure):
@@ -53,8 +69,8 @@ class State(C.Structure):
         'net', 'x', 'corr', 'coords1', 'flow', 'delta', 'mask', 'ws', 'ctx')]
 
 
-TILE_MAX_PER_AXIS = 32      # include/raft_hip.h RAFT_TILE_MAX_PER_AXIS
-TILE_MAX_TAPS = 4           # include/raft_hip.h RAFT_TILE_MAX_TAPS
+TILE_MAX_PER_AXIS = _CONSTANTS['RAFT_TILE_MAX_PER_AXIS']
+TILE_MAX_TAPS = _CONSTANTS['RAFT_TILE_MAX_TAPS']
 
 
 class TileOrigins(C.Structure):
@@ -72,125 +88,60 @@ class AugmentParams(C.Structure):
                 ('rect', (C.c_int32 * 4) * 2)]
 
 
-AUGMENT_SUM_BLOCKS = 64     # RAFT_AUGMENT_SUM_BLOCKS
+AUGMENT_SUM_BLOCKS = _CONSTANTS['RAFT_AUGMENT_SUM_BLOCKS']
 
-_P = C.c_void_p
-_I = C.c_int
-_SIGNATURES = {
-    'raft_version': (C.c_int, []),
-    'raft_error_string': (C.c_char_p, [_I]),
-    'raft_set_option': (_I, [C.c_char_p, C.c_char_p]),
-    'raft_get_option': (_I, [C.c_char_p, C.c_char_p, C.c_size_t]),
-    'raft_set_thread_concurrency': (_I, [_I]),
-    'raft_loop_ctx_create': (_I, [C.POINTER(C.c_void_p)]),
-    'raft_loop_ctx_destroy': (_I, [C.c_void_p]),
-    'raft_crc32c': (C.c_uint32, [C.c_uint32, C.c_void_p, C.c_size_t]),
-    'raft_corr_pyramid_layout': (_I, [_I, _I, _I, _I, c_i64_p, c_int_p, c_int_p]),
-    'raft_corr_build_workspace_floats': (C.c_int64, [_I, _I, _I, _I, _I]),
-    'raft_corr_build_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _P, c_i64_p, _P, _P]),
-    'raft_corr_lookup_f32': (_I, [_P, c_i64_p, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
-    'raft_lookup_convc1_f32': (_I, [_P, c_i64_p, _P, _I, _I, _I, _P, _P, _I, _I, _P, _I, _P]),
-    'raft_fmap_pyramid_f32': (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
-    'raft_corr_lookup_ondemand_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
-    'raft_bilinear_sampler_f32': (_I, [_P, _P, C.c_int64, _I, _I, _I, _I, _P, _P]),
-    'raft_coords_grid_f32': (_I, [_P, _I, _I, _I, _P]),
-    'raft_upsample_convex_f32': (_I, [_P, _P, _I, _I, _I, _P, _P]),
-    'raft_upflow8_f32': (_I, [_P, _I, _I, _I, _P, _P]),
-    'raft_stream_copy_f32': (_I, [_P, _P, C.c_int64, _P]),
-    'raft_crop_or_pad_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    'raft_crop_or_pad_u8_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    'raft_crop_or_pad_u8': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    'raft_resize_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
-    'raft_resize_u8_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
-    'raft_tile_gather_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, TileOrigins, _P]),
-    'raft_tile_gather_u8_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, TileOrigins, _P]),
-    'raft_tile_blend_f32': (_I, [_P, _P, C.c_int64, _I, _I, _I, _I, _I, TileOrigins, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
-    'raft_flow_to_image_workspace_floats': (C.c_int64, [_I]),
-    'raft_flow_rad_max_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, C.c_float, _P]),
-    'raft_flow_to_image_u8': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.c_float, _I, C.c_float, _P]),
-    'raft_warp_f32': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    'raft_warp_u8_f32': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    'raft_flow_consistency_f32': (_I, [_P, _P, _P, _P, _I, _I, _I, C.c_float, C.c_float, _P]),
-    'raft_augment_params_bytes': (_I, []),
-    'raft_augment_sums_u8': (_I, [_P, _P, _P, _I, _I, _I, _P]),
-    'raft_augment_gather_u8': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    'raft_augment_gather_sparse_u8': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    'raft_mfma_probe_f32': (_I, [_P, _I, _I, _P]),
-    'raft_metrics_workspace_doubles': (C.c_int64, []),
-    'raft_flow_metrics_f32': (_I, [_P, _P, _P, C.c_int64, C.c_float, _P, _P, _P]),
-    'raft_sequence_loss_f32': (_I, [_P, _P, _P, C.c_int64, _I, C.c_int64, C.c_double, C.c_float, _P, _P, _P]),
-    'raft_sequence_loss_grad_f32': (_I, [_P, _P, _P, C.c_int64, _I, C.c_int64, C.c_double, C.c_float, C.c_float, _P, _P]),
-    'raft_photometric_loss_workspace_doubles': (C.c_int64, []),
-    'raft_photometric_loss_f32': (_I, [_P, _P, _P, _P, C.c_int64, _I, _I, _I, _I, C.c_double, C.c_float, C.c_float, C.c_float,
-                                       C.c_float, _P, _P, _P, _P]),
-    'raft_corr_lookup_backward_f32': (_I, [_P, c_i64_p, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    'raft_relu_backward_f32': (_I, [_P, _P, _P, C.c_int64, _P]),
-    'raft_pack_train_conv_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_double), _I, _I, _I, _P, _P, _P]),
-    'raft_conv2d_wgrad_workspace_floats': (C.c_int64, [_I, _I, _I, _I, _I, _I, _I]),
-    'raft_conv2d_wgrad_f32': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
-    'raft_conv2d_wgrad_multi_f32': (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
-    'raft_conv7x7_c2_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
-    'raft_conv7x7_c2_wgrad_workspace_floats': (C.c_int64, [_I]),
-    'raft_conv7x7_c2_backward_f32': (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
-    'raft_gru_gate_zr_f32': (_I, [_P, _P, _I, C.c_int64, _P, _P, _P, _P]),
-    'raft_gru_gate_q_f32': (_I, [_P, _P, _P, C.c_int64, _P, _P, _P]),
-    'raft_gru_gate_q_backward_f32': (_I, [_P, _P, _P, _P, C.c_int64, _P, _P, _P, _P]),
-    'raft_gru_gate_r_backward_f32': (_I, [_P, _P, _P, C.c_int64, _P, _P, _P]),
-    'raft_axpby_f32': (_I, [C.c_float, _P, C.c_float, _P, _P, C.c_int64, _P]),
-    'raft_upsample_convex_backward_workspace_floats': (C.c_int64, [_I, _I, _I]),
-    'raft_upsample_convex_backward_f32': (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
-    'raft_sumsq_workspace_doubles': (C.c_int64, []),
-    'raft_sumsq_f32': (_I, [_P, C.c_int64, _I, _P, _P, _P]),
-    'raft_adamw_step_f32': (_I, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P, C.c_float, _P]),
-    'raft_sumsq_multi_workspace_doubles': (C.c_int64, [_I]),
-    'raft_sumsq_multi_f32': (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), _I, _P, _P, _P]),
-    'raft_adamw_step_multi_f32': (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                       C.POINTER(C.c_int64), _I, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P, C.c_float, _P]),
-    'raft_gemm_f32': (_I, [_P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64, _I, _I, _I, _I, _I,
-                          C.c_float, C.c_float, _P]),
-    'raft_corr_build_backward_f32': (_I, [_P, _P, _P, c_i64_p, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
-    'raft_prepare_state_backward_f32': (_I, [_P, _P, _P, _P, _I, _I, C.c_int64, _P, _P]),
-    'raft_norm_workspace_doubles': (C.c_int64, [_I, _I]),
-    'raft_norm_forward_f32': (_I, [_P, _I, C.c_int64, _I, _P, _P, C.c_float, _I, _P, _P, _P, _P, _P, _P]),
-    'raft_norm_backward_f32': (_I, [_P, _P, _P, _P, _P, _I, C.c_int64, _I, _P, _P, _P, _P, _P]),
-    'raft_axpby_relu_f32': (_I, [C.c_float, _P, C.c_float, _P, _P, C.c_int64, _P]),
-    'raft_f32_to_bf16': (_I, [_P, _P, C.c_int64, _P]),
-    'raft_bf16_to_f32': (_I, [_P, _P, C.c_int64, _P]),
-    'raft_dropout_f32': (_I, [_P, C.c_int64, C.c_float, C.c_uint64, _P, _P, _P]),
-    'raft_dropout_backward_f32': (_I, [_P, _P, C.c_int64, C.c_float, _P, _P]),
-    'raft_upflow8_backward_f32': (_I, [_P, _I, _I, _I, _P, _P]),
-    'raft_conv2d_f32': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I,
-                             C.c_float, _P, _I, _P]),
-    'raft_conv2d_winograd_f32': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, C.c_float, _P, _I, _P]),
-    'raft_conv2d_winograd4_f32': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, C.c_float, _P, _I, _P]),
-    'raft_conv1d_winograd_f32': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, C.c_float, _P, _I, _P]),
-    'raft_conv1d_winograd4_f32': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, C.c_float, _P, _I, _P]),
-    'raft_update_workspace_floats': (C.c_int64, [_I, _I, _I]),
-    'raft_prepare_state_f32': (_I, [_P, _I, _I, _I, C.POINTER(State), _P]),
-    'raft_gru_context_f32': (_I, [C.POINTER(BasicUpdateWeights), _I, _I, _I, C.POINTER(State), _P]),
-    'raft_update_basic_f32': (_I, [C.POINTER(BasicUpdateWeights), _I, _I, _I, C.POINTER(State), _P]),
-    'raft_iterate_basic_f32': (_I, [C.POINTER(BasicUpdateWeights), _P, c_i64_p, _I, _I, _I, _I,
-                                    C.POINTER(State), _P, _P]),
-    'raft_iterate_basic_overlap_f32': (_I, [C.POINTER(BasicUpdateWeights), _P, c_i64_p, _I, _I, _I, _I,
-                                            C.POINTER(State), _P, _P, _P, _P, _P]),
-    'raft_iterate_basic_ondemand_f32': (_I, [C.POINTER(BasicUpdateWeights), _P, _P, _I, _I, _I, _I, _I,
-                                        C.POINTER(State), _P, _P, _P, _P, _P]),
-    'raft_iterate_basic_final_f32': (_I, [C.POINTER(BasicUpdateWeights), _P, c_i64_p, _I, _I, _I, _I,
-                                          C.POINTER(State), _P, _P, _P, _P, _P]),
-    'raft_iterate_basic_timed_f32': (_I, [C.POINTER(BasicUpdateWeights), _P, c_i64_p, _I, _I, _I, _I,
-                                          C.POINTER(State), _P, _P, C.POINTER(C.c_float)]),
-    'raft_encoder_workspace_floats': (C.c_int64, [C.POINTER(EncoderWeights), _I, _I, _I]),
-    'raft_encoder_f32': (_I, [C.POINTER(EncoderWeights), _P, _I, _I, _I, _I, _P, _P, _P]),
-    'raft_encoder_pair_f32': (_I, [C.POINTER(EncoderWeights), _P, _P, _I, _I, _I, _I, _P, _P, _P]),
-    'raft_small_update_workspace_floats': (C.c_int64, [_I, _I, _I]),
-    'raft_prepare_state_small_f32': (_I, [_P, _I, _I, _I, C.POINTER(State), _P]),
-    'raft_update_small_f32': (_I, [C.POINTER(SmallUpdateWeights), _I, _I, _I, C.POINTER(State), _P]),
-    'raft_iterate_small_f32': (_I, [C.POINTER(SmallUpdateWeights), _P, c_i64_p, _I, _I, _I, _I,
-                                    C.POINTER(State), _P, _P]),
-    'raft_forward_interpolate_f32': (_I, [_P, _I, _I, _I, _P, _P]),
-    'raft_warm_start_f32': (_I, [_P, _I, _I, _I, C.POINTER(State), _P]),
-    'raft_warm_start_small_f32': (_I, [_P, _I, _I, _I, C.POINTER(State), _P]),
-}
+_SCALARS = {'int': C.c_int, 'float': C.c_float, 'double': C.c_double, 'int64_t': C.c_int64, 'uint64_t': C.c_uint64,
+            'uint32_t': C.c_uint32, 'size_t': C.c_size_t}
+# Structs that cross the ABI by value or as HOST pointers.  RaftAugmentParams is absent on purpose: its records lie in device
+# memory, so a pointer to them travels as void* like every other device pointer.
+_STRUCTS = {'raft_conv_weights': ConvWeights, 'raft_basic_update_weights': BasicUpdateWeights,
+            'raft_small_update_weights': SmallUpdateWeights, 'raft_encoder_weights': EncoderWeights, 'raft_state': State,
+            'RaftTileOrigins': TileOrigins}
+
+
+def _ctype(text: str, decl: str):
+    """The ctypes type of one C type of the header's closed vocabulary; ``decl`` is quoted when there is none."""
+    base, stars = ' '.join(w for w in text.replace('*', ' ').split() if w != 'const'), text.count('*')
+    if stars >= 2:                              # host arrays of pointers, the out-parameter of raft_loop_ctx_create
+        return C.POINTER(C.c_void_p)
+    if stars == 1:
+        if base == 'char':
+            return C.c_char_p
+        if base == 'int64_t':                   # host arrays: level offsets, element counts
+            return C.POINTER(C.c_int64)
+        return C.POINTER(_STRUCTS[base]) if base in _STRUCTS else C.c_void_p
+    if base in _SCALARS:
+        return _SCALARS[base]
+    if base in _STRUCTS:
+        return _STRUCTS[base]
+    raise ValueError(f'include/raft_hip.h: no ctypes type for {text.strip()!r} in the declaration {decl!r}')
+
+
+_TYPED_NAME = re.compile(r'\s*(.*?[\s\*])(\w+)\s*')       # "const float *x", "int64_t raft_f": a type, then a name
+
+
+def header_signatures(text: str) -> dict:
+    """``{name: (restype, [argtypes])}`` of every prototype in the header ``text``, in declaration order.  A declaration that
+    is no typedef, no enum and no prototype of known types raises ``ValueError``: nothing is skipped or guessed."""
+    text = re.sub(r'#ifdef __cplusplus.*?#endif', ' ', _COMMENT.sub(' ', text), flags=re.S)      # the extern "C" braces
+    text = re.sub(r'^[ \t]*#[^\n]*', ' ', text, flags=re.M)
+    text = re.sub(r'\{[^{}]*\}', ' ', text)                                                      # struct and enum bodies
+    sigs = {}
+    for decl in text.split(';'):
+        decl = ' '.join(decl.split())
+        if not decl or decl.split()[0] in ('typedef', 'enum'):
+            continue
+        head, _, params = decl.partition('(')
+        params = [] if params[:-1].strip() == 'void' else params[:-1].split(',')
+        parts = [_TYPED_NAME.fullmatch(p) for p in [head] + params]       # "return type, name" reads like a parameter
+        if not decl.endswith(')') or decl.count('(') != 1 or decl.count(')') != 1 or None in parts:
+            raise ValueError(f'include/raft_hip.h: cannot split the declaration {decl!r}')
+        res, *args = [_ctype(p[1], decl) for p in parts]
+        sigs[parts[0][2]] = (res, args)
+    return sigs
+
+
+_SIGNATURES = header_signatures(_HEADER)
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
