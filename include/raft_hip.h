@@ -691,6 +691,29 @@ int raft_photometric_loss_f32(const float *image1, const float *image2, const ui
                               float edge_weight, float eps, float upstream, float *out3, float *d_preds, double *workspace,
                               void *stream);
 
+/* Soft census term of the self-supervised loss and its gradient (csrc/census_loss.hip).  Inputs as for
+ * raft_photometric_loss_f32.  With gray(c) = (0.299f*R + 0.587f*G) + 0.114f*B on 0..255, g1 = gray(image1), w_i the bilinear sample
+ * of gray(image2) under p_i (0 out of frame), f(d) = d / sqrtf(0.81f + d*d), h(e) = e*e / (0.1f + e*e),
+ * interior(x, y) = 3 <= x <= W-4 && 3 <= y <= H-4, M_i = mask && inside_i && interior:
+ *   D(y) = (1/48) * sum over the 48 neighbours z of y in a 7x7 patch of h(f(w_i(z) - w_i(y)) - f(g1(z) - g1(y)))
+ *   cen_i = sum_y M_i(y) * D(y) / (B*H*W),     w_i = (float)gamma^(n-i-1)
+ *   out2[0] = (add_to ? *add_to : 0) + census_weight * sum_i w_i * cen_i  (formed in double, rounded once; add_to may be out2);
+ *   out2[1] = cen_{n-1}
+ * d_preds: NULL (value only), or the layout of preds; every element is touched exactly once with
+ * upstream * census_weight * w_i * d cen_i -- stored (accumulate == 0) or added to what is there with one float32 addition
+ * (accumulate == 1); gaps of a pred_stride larger than 2*B*H*W are not touched.  mask and inside are constants of the gradient;
+ * the derivatives of w_i are the one-sided ones of raft_photometric_loss_f32.
+ * Deterministic (no atomics, no memset).  `workspace`: raft_census_loss_workspace_bytes(n_predictions, B, H, W) bytes (float64
+ * partial records, g1, and per prediction the planes w_i and M_i; 0 for sizes the entry refuses).
+ * RAFT_E_NULL: image1, image2, preds, out2 or workspace NULL.  RAFT_E_SHAPE: a non-positive size, pred_stride < 2*B*H*W,
+ * B*H*W*3 of 2^31 or more, gamma / census_weight negative or not finite, upstream not finite, accumulate not 0 or 1.
+ * RAFT_E_UNSUPPORTED: n_predictions > 64 or an odd pred_stride.  RAFT_E_ALIGN: preds, d_preds or workspace not 8-byte aligned.
+ * All checks precede the first launch. */
+int64_t raft_census_loss_workspace_bytes(int n_predictions, int B, int H, int W);
+int raft_census_loss_f32(const float *image1, const float *image2, const uint8_t *mask, const float *preds, int64_t pred_stride,
+                         int n_predictions, int B, int H, int W, double gamma, float census_weight, float upstream,
+                         const float *add_to, float *out2, float *d_preds, int accumulate, void *workspace, void *stream);
+
 /* Backward of raft_corr_lookup_f32 (CorrBlock.retrieve + bilinear_sampler, corr.py:116-152, 28-69), with TensorFlow's
  * gradient conventions: floor / ceil contribute nothing, clip_by_value passes the gradient on [0, size - 1].
  * d_out: (B, h, w, ld_out) upstream gradient of the lookup output (first levels*(2r+1)^2 channels used).

@@ -1,0 +1,345 @@
+// Soft census term of the self-supervised sequence loss (no reference counterpart): the data term that
+// survives exposure changes, with d term / d prediction_i.  Definitions (every product and sum rounded on its own):
+//
+//   gray(c) = (0.299f*R + 0.587f*G) + 0.114f*B on 0..255,  g1 = gray(image1), g2 = gray(image2)
+//   w_i(x)  = inside ? bilinear(taps of flow_sample.h under p_i, g2) : 0          (the warped gray)
+//   f(d) = d / sqrtf(0.81f + d*d)   (soft ternary transform)      h(e) = e*e / (0.1f + e*e)   (soft Hamming distance)
+//   interior(x, y) = 3 <= x <= W-4 && 3 <= y <= H-4,      M_i = mask && inside_i && interior
+//   e(y, z) = f(w(z) - w(y)) - f(g1(z) - g1(y))
+//   D(y) = (sum over the 48 neighbours z of y in a 7x7 patch, rows first, of h(e(y, z))) / 48.f
+//   cen_i = sum_y M_i(y) * D(y) / (B*H*W),      out2 = {add_to + census_weight * sum_i w_i cen_i, cen_{n-1}},  w_i = (float)gamma^(n-i-1)
+//
+// Gradient as a gather (f is odd, h is even, both exactly in IEEE arithmetic, so e(z, y) = -e(y, z) and a pixel's two roles, as
+// centre and as neighbour of a centre, collapse into ONE sweep over its 7x7 window):
+//   S(y) = sum over z in frame, z != y, |z - y|_inf <= 3, rows first, of (M(y) + M(z)) * h'(e(y, z)) * f'(w(z) - w(y))
+//   h'(e) = ((2*e)*0.1f) / (q*q), q = 0.1f + e*e        f'(d) = 0.81f / (r * sqrtf(r)), r = 0.81f + d*d
+//   d cen_i / d w(y) = -S(y) / (48*B*H*W),    d/du = that * dwdu(y), d/dv = that * dwdv(y)  (the one-sided derivatives of the cell the
+//   taps come from, 0 out of frame; `inside` and `mask` are constants of the gradient)
+//
+// Mapping: three launches.  (1) census_warp_kernel, one thread per pixel and prediction: g1 once, and per prediction the warped gray
+// w_i and M_i (as 1.f / 0.f), into the workspace.  (2) census_sweep_kernel, one thread per pixel looping over the predictions: the 48
+// values f(g1(z) - g1(y)) do not depend on the prediction and are computed once per pixel (kept in the thread's own LDS column);
+// per prediction the thread reads the 7x7 windows of w_i (and of M_i for the gradient) through the cache, as photometric_loss.hip
+// reads its stencil, forms D and S from the same 48 pairs, re-gathers the four taps of g2 for dwdu / dwdv and touches its element
+// of d_preds once.  A pixel whose window lies in the frame takes a path without tests.  (3) a one-workgroup kernel adds the
+// float64 partial records in index order.  Deterministic: no atomics, no memset.
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+#include "flow_sample.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxRecords = 768;      // partial records of the sweep: 3 workgroups per CU, what its 49 KiB of LDS let a CU hold
+constexpr int kVals = 2;              // sum_i w_i * CEN_i, CEN_{n-1} (sums before normalisation)
+constexpr int kMaxPred = 64;
+constexpr int kRadius = 3, kSide = 2 * kRadius + 1;
+static_assert(kSide * kSide - 1 == 48, "the 48 neighbours of the definition");
+
+struct PredWeights {
+    float w[kMaxPred];
+};
+
+__device__ __forceinline__ float gray(const float *__restrict__ c) { return (0.299f * c[0] + 0.587f * c[1]) + 0.114f * c[2]; }
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// the four taps of gray(image2) of one image for a sample
+__device__ __forceinline__ void gray_taps(const float *__restrict__ i2, const Taps &t, float (&q)[4]) {
+    q[0] = gray(i2 + (int64_t)t.o00 * 3);
+    q[1] = gray(i2 + (int64_t)t.o01 * 3);
+    q[2] = gray(i2 + (int64_t)t.o10 * 3);
+    q[3] = gray(i2 + (int64_t)t.o11 * 3);
+}
+
+template <bool MASK>
+__global__ void __launch_bounds__(kThreads) census_warp_kernel(const float *__restrict__ image1, const float *__restrict__ image2,
+                                                               const uint8_t *__restrict__ mask, const float2 *__restrict__ preds,
+                                                               int64_t stride2, int B, int H, int W, float *__restrict__ g1,
+                                                               float *__restrict__ wv, float *__restrict__ valid) {
+    const int HW = H * W;
+    const int i = blockIdx.z;
+    const int64_t npix = (int64_t)B * HW;
+    for (int n = blockIdx.y; n < B; n += gridDim.y) {
+        const int64_t base = (int64_t)n * HW;
+        const float *i2 = image2 + base * 3;
+        for (int p = (int)blockIdx.x * kThreads + (int)threadIdx.x; p < HW; p += (int)gridDim.x * kThreads) {
+            const int y = p / W, x = p - y * W;
+            if (i == 0) g1[base + p] = gray(image1 + (base + p) * 3);
+            const Taps t = flow_taps(x, y, preds[(int64_t)i * stride2 + base + p], H, W);
+            float q[4];
+            gray_taps(i2, t, q);
+            const float w2 = bilinear(t, q[0], q[1], q[2], q[3]);
+            const bool use = MASK ? mask[base + p] != 0 : true;
+            const bool interior = x >= kRadius && x <= W - 1 - kRadius && y >= kRadius && y <= H - 1 - kRadius;
+            wv[(int64_t)i * npix + base + p] = t.in ? w2 : 0.f;
+            valid[(int64_t)i * npix + base + p] = (use && t.in && interior) ? 1.f : 0.f;
+        }
+    }
+}
+
+__device__ __forceinline__ float soft_sign(float d) { return d / sqrtf(0.81f + d * d); }
+
+// One pair (y, z): d = w(z) - w(y), fg = f(g1(z) - g1(y)), m = M(y) + M(z).  Adds h(e) to hs and, for the gradient, m * h'(e) * f'(d)
+// to S when `ok` (z in frame).
+template <bool GRAD>
+__device__ __forceinline__ void census_pair(float d, float fg, float m, bool ok, float &hs, float &S) {
+    const float r = 0.81f + d * d;
+    const float sr = sqrtf(r);
+    const float e = d / sr - fg;
+    const float q = 0.1f + e * e;
+    hs += (e * e) / q;
+    if (GRAD) {
+        const float term = (m * (((2.f * e) * 0.1f) / (q * q))) * (0.81f / (r * sr));
+        S += ok ? term : 0.f;
+    }
+}
+
+struct SweepArgs {
+    const float *image2;
+    const float2 *preds;
+    int64_t stride2, npix;
+    int n_pred, H, W;
+    float scale;                      // upstream * census_weight
+    float inv48n;                     // 1 / (48*B*H*W)
+    int accumulate;
+    const float *g1, *wv, *valid;         // valid: M as 1.f / 0.f, so that a window row of it loads like a row of w
+    float2 *d_preds;
+};
+
+// upstream * census_weight * w_i * d cen_i / d (u, v) of one pixel from its S: the taps of g2 are gathered again (cheaper than
+// a second and third plane per prediction in the workspace)
+__device__ __forceinline__ void census_store_grad(const SweepArgs &a, int x, int y, int64_t at, int i, float wi, float S) {
+    const int64_t n_base = at - ((int64_t)y * a.W + x);
+    const Taps t = flow_taps(x, y, a.preds[(int64_t)i * a.stride2 + at], a.H, a.W);
+    float q[4];
+    gray_taps(a.image2 + n_base * 3, t, q);
+    const float du = t.in ? (1.f - t.b) * (q[1] - q[0]) + t.b * (q[3] - q[2]) : 0.f;
+    const float dv = t.in ? (1.f - t.a) * (q[2] - q[0]) + t.a * (q[3] - q[1]) : 0.f;
+    const float gw = 0.f - (a.scale * wi) * (S * a.inv48n);
+    float2 o = make_float2(gw * du, gw * dv);
+    float2 *dst = a.d_preds + (int64_t)i * a.stride2 + at;
+    if (a.accumulate) {
+        const float2 was = *dst;
+        o.x = was.x + o.x;
+        o.y = was.y + o.y;
+    }
+    *dst = o;
+}
+
+// One row of a pixel's window: seven values of w and, for the gradient, of M.
+template <bool GRAD>
+struct WindowRow {
+    float w[kSide], m[GRAD ? kSide : 1];
+    __device__ __forceinline__ void load(const float *__restrict__ wr, const float *__restrict__ mr) {
+#pragma unroll
+        for (int dx = -kRadius; dx <= kRadius; ++dx) {
+            w[dx + kRadius] = wr[dx];
+            if (GRAD) m[dx + kRadius] = mr[dx];
+        }
+    }
+};
+
+// A pixel whose 7x7 window lies in the frame, all predictions: no tests.  The values f(g1(z) - g1(y)) do not depend on the
+// prediction: the thread computes them once and keeps them in its own column of `fg` (LDS; nobody else reads the column, so no
+// barrier).  The rows of the window are a rolled loop: unrolled 48 times the compiler keeps several hundred values in flight and
+// the gradient kernel runs at one wave per SIMD (measured: NOTEBOOK section 27).  `at` = the pixel's index over all images.
+template <bool GRAD>
+__device__ __forceinline__ void census_pixel_whole(const SweepArgs &a, const PredWeights &pw, int x, int y, int64_t at,
+                                                   float (*fg)[kThreads], double (&acc)[kVals]) {
+    const int W = a.W, tid = threadIdx.x;
+    const float *gp = a.g1 + at;
+    const float gc = gp[0];
+#pragma nounroll
+    for (int dy = -kRadius; dy <= kRadius; ++dy) {
+        const float *gr = gp + dy * W;
+#pragma unroll
+        for (int dx = -kRadius; dx <= kRadius; ++dx) fg[(dy + kRadius) * kSide + dx + kRadius][tid] = soft_sign(gr[dx] - gc);
+    }
+    for (int i = 0; i < a.n_pred; ++i) {
+        const int64_t ib = (int64_t)i * a.npix + at;
+        const float mcf = a.valid[ib];
+        const bool mc = mcf != 0.f;
+        if (!GRAD && !mc) continue;
+        const float *wp = a.wv + ib, *vp = a.valid + ib;
+        const float wc = wp[0];
+        float hs = 0.f, S = 0.f;
+        // the next row of the window is loaded before the current one is worked on (its latency hides behind ~500 instructions)
+        WindowRow<GRAD> cur, nxt;
+        cur.load(wp - kRadius * W, vp - kRadius * W);
+#pragma nounroll
+        for (int dy = -kRadius; dy <= kRadius; ++dy) {
+            const int dn = dy < kRadius ? dy + 1 : dy;          // (behind the last row: that row again, not a branch)
+            nxt.load(wp + dn * W, vp + dn * W);
+#pragma unroll
+            for (int dx = -kRadius; dx <= kRadius; ++dx) {
+                if (dy == 0 && dx == 0) continue;
+                census_pair<GRAD>(cur.w[dx + kRadius] - wc, fg[(dy + kRadius) * kSide + dx + kRadius][tid],
+                                  GRAD ? mcf + cur.m[dx + kRadius] : 0.f, true, hs, S);
+            }
+            cur = nxt;
+        }
+        if (mc) {
+            const float D = hs / 48.f;
+            acc[0] += (double)pw.w[i] * (double)D;
+            if (i == a.n_pred - 1) acc[1] += (double)D;
+        }
+        if (GRAD) census_store_grad(a, x, y, at, i, pw.w[i], S);
+    }
+}
+
+// A pixel whose window leaves the frame (gradient only: it is not interior, so M = 0 and it has no value of its own): the same
+// pairs in the same order, neighbours out of frame read at a clamped position and dropped.  Rolled loops: these are few pixels.
+__device__ __forceinline__ void census_pixel_edge(const SweepArgs &a, const PredWeights &pw, int x, int y, int64_t at) {
+    const int H = a.H, W = a.W;
+    const int64_t img = at - ((int64_t)y * W + x);
+    const float gc = a.g1[at];
+    for (int i = 0; i < a.n_pred; ++i) {
+        const float *wp = a.wv + (int64_t)i * a.npix + img;
+        const float *vp = a.valid + (int64_t)i * a.npix + img;
+        const float wc = wp[y * W + x];
+        float hs = 0.f, S = 0.f;
+#pragma nounroll
+        for (int dy = -kRadius; dy <= kRadius; ++dy) {
+#pragma nounroll
+            for (int dx = -kRadius; dx <= kRadius; ++dx) {
+                if (dy == 0 && dx == 0) continue;
+                const bool ok = y + dy >= 0 && y + dy < H && x + dx >= 0 && x + dx < W;
+                const int z = min(max(y + dy, 0), H - 1) * W + min(max(x + dx, 0), W - 1);
+                census_pair<true>(wp[z] - wc, soft_sign(a.g1[img + z] - gc), vp[z], ok, hs, S);
+            }
+        }
+        census_store_grad(a, x, y, at, i, pw.w[i], S);
+    }
+}
+
+template <bool GRAD>
+__global__ void __launch_bounds__(kThreads) census_sweep_kernel(SweepArgs a, int B, PredWeights pw, double *__restrict__ part) {
+    const int H = a.H, W = a.W, HW = H * W;
+    __shared__ float fg[kSide * kSide][kThreads];          // 49 KiB: three workgroups per CU
+    double acc[kVals] = {0.0, 0.0};
+    for (int n = blockIdx.y; n < B; n += gridDim.y) {
+        const int64_t base = (int64_t)n * HW;
+        for (int p = (int)blockIdx.x * kThreads + (int)threadIdx.x; p < HW; p += (int)gridDim.x * kThreads) {
+            const int y = p / W, x = p - y * W;
+            const bool whole = x >= kRadius && x <= W - 1 - kRadius && y >= kRadius && y <= H - 1 - kRadius;
+            if (whole)
+                census_pixel_whole<GRAD>(a, pw, x, y, base + p, fg, acc);
+            else if (GRAD)
+                census_pixel_edge(a, pw, x, y, base + p);
+        }
+    }
+    // one partial record per workgroup, numbered along x then y
+    __shared__ double sh[kThreads / 64][kVals];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int v = 0; v < kVals; ++v) {
+        const double r = wave_sum(acc[v]);
+        if (lane == 0) sh[wave][v] = r;
+    }
+    __syncthreads();
+    if (threadIdx.x < kVals) {
+        const int64_t rec = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+        part[rec * kVals + threadIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+    }
+}
+
+__global__ void __launch_bounds__(64) census_final_kernel(const double *__restrict__ part, int nparts, double inv, double census_weight,
+                                                          const float *add_to, float *out2) {
+    __shared__ double tot[kVals];
+    if (threadIdx.x < kVals) {
+        double s = 0.0;
+        for (int r = 0; r < nparts; ++r) s += part[(int64_t)r * kVals + threadIdx.x];
+        tot[threadIdx.x] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double before = add_to != nullptr ? (double)add_to[0] : 0.0;      // (read before out2 is written: they may be one address)
+        out2[0] = (float)(before + census_weight * (tot[0] * inv));
+        out2[1] = (float)(tot[1] * inv);
+    }
+}
+
+bool finite_nonneg(double v) { return v >= 0.0 && v <= 3.402823466e38; }      // (a NaN fails)
+
+constexpr int64_t kRecordBytes = (int64_t)kMaxRecords * kVals * (int64_t)sizeof(double);
+
+bool shape_ok(int n_predictions, int B, int H, int W) {
+    if (!(n_predictions > 0 && B > 0 && H > 0 && W > 0)) return false;
+    const int64_t limit = ((int64_t)1 << 31) - 1;
+    return (int64_t)B <= limit / H && (int64_t)B * H <= limit / W && (int64_t)B * H * W <= limit / 3;
+}
+
+}   // namespace
+
+// records | g1: B*H*W floats | w: n*B*H*W floats | M: n*B*H*W floats
+extern "C" int64_t raft_census_loss_workspace_bytes(int n_predictions, int B, int H, int W) {
+    if (!shape_ok(n_predictions, B, H, W) || n_predictions > kMaxPred) return 0;
+    const int64_t npix = (int64_t)B * H * W;
+    return kRecordBytes + 4 * npix + 8 * npix * n_predictions;
+}
+
+extern "C" int raft_census_loss_f32(const float *image1, const float *image2, const uint8_t *mask, const float *preds,
+                                    int64_t pred_stride, int n_predictions, int B, int H, int W, double gamma, float census_weight,
+                                    float upstream, const float *add_to, float *out2, float *d_preds, int accumulate, void *workspace,
+                                    void *stream) {
+    RAFT_REQUIRE_PTR(image1);
+    RAFT_REQUIRE_PTR(image2);
+    RAFT_REQUIRE_PTR(preds);
+    RAFT_REQUIRE_PTR(out2);
+    RAFT_REQUIRE_PTR(workspace);
+    RAFT_REQUIRE(shape_ok(n_predictions, B, H, W), RAFT_E_SHAPE);
+    const int64_t npix = (int64_t)B * H * W;
+    RAFT_REQUIRE(pred_stride >= 2 * npix, RAFT_E_SHAPE);
+    RAFT_REQUIRE(n_predictions <= kMaxPred && (pred_stride & 1) == 0, RAFT_E_UNSUPPORTED);
+    RAFT_REQUIRE(finite_nonneg(gamma) && finite_nonneg(census_weight), RAFT_E_SHAPE);
+    RAFT_REQUIRE(upstream >= -3.402823466e38f && upstream <= 3.402823466e38f, RAFT_E_SHAPE);
+    RAFT_REQUIRE(accumulate == 0 || accumulate == 1, RAFT_E_SHAPE);
+    RAFT_REQUIRE(((((uintptr_t)preds) | ((uintptr_t)d_preds) | ((uintptr_t)workspace)) & 7u) == 0, RAFT_E_ALIGN);   // float2 / double
+
+    PredWeights pw = {};
+    for (int i = 0; i < n_predictions; ++i) {     // gamma ** (n - i - 1) in double, rounded to fp32 once: as raft_sequence_loss_f32
+        double w = 1.0;
+        for (int j = 0; j < n_predictions - i - 1; ++j) w *= gamma;
+        pw.w[i] = (float)w;
+    }
+    double *part = (double *)workspace;
+    float *g1 = (float *)((char *)workspace + kRecordBytes);
+    float *wv = g1 + npix;
+    float *valid = wv + npix * n_predictions;
+    hipStream_t s = (hipStream_t)stream;
+    const float2 *pr = (const float2 *)preds;
+    const int64_t stride2 = pred_stride / 2;
+    const int64_t blocks = ((int64_t)H * W + kThreads - 1) / kThreads;
+    {
+        const dim3 grid((unsigned)(blocks < 1024 ? blocks : 1024), (unsigned)(B < 64 ? B : 64), (unsigned)n_predictions);
+        if (mask != nullptr)
+            census_warp_kernel<true><<<grid, kThreads, 0, s>>>(image1, image2, mask, pr, stride2, B, H, W, g1, wv, valid);
+        else
+            census_warp_kernel<false><<<grid, kThreads, 0, s>>>(image1, image2, mask, pr, stride2, B, H, W, g1, wv, valid);
+        RAFT_TRY(raft_launch_status());
+    }
+    SweepArgs a;
+    a.image2 = image2, a.preds = pr, a.stride2 = stride2, a.npix = npix, a.n_pred = n_predictions, a.H = H, a.W = W;
+    a.scale = upstream * census_weight;
+    a.inv48n = (float)(1.0 / (48.0 * (double)npix));
+    a.accumulate = accumulate;
+    a.g1 = g1, a.wv = wv, a.valid = valid, a.d_preds = (float2 *)d_preds;
+    const int gy = B < kMaxRecords ? B : kMaxRecords;
+    const int64_t cap = kMaxRecords / gy;
+    const int gx = (int)(blocks < cap ? blocks : cap);
+    const dim3 grid((unsigned)gx, (unsigned)gy);
+    if (d_preds != nullptr)
+        census_sweep_kernel<true><<<grid, kThreads, 0, s>>>(a, B, pw, part);
+    else
+        census_sweep_kernel<false><<<grid, kThreads, 0, s>>>(a, B, pw, part);
+    RAFT_TRY(raft_launch_status());
+    census_final_kernel<<<1, 64, 0, s>>>(part, gx * gy, 1.0 / (double)npix, (double)census_weight, add_to, out2);
+    return raft_launch_status();
+}

@@ -228,19 +228,23 @@ def sequence_loss_grad(y_true, y_pred, gamma=0.8, max_flow=400, upstream=1.0):
     return [_dev.wrap(out[i]) for i in range(n)]
 
 
-def photometric_sequence_loss_value_and_grad(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, upstream=1.0):
+def photometric_sequence_loss_value_and_grad(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, upstream=1.0,
+                                             census_weight=0.0):
     """``(terms, grads)`` of ``losses.PhotometricSequenceLoss`` from ONE launch: ``terms`` is
     ``{'loss', 'photometric', 'smoothness'}`` and ``grads[i]`` = ``upstream * d loss / d y_pred[i]``, shaped like the predictions.
-    ``y_true = (image1, image2)`` or ``(image1, image2, mask)``."""
+    ``y_true = (image1, image2)`` or ``(image1, image2, mask)``.  With ``census_weight > 0`` the census entry follows on the same
+    stream and adds its share to both (section 18); ``terms`` then has ``'census'`` too."""
     from . import losses
-    out, d = losses._photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, upstream=upstream, want_grad=True)
+    out, d = losses._photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, upstream=upstream, want_grad=True,
+                                        census_weight=census_weight)
     return losses._photometric_terms(out), [] if d is None else [_dev.wrap(d[i]) for i in range(d.shape[0])]
 
 
-def photometric_sequence_loss_grad(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, upstream=1.0):
+def photometric_sequence_loss_grad(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, upstream=1.0,
+                                   census_weight=0.0):
     """``upstream * d PhotometricSequenceLoss(...)(y_true, y_pred) / d y_pred[i]`` for every i: list of tensors shaped like the
     predictions."""
-    return photometric_sequence_loss_value_and_grad(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, upstream)[1]
+    return photometric_sequence_loss_value_and_grad(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, upstream, census_weight)[1]
 
 
 def corr_lookup_backward(corr_block, coords, d_out, d_pyramid=None, want_pyramid_grad=True):

@@ -6,7 +6,7 @@
 
 and the self-supervised loss the reference does not have (csrc/photometric_loss.hip):
 
-    PhotometricSequenceLoss(gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01)
+    PhotometricSequenceLoss(gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, census_weight=0.0)
     photometric_sequence_loss(y_true, y_pred, ...)                y_true = (image1, image2) or (image1, image2, mask)
 
 ``y_true = (flow_gt, valid)`` with ``flow_gt`` (bs, H, W, 2) float and ``valid`` (bs, H, W) bool; ``y_pred`` is the list
@@ -83,6 +83,7 @@ def sequence_loss(y_true, y_pred, gamma=0.8, max_flow=400):
 # ---------------------------------------------------------------- self-supervised: photometric + smoothness
 _F32_MAX = 3.402823466e38
 _PHOTOMETRIC_WS = {}
+_CENSUS_WS = {}
 
 
 def _photometric_workspace(device):
@@ -101,6 +102,14 @@ def _real(name, v):
         return float(v)
     except (TypeError, ValueError) as exc:
         raise ValueError(f'{name} must be a real number, got {v!r}') from exc
+
+
+def _census_weight(census_weight):
+    """``census_weight`` as raft_census_loss_f32 checks it: finite and >= 0."""
+    v = _real('census_weight', census_weight)
+    if not 0.0 <= v <= _F32_MAX:
+        raise ValueError(f'census_weight must be finite and >= 0, got {v!r}')
+    return v
 
 
 def _photometric_params(gamma, smooth_weight, edge_weight, eps, upstream=1.0):
@@ -167,17 +176,36 @@ def _mask_to_device(mask, device):
     return (mask != 0).to(device=device, dtype=torch.uint8).contiguous()
 
 
-def _photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, upstream=1.0, want_grad=False):
-    """One raft_photometric_loss_f32 call: ``(out3, d_preds)`` -- out3 = device ``[loss, photometric, smoothness]`` (the last
-    two of the LAST prediction), d_preds the stacked gradients ``(n, B, H, W, 2)`` or None."""
+def _census_workspace(device, nbytes):
+    """One grow-only buffer per device (the launches of a stream are ordered, so one buffer serves them all)."""
+    key = (device.type, device.index)
+    ws = _CENSUS_WS.get(key)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=device)
+        _CENSUS_WS[key] = ws
+    return ws
+
+
+def _photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, upstream=1.0, want_grad=False, census_weight=0.0):
+    """One raft_photometric_loss_f32 call: ``(out, d_preds)`` -- ``out`` maps 'loss', 'photometric', 'smoothness' to elements of
+    one device buffer (the last two of the LAST prediction), d_preds is the stacked gradients ``(n, B, H, W, 2)`` or None.
+    With ``census_weight > 0`` a raft_census_loss_f32 call follows on the same stream: it adds its term
+    to the loss and its gradient to d_preds on the device, and ``out`` gains 'census'."""
     gamma, smooth_weight, edge_weight, eps, upstream = _photometric_params(gamma, smooth_weight, edge_weight, eps, upstream)
+    census_weight = _census_weight(census_weight)
     image1, image2, mask, preds, (B, H, W) = _check_unlabelled(y_true, y_pred)
     image1 = _dev.to_device(image1).as_subclass(torch.Tensor)
     image2 = _dev.to_device(image2).as_subclass(torch.Tensor)
     if mask is not None:
         mask = _mask_to_device(mask, image1.device)
     n = len(preds)
-    out = torch.zeros((3,), dtype=torch.float32, device=image1.device)
+    census = census_weight > 0.0
+    # [loss, photometric, smoothness], and behind them [loss with the census term, census]
+    buf = torch.zeros((5 if census else 3,), dtype=torch.float32, device=image1.device)
+    out = {'loss': buf[3] if census else buf[0], 'photometric': buf[1]}
+    if census:
+        out['census'] = buf[4]
+    out['smoothness'] = buf[2]
     if n == 0:
         return out, None
     preds = [_dev.to_device(p).as_subclass(torch.Tensor).to(torch.float32) for p in preds]
@@ -187,16 +215,23 @@ def _photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, 
     in_place = all(p.is_contiguous() and p.data_ptr() == base.data_ptr() + 4 * stride * i for i, p in enumerate(preds))
     stacked = base if in_place else torch.stack([p.contiguous() for p in preds])
     d_preds = torch.empty((n, B, H, W, 2), dtype=torch.float32, device=image1.device) if want_grad else None
-    check(_dev.lib().raft_photometric_loss_f32(_dev.ptr(image1), _dev.ptr(image2), _dev.ptr(mask) if mask is not None else None,
-                                               _dev.ptr(stacked), stride, n, B, H, W, gamma, smooth_weight, edge_weight, eps,
-                                               upstream, _dev.ptr(out), _dev.ptr(d_preds) if want_grad else None,
-                                               _dev.ptr(_photometric_workspace(out.device)), _dev.stream_ptr()),
+    lib = _dev.lib()
+    check(lib.raft_photometric_loss_f32(_dev.ptr(image1), _dev.ptr(image2), _dev.ptr(mask) if mask is not None else None,
+                                        _dev.ptr(stacked), stride, n, B, H, W, gamma, smooth_weight, edge_weight, eps,
+                                        upstream, _dev.ptr(buf), _dev.ptr(d_preds) if want_grad else None,
+                                        _dev.ptr(_photometric_workspace(buf.device)), _dev.stream_ptr()),
           'photometric_loss')
+    if census:
+        ws = _census_workspace(buf.device, int(lib.raft_census_loss_workspace_bytes(n, B, H, W)))
+        check(lib.raft_census_loss_f32(_dev.ptr(image1), _dev.ptr(image2), _dev.ptr(mask) if mask is not None else None,
+                                       _dev.ptr(stacked), stride, n, B, H, W, gamma, census_weight, upstream, _dev.ptr(buf),
+                                       _dev.ptr(buf[3:]), _dev.ptr(d_preds) if want_grad else None, 1, _dev.ptr(ws),
+                                       _dev.stream_ptr()), 'census_loss')
     return out, d_preds
 
 
 def _photometric_terms(out):
-    return {k: _dev.wrap(out[i]) for i, k in enumerate(('loss', 'photometric', 'smoothness'))}
+    return {k: _dev.wrap(v) for k, v in out.items()}
 
 
 class PhotometricSequenceLoss:
@@ -205,26 +240,33 @@ class PhotometricSequenceLoss:
     frame and, if given, in ``mask``) and ``sm_i`` the edge-aware first-order smoothness of prediction i.
     ``y_true = (image1, image2)`` or ``(image1, image2, mask)``: images ``(B, H, W, 3)`` in 0..255, ``mask`` ``(B, H, W)``,
     nonzero = use the pixel (e.g. ``predict_step_bidirectional(...).occluded_forward == 0``).
-    ``smooth_weight``, ``edge_weight`` and ``eps`` are choices, not tuned values.  ``RAFT.compile(loss=PhotometricSequenceLoss())``
+    ``census_weight > 0`` adds ``census_weight * cen_i`` to every prediction's term: the soft census distance (7x7 patches of
+    gray values, UnFlow's constants) between frame 1 and the warped frame 2, a data term that does not assume brightness
+    constancy.
+    ``smooth_weight``, ``edge_weight`` and ``eps`` are choices, not tuned values, and ``census_weight`` has no tuned default
+    either (0 = the term is off): nothing here was trained on real footage.  ``RAFT.compile(loss=PhotometricSequenceLoss())``
     makes ``train_step`` take unlabelled pairs."""
 
-    def __init__(self, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01):
+    def __init__(self, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, census_weight=0.0):
         self.gamma, self.smooth_weight, self.edge_weight, self.eps, _ = _photometric_params(gamma, smooth_weight, edge_weight, eps)
+        self.census_weight = _census_weight(census_weight)
 
     def _params(self):
-        return dict(gamma=self.gamma, smooth_weight=self.smooth_weight, edge_weight=self.edge_weight, eps=self.eps)
+        return dict(gamma=self.gamma, smooth_weight=self.smooth_weight, edge_weight=self.edge_weight, eps=self.eps,
+                    census_weight=self.census_weight)
 
     def terms(self, y_true, y_pred):
-        """``{'loss', 'photometric', 'smoothness'}``: the loss, and the two terms of the LAST prediction (0-d device scalars)."""
+        """``{'loss', 'photometric', 'smoothness'}``, with ``census_weight > 0`` also ``'census'``: the loss, and the terms of the
+        LAST prediction (0-d device scalars)."""
         return _photometric_terms(_photometric_launch(y_true, y_pred, **self._params())[0])
 
     def __call__(self, y_true, y_pred):
         return self.terms(y_true, y_pred)['loss']
 
 
-def photometric_sequence_loss(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01):
-    """``PhotometricSequenceLoss(gamma, smooth_weight, edge_weight, eps)(y_true, y_pred)``."""
-    return PhotometricSequenceLoss(gamma, smooth_weight, edge_weight, eps)(y_true, y_pred)
+def photometric_sequence_loss(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, census_weight=0.0):
+    """``PhotometricSequenceLoss(gamma, smooth_weight, edge_weight, eps, census_weight)(y_true, y_pred)``."""
+    return PhotometricSequenceLoss(gamma, smooth_weight, edge_weight, eps, census_weight)(y_true, y_pred)
 
 
 def _metrics(y_true, y_pred, max_flow):

@@ -681,7 +681,7 @@ class RAFT:
         """reference model.py:111-124.  ``loss`` / ``epe`` default to ``tf_raft_amd.losses.sequence_loss`` /
         ``end_point_error``; ``loss=losses.PhotometricSequenceLoss(...)`` makes ``train_step`` take unlabelled pairs
         ``(image1, image2)`` or ``(image1, image2, mask)`` and report ``loss`` / ``photometric`` / ``smoothness`` (DESIGN.md
-        section 17; ``test_step`` still wants ground truth).  ``trainable``: which weights ``train_step`` updates -- ``'all'``
+        section 17; ``test_step`` still wants ground truth), and ``census`` when the loss has ``census_weight > 0`` (section 18).  ``trainable``: which weights ``train_step`` updates -- ``'all'``
         (the reference's behaviour: encoders, norms and update block) or ``'update_block'`` (encoders frozen, run by the
         inference kernels)."""
         from . import losses
@@ -700,7 +700,11 @@ class RAFT:
         self.tape_dtype = tape_dtype
         self.flow_metrics = OrderedDict((k, losses.Mean(name=k)) for k in ('loss', 'epe', 'u1', 'u3', 'u5'))
         if isinstance(self.loss, losses.PhotometricSequenceLoss):       # (the EPE means stay: test_step feeds them)
-            self.flow_metrics.update((k, losses.Mean(name=k)) for k in ('photometric', 'smoothness'))
+            self.flow_metrics.update((k, losses.Mean(name=k)) for k in self._unlabelled_keys()[1:])
+
+    def _unlabelled_keys(self):
+        """What ``train_step`` reports under a PhotometricSequenceLoss."""
+        return ('loss', 'photometric', 'census', 'smoothness') if self.loss.census_weight > 0 else ('loss', 'photometric', 'smoothness')
 
     BN_MOMENTUM = 0.99      # Keras BatchNormalization default (extractor.py:10 passes none)
 
@@ -835,9 +839,9 @@ class RAFT:
         self._host_stale = True
         self._inference_stale = True
         if photometric:
-            for k in ('loss', 'photometric', 'smoothness'):
+            for k in self._unlabelled_keys():
                 self.flow_metrics[k].update_state(terms[k])
-            return {k: self.flow_metrics[k].result() for k in ('loss', 'photometric', 'smoothness')}
+            return {k: self.flow_metrics[k].result() for k in self._unlabelled_keys()}
         info = self.epe([flow, valid], preds[-1])
         self.flow_metrics['loss'].update_state(loss)
         for k in ('epe', 'u1', 'u3', 'u5'):
