@@ -13,7 +13,7 @@
 // stand-ins tests/augstub do): integer arithmetic where OpenCV uses fixed point, and individually rounded IEEE operations
 // elsewhere -- contraction into fused multiply-adds is switched off for this file, and the roundings that matter are spelled
 // with the __f*_rn / __d*_rn intrinsics as well.
-#include "common.h"
+#include "loss_common.h"
 
 #pragma clang fp contract(off)
 
@@ -114,12 +114,6 @@ __device__ __forceinline__ Rgb load_rgb(const uint8_t *img, int64_t pixel) {
     return {p[0], p[1], p[2]};
 }
 
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ------------------------------------------------------------------ channel sums of colour-mapped frame 2
 __global__ void __launch_bounds__(kThreads) augment_sums_kernel(const uint8_t *__restrict__ img2, const RaftAugmentParams *__restrict__ params,
                                                                 unsigned *__restrict__ partial, int HW) {
@@ -141,9 +135,9 @@ __global__ void __launch_bounds__(kThreads) augment_sums_kernel(const uint8_t *_
         sg += c.g;
         sb += c.b;
     }
-    sr = wave_sum(sr);
-    sg = wave_sum(sg);
-    sb = wave_sum(sb);
+    sr = raft_wave_sum(sr);
+    sg = raft_wave_sum(sg);
+    sb = raft_wave_sum(sb);
     if ((threadIdx.x & 63) == 0) {
         wsum[threadIdx.x >> 6][0] = sr;
         wsum[threadIdx.x >> 6][1] = sg;
@@ -214,7 +208,7 @@ __device__ __forceinline__ void gather_prologue(Shared &sh, const RaftAugmentPar
     if ((p.color[0] | p.color[1]) & 2) fill_hsv_tables(sh.sdiv, sh.hdiv);
     if (p.n_rect > 0 && threadIdx.x < 64) {         // the first wave adds the partial sums up
         const unsigned *ps = partial + ((int64_t)n * kSumBlocks + threadIdx.x) * 4;
-        const unsigned sr = wave_sum(ps[0]), sg = wave_sum(ps[1]), sb = wave_sum(ps[2]);
+        const unsigned sr = raft_wave_sum(ps[0]), sg = raft_wave_sum(ps[1]), sb = raft_wave_sum(ps[2]);
         if (threadIdx.x == 0) {
             const unsigned hw = (unsigned)HW;
             sh.mean[0] = (int)(sr / hw);

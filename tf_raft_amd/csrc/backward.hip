@@ -1,67 +1,17 @@
 // First slice of the training step (reference tf_raft/model.py:126-144 under tf.GradientTape), gfx950:
 //
-//   raft_sequence_loss_grad_f32    d sequence_loss / d prediction_i                       [losses.py:4-21]
 //   raft_corr_lookup_backward_f32  backward of CorrBlock.retrieve + bilinear_sampler: gradient w.r.t. the lookup
 //                                  coordinates and w.r.t. the correlation pyramid           [corr.py:116-152, 28-69]
 //   raft_conv2d_wgrad_f32          d Conv2D / d kernel and d bias (stride 1, 'same')       [update.py:10-11, 91-95, 138-140]
 //   raft_relu_backward_f32         dy * (y > 0)
 // (d Conv2D / d input needs no kernel of its own: it is the forward convolution of dy with the spatially flipped,
-//  in/out-transposed kernel -- tf_raft_amd/packing.py pack_conv_dgrad + raft_conv2d_f32.)
+//  in/out-transposed kernel -- tf_raft_amd/packing.py pack_conv_dgrad + raft_conv2d_f32.  The step before these,
+//  d sequence_loss / d prediction_i, is raft_sequence_loss_grad_f32 in metrics.hip, next to the loss.)
 //
 // All reductions are deterministic: no atomics anywhere; a correlation map is owned by its query (one wavefront), weight
 // gradients are split over pixel slices into a workspace and added in slice order by a second kernel.
-#include "common.h"
+#include "loss_common.h"
 #include "lookup_common.h"
-
-// ------------------------------------------------------------------------------------------------
-// sequence_loss backward: loss = sum_i w_i * mean over 2*npix elements of m * |p_i - g|, w_i = gamma^(n-i-1)
-//   d loss / d p_i[e] = upstream * w_i * m * sign(p_i[e] - g[e]) / (2 * npix)        (sign(0) = 0, as tf.abs)
-// ------------------------------------------------------------------------------------------------
-namespace {
-constexpr int MAX_PRED = 64;
-struct LossWeights {
-    float w[MAX_PRED];
-};
-
-__global__ void __launch_bounds__(256) sequence_loss_grad_kernel(const float2 *__restrict__ gt, const unsigned char *__restrict__ valid,
-                                                                  const float2 *__restrict__ preds, int64_t pred_stride, int n_pred,
-                                                                  int64_t npix, float max_flow, LossWeights lw,
-                                                                  float2 *__restrict__ d_preds) {
-#pragma clang fp contract(off)
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= npix) return;
-    const float2 g = gt[i];
-    const float mag = sqrtf(g.x * g.x + g.y * g.y);                       // losses.py:11
-    const float m = (valid[i] != 0 && mag < max_flow) ? 1.0f : 0.0f;
-    auto sgn = [](float v) { return v > 0.f ? 1.0f : (v < 0.f ? -1.0f : 0.0f); };
-    for (int k = 0; k < n_pred; ++k) {
-        const float2 p = preds[(int64_t)k * pred_stride + i];
-        d_preds[(int64_t)k * pred_stride + i] = make_float2(lw.w[k] * m * sgn(p.x - g.x), lw.w[k] * m * sgn(p.y - g.y));
-    }
-}
-}   // namespace
-
-extern "C" int raft_sequence_loss_grad_f32(const float *flow_gt, const unsigned char *valid, const float *preds,
-                                           int64_t pred_stride, int n_predictions, int64_t npix, double gamma, float max_flow,
-                                           float upstream, float *d_preds, void *stream) {
-    RAFT_REQUIRE_PTR(flow_gt);
-    RAFT_REQUIRE_PTR(valid);
-    RAFT_REQUIRE_PTR(preds);
-    RAFT_REQUIRE_PTR(d_preds);
-    RAFT_REQUIRE(npix > 0 && n_predictions > 0 && pred_stride >= npix * 2, RAFT_E_SHAPE);
-    RAFT_REQUIRE(n_predictions <= MAX_PRED && (pred_stride & 1) == 0, RAFT_E_UNSUPPORTED);
-    RAFT_REQUIRE(((uintptr_t)flow_gt & 7) == 0 && ((uintptr_t)preds & 7) == 0 && ((uintptr_t)d_preds & 7) == 0, RAFT_E_ALIGN);
-    LossWeights lw = {};
-    for (int i = 0; i < n_predictions; ++i) {
-        double w = 1.0;
-        for (int k = 0; k < n_predictions - i - 1; ++k) w *= gamma;
-        lw.w[i] = (float)(w * (double)upstream / (2.0 * (double)npix));
-    }
-    sequence_loss_grad_kernel<<<raft_ceil_div(npix, 256), 256, 0, (hipStream_t)stream>>>(
-        (const float2 *)flow_gt, valid, (const float2 *)preds, pred_stride / 2, n_predictions, npix, max_flow, lw,
-        (float2 *)d_preds);
-    return raft_launch_status();
-}
 
 // ------------------------------------------------------------------------------------------------
 // corr_lookup backward.  Forward (corr.py:116-152): for level l, tap (a, b):
@@ -169,11 +119,7 @@ __global__ void __launch_bounds__(256) corr_lookup_backward_kernel(LookupBwdArgs
         __builtin_amdgcn_wave_barrier();                                 // the next level overwrites the LDS tables
     }
     // fixed-order butterfly: deterministic
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        acc_x += __shfl_xor(acc_x, o, 64);
-        acc_y += __shfl_xor(acc_y, o, 64);
-    }
+    raft_wave_sum_each(acc_x, acc_y);
     if (lane == 0) *(float2 *)(p.d_coords + 2 * q) = make_float2(acc_x, acc_y);
 }
 }   // namespace
@@ -625,11 +571,7 @@ __global__ void __launch_bounds__(256) conv7x7_c2_dgrad_kernel(const float *__re
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        a0 += __shfl_xor(a0, o, 64);
-        a1 += __shfl_xor(a1, o, 64);
-    }
+    raft_wave_sum_each(a0, a1);
     if (lane == 0) ((float2 *)dflow)[p] = make_float2(a0, a1);
 }
 
@@ -745,6 +687,9 @@ __global__ void __launch_bounds__(256) upsample_convex_bwd_kernel(const float *_
     for (int k = 0; k < 9; ++k) {
         dm[k] = mk[k] * (s[k] - sbar);
         float tx = 8.0f * mk[k] * g.x, ty = 8.0f * mk[k] * g.y;
+        // raft_wave_sum_each(tx, ty), written out: through the helper (in any form: it is optimised on its own before it is
+        // inlined) the same instructions of this 9x unrolled body are scheduled differently, 46 VGPRs for 48.  That schedule
+        // was never timed, so the kernel keeps the one the training profiles were taken with
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             tx += __shfl_xor(tx, o, 64);
@@ -809,8 +754,7 @@ __global__ void __launch_bounds__(256) sumsq_partial_kernel(const float *__restr
         const double v = (double)x[i];
         acc += v * v;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = raft_wave_sum(acc);
     __shared__ double sh[4];
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
     __syncthreads();

@@ -22,8 +22,8 @@
 // per prediction the thread reads the 7x7 windows of w_i (and of M_i for the gradient) through the cache, as photometric_loss.hip
 // reads its stencil, forms D and S from the same 48 pairs, re-gathers the four taps of g2 for dwdu / dwdv and touches its element
 // of d_preds once.  A pixel whose window lies in the frame takes a path without tests.  (3) a one-workgroup kernel adds the
-// float64 partial records in index order.  Deterministic: no atomics, no memset.
-#include "common.h"
+// sweep's records and normalises.  Deterministic: the reduction of loss_common.h.
+#include "loss_common.h"
 
 #pragma clang fp contract(off)
 
@@ -31,24 +31,13 @@
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = 256;         // (what raft_block_sum_store and raft_record_grid take a workgroup to be)
 constexpr int kMaxRecords = 768;      // partial records of the sweep: 3 workgroups per CU, what its 49 KiB of LDS let a CU hold
 constexpr int kVals = 2;              // sum_i w_i * CEN_i, CEN_{n-1} (sums before normalisation)
-constexpr int kMaxPred = 64;
 constexpr int kRadius = 3, kSide = 2 * kRadius + 1;
 static_assert(kSide * kSide - 1 == 48, "the 48 neighbours of the definition");
 
-struct PredWeights {
-    float w[kMaxPred];
-};
-
 __device__ __forceinline__ float gray(const float *__restrict__ c) { return (0.299f * c[0] + 0.587f * c[1]) + 0.114f * c[2]; }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // the four taps of gray(image2) of one image for a sample
 __device__ __forceinline__ void gray_taps(const float *__restrict__ i2, const Taps &t, float (&q)[4]) {
@@ -235,30 +224,13 @@ __global__ void __launch_bounds__(kThreads) census_sweep_kernel(SweepArgs a, int
                 census_pixel_edge(a, pw, x, y, base + p);
         }
     }
-    // one partial record per workgroup, numbered along x then y
-    __shared__ double sh[kThreads / 64][kVals];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int v = 0; v < kVals; ++v) {
-        const double r = wave_sum(acc[v]);
-        if (lane == 0) sh[wave][v] = r;
-    }
-    __syncthreads();
-    if (threadIdx.x < kVals) {
-        const int64_t rec = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-        part[rec * kVals + threadIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
-    }
+    raft_block_sum_store(acc, part);
 }
 
 __global__ void __launch_bounds__(64) census_final_kernel(const double *__restrict__ part, int nparts, double inv, double census_weight,
                                                           const float *add_to, float *out2) {
     __shared__ double tot[kVals];
-    if (threadIdx.x < kVals) {
-        double s = 0.0;
-        for (int r = 0; r < nparts; ++r) s += part[(int64_t)r * kVals + threadIdx.x];
-        tot[threadIdx.x] = s;
-    }
-    __syncthreads();
+    raft_sum_records(part, nparts, tot);
     if (threadIdx.x == 0) {
         const double before = add_to != nullptr ? (double)add_to[0] : 0.0;      // (read before out2 is written: they may be one address)
         out2[0] = (float)(before + census_weight * (tot[0] * inv));
@@ -266,21 +238,13 @@ __global__ void __launch_bounds__(64) census_final_kernel(const double *__restri
     }
 }
 
-bool finite_nonneg(double v) { return v >= 0.0 && v <= 3.402823466e38; }      // (a NaN fails)
-
 constexpr int64_t kRecordBytes = (int64_t)kMaxRecords * kVals * (int64_t)sizeof(double);
-
-bool shape_ok(int n_predictions, int B, int H, int W) {
-    if (!(n_predictions > 0 && B > 0 && H > 0 && W > 0)) return false;
-    const int64_t limit = ((int64_t)1 << 31) - 1;
-    return (int64_t)B <= limit / H && (int64_t)B * H <= limit / W && (int64_t)B * H * W <= limit / 3;
-}
 
 }   // namespace
 
 // records | g1: B*H*W floats | w: n*B*H*W floats | M: n*B*H*W floats
 extern "C" int64_t raft_census_loss_workspace_bytes(int n_predictions, int B, int H, int W) {
-    if (!shape_ok(n_predictions, B, H, W) || n_predictions > kMaxPred) return 0;
+    if (!raft_loss_shape_ok(n_predictions, B, H, W) || n_predictions > kMaxPredictions) return 0;
     const int64_t npix = (int64_t)B * H * W;
     return kRecordBytes + 4 * npix + 8 * npix * n_predictions;
 }
@@ -294,21 +258,16 @@ extern "C" int raft_census_loss_f32(const float *image1, const float *image2, co
     RAFT_REQUIRE_PTR(preds);
     RAFT_REQUIRE_PTR(out2);
     RAFT_REQUIRE_PTR(workspace);
-    RAFT_REQUIRE(shape_ok(n_predictions, B, H, W), RAFT_E_SHAPE);
+    RAFT_REQUIRE(raft_loss_shape_ok(n_predictions, B, H, W), RAFT_E_SHAPE);
     const int64_t npix = (int64_t)B * H * W;
     RAFT_REQUIRE(pred_stride >= 2 * npix, RAFT_E_SHAPE);
-    RAFT_REQUIRE(n_predictions <= kMaxPred && (pred_stride & 1) == 0, RAFT_E_UNSUPPORTED);
-    RAFT_REQUIRE(finite_nonneg(gamma) && finite_nonneg(census_weight), RAFT_E_SHAPE);
-    RAFT_REQUIRE(upstream >= -3.402823466e38f && upstream <= 3.402823466e38f, RAFT_E_SHAPE);
+    RAFT_REQUIRE(n_predictions <= kMaxPredictions && (pred_stride & 1) == 0, RAFT_E_UNSUPPORTED);
+    RAFT_REQUIRE(raft_finite_nonneg(gamma) && raft_finite_nonneg(census_weight), RAFT_E_SHAPE);
+    RAFT_REQUIRE(raft_finite_f32(upstream), RAFT_E_SHAPE);
     RAFT_REQUIRE(accumulate == 0 || accumulate == 1, RAFT_E_SHAPE);
     RAFT_REQUIRE(((((uintptr_t)preds) | ((uintptr_t)d_preds) | ((uintptr_t)workspace)) & 7u) == 0, RAFT_E_ALIGN);   // float2 / double
 
-    PredWeights pw = {};
-    for (int i = 0; i < n_predictions; ++i) {     // gamma ** (n - i - 1) in double, rounded to fp32 once: as raft_sequence_loss_f32
-        double w = 1.0;
-        for (int j = 0; j < n_predictions - i - 1; ++j) w *= gamma;
-        pw.w[i] = (float)w;
-    }
+    const PredWeights pw = raft_pred_weights(gamma, n_predictions);
     double *part = (double *)workspace;
     float *g1 = (float *)((char *)workspace + kRecordBytes);
     float *wv = g1 + npix;
@@ -331,15 +290,12 @@ extern "C" int raft_census_loss_f32(const float *image1, const float *image2, co
     a.inv48n = (float)(1.0 / (48.0 * (double)npix));
     a.accumulate = accumulate;
     a.g1 = g1, a.wv = wv, a.valid = valid, a.d_preds = (float2 *)d_preds;
-    const int gy = B < kMaxRecords ? B : kMaxRecords;
-    const int64_t cap = kMaxRecords / gy;
-    const int gx = (int)(blocks < cap ? blocks : cap);
-    const dim3 grid((unsigned)gx, (unsigned)gy);
+    const dim3 grid = raft_record_grid(B, (int64_t)H * W, kMaxRecords);
     if (d_preds != nullptr)
         census_sweep_kernel<true><<<grid, kThreads, 0, s>>>(a, B, pw, part);
     else
         census_sweep_kernel<false><<<grid, kThreads, 0, s>>>(a, B, pw, part);
     RAFT_TRY(raft_launch_status());
-    census_final_kernel<<<1, 64, 0, s>>>(part, gx * gy, 1.0 / (double)npix, (double)census_weight, add_to, out2);
+    census_final_kernel<<<1, 64, 0, s>>>(part, (int)(grid.x * grid.y), 1.0 / (double)npix, (double)census_weight, add_to, out2);
     return raft_launch_status();
 }

@@ -17,7 +17,7 @@
 //
 // No atomics, no memset, no host synchronisation: the first kernel writes every one of its kFlowVizPartials partial maxima per
 // image, the second folds them in its prologue (a maximum of non-negative floats is exact in any order).
-#include "common.h"
+#include "loss_common.h"
 
 #pragma clang fp contract(off)
 
@@ -61,12 +61,6 @@ __device__ __forceinline__ float viz_clip(float x, float clip) {
     return x > clip ? clip : x;
 }
 
-__device__ __forceinline__ float wave_max(float m) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) m = fmaxf(m, __shfl_xor(m, s, 64));
-    return m;
-}
-
 // One wave owns one source row of the window at a time; blockIdx.y walks the images.  partial[n * kFlowVizPartials + blockIdx.x].
 __global__ void __launch_bounds__(256) flow_rad_max_kernel(const float2 *__restrict__ flow, float *__restrict__ partial, VizGeom g) {
     __shared__ float wave_part[4];
@@ -85,7 +79,7 @@ __global__ void __launch_bounds__(256) flow_rad_max_kernel(const float2 *__restr
                 m = fmaxf(m, sqrtf(f.x * f.x + f.y * f.y));      // flow_viz.py:127 (fmaxf: a NaN magnitude does not count)
             }
         }
-        m = wave_max(m);
+        m = raft_wave_max(m);
         __syncthreads();                                          // the previous image's wave_part has been read
         if (lane == 0) wave_part[wave] = m;
         __syncthreads();
@@ -147,7 +141,7 @@ __global__ void __launch_bounds__(256) flow_to_image_kernel(const float2 *__rest
         float rad_max = fixed_rad_max;
         if (!(fixed_rad_max > 0.f)) {
             const float *p = partial + (int64_t)n * kFlowVizPartials;
-            rad_max = wave_max(fmaxf(p[lane], p[lane + 64]));
+            rad_max = raft_wave_max(fmaxf(p[lane], p[lane + 64]));
         }
         const float d = rad_max + 1e-5f;                          // flow_viz.py:130: float32 + float32(1e-5)
         uint8_t *out = image + (int64_t)n * HW * 3;

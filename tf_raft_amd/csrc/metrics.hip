@@ -5,49 +5,18 @@
 //                           out = {mean EPE, rate EPE<1, rate EPE<3, rate EPE<5, number of valid' pixels}
 //   raft_sequence_loss_f32  sequence_loss (losses.py:4-21): sum_i gamma^(n-i-1) * mean(valid' * |pred_i - gt|), the
 //                           mean running over ALL B*H*W*2 elements; the n predictions are read in one pass
+//   raft_sequence_loss_grad_f32   d sequence_loss / d prediction_i, the first step of the training backward (grad.py)
 //
-// Both are single passes over HBM: per pixel 8 B of ground truth, 1 B of mask and 8 B per prediction.  Deterministic:
-// every thread accumulates its grid-stride pixels in float64, a workgroup reduces with shuffles + LDS into one partial
-// record, and a second one-workgroup kernel adds the partial records in index order (no atomics).
+// The first two are single passes over HBM: per pixel 8 B of ground truth, 1 B of mask and 8 B per prediction, reduced
+// with the deterministic scheme of loss_common.h (float64 accumulators, one record per workgroup, records added in index
+// order; no atomics).  The gradient is one pass with 8 B read and 8 B written per pixel and prediction.
 // The per-pixel arithmetic keeps the reference's operation order (x*x + y*y, then sqrt; fp32, no contraction).
-#include "common.h"
+#include "loss_common.h"
 
 namespace {
 
 constexpr int METRIC_WGS = 1024;      // partial records (>= 4 workgroups per CU)
 constexpr int METRIC_VALS = 5;
-constexpr int MAX_PRED = 64;
-
-struct LossWeights {
-    float w[MAX_PRED];
-};
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// reduce NV per-thread doubles over the 256 threads of a workgroup into part[blockIdx.x][NV]
-template <int NV>
-__device__ inline void block_reduce_store(double (&v)[NV], double *__restrict__ part) {
-    __shared__ double sh[4][NV];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const double s = wave_sum(v[k]);
-        if (lane == 0) sh[w][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) part[(int64_t)blockIdx.x * NV + threadIdx.x] =
-        ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
-}
-
-__device__ inline bool pixel_valid(float2 g, unsigned char v, float max_flow) {
-#pragma clang fp contract(off)
-    const float mag = sqrtf(g.x * g.x + g.y * g.y);      // losses.py:11 / 28
-    return v != 0 && mag < max_flow;
-}
 
 __global__ void __launch_bounds__(256) flow_metrics_partial_kernel(const float2 *__restrict__ gt,
                                                                     const unsigned char *__restrict__ valid,
@@ -66,18 +35,13 @@ __global__ void __launch_bounds__(256) flow_metrics_partial_kernel(const float2 
         acc[3] += epe < 5.0f ? 1.0 : 0.0;
         acc[4] += 1.0;
     }
-    block_reduce_store<METRIC_VALS>(acc, part);
+    raft_block_sum_store<false>(acc, part);      // a 1-D grid
 }
 
 __global__ void __launch_bounds__(256) flow_metrics_final_kernel(const double *__restrict__ part, int nparts,
                                                                   float *__restrict__ out) {
     __shared__ double tot[METRIC_VALS];
-    if (threadIdx.x < METRIC_VALS) {
-        double s = 0.0;
-        for (int k = 0; k < nparts; ++k) s += part[(int64_t)k * METRIC_VALS + threadIdx.x];
-        tot[threadIdx.x] = s;
-    }
-    __syncthreads();
+    raft_sum_records(part, nparts, tot);
     if (threadIdx.x < METRIC_VALS) {
         // the mean of an empty selection is NaN, as tf.reduce_mean of an empty tensor
         const double n = tot[4];
@@ -88,7 +52,7 @@ __global__ void __launch_bounds__(256) flow_metrics_final_kernel(const double *_
 __global__ void __launch_bounds__(256) sequence_loss_partial_kernel(const float2 *__restrict__ gt,
                                                                      const unsigned char *__restrict__ valid,
                                                                      const float2 *__restrict__ preds, int64_t pred_stride,
-                                                                     int n_pred, int64_t npix, float max_flow, LossWeights lw,
+                                                                     int n_pred, int64_t npix, float max_flow, PredWeights lw,
                                                                      double *__restrict__ part) {
 #pragma clang fp contract(off)
     double acc[1] = {0.0};
@@ -104,15 +68,31 @@ __global__ void __launch_bounds__(256) sequence_loss_partial_kernel(const float2
         }
         acc[0] += s;
     }
-    block_reduce_store<1>(acc, part);
+    raft_block_sum_store<false>(acc, part);      // a 1-D grid
 }
 
 __global__ void __launch_bounds__(64) sequence_loss_final_kernel(const double *__restrict__ part, int nparts, double inv_count,
                                                                   float *__restrict__ out) {
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int k = 0; k < nparts; ++k) s += part[k];
-        out[0] = (float)(s * inv_count);
+    double tot[1];                                        // thread 0's own: nobody else reads the total
+    raft_sum_records(part, nparts, tot);
+    if (threadIdx.x == 0) out[0] = (float)(tot[0] * inv_count);
+}
+
+// d loss / d p_i[e] = upstream * w_i * m * sign(p_i[e] - g[e]) / (2 * npix)        (sign(0) = 0, as tf.abs); the host folds
+// upstream / (2 * npix) into the weights
+__global__ void __launch_bounds__(256) sequence_loss_grad_kernel(const float2 *__restrict__ gt, const unsigned char *__restrict__ valid,
+                                                                  const float2 *__restrict__ preds, int64_t pred_stride, int n_pred,
+                                                                  int64_t npix, float max_flow, PredWeights lw,
+                                                                  float2 *__restrict__ d_preds) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= npix) return;
+    const float2 g = gt[i];
+    const float m = pixel_valid(g, valid[i], max_flow) ? 1.0f : 0.0f;
+    auto sgn = [](float v) { return v > 0.f ? 1.0f : (v < 0.f ? -1.0f : 0.0f); };
+    for (int k = 0; k < n_pred; ++k) {
+        const float2 p = preds[(int64_t)k * pred_stride + i];
+        d_preds[(int64_t)k * pred_stride + i] = make_float2(lw.w[k] * m * sgn(p.x - g.x), lw.w[k] * m * sgn(p.y - g.y));
     }
 }
 
@@ -152,19 +132,30 @@ extern "C" int raft_sequence_loss_f32(const float *flow_gt, const unsigned char 
     RAFT_REQUIRE_PTR(loss_out);
     RAFT_REQUIRE_PTR(workspace);
     RAFT_REQUIRE(npix > 0 && n_predictions > 0 && pred_stride >= npix * 2, RAFT_E_SHAPE);
-    RAFT_REQUIRE(n_predictions <= MAX_PRED && (pred_stride & 1) == 0, RAFT_E_UNSUPPORTED);
+    RAFT_REQUIRE(n_predictions <= kMaxPredictions && (pred_stride & 1) == 0, RAFT_E_UNSUPPORTED);
     RAFT_REQUIRE(((uintptr_t)flow_gt & 7) == 0 && ((uintptr_t)preds & 7) == 0 && ((uintptr_t)workspace & 7) == 0, RAFT_E_ALIGN);
     hipStream_t s = (hipStream_t)stream;
-    LossWeights lw = {};
-    for (int i = 0; i < n_predictions; ++i) {   // losses.py:17: gamma ** (n - i - 1), a Python float rounded to fp32 by the product
-        double w = 1.0;
-        for (int k = 0; k < n_predictions - i - 1; ++k) w *= gamma;
-        lw.w[i] = (float)w;
-    }
     const int grid = metric_grid(npix);
     sequence_loss_partial_kernel<<<grid, 256, 0, s>>>((const float2 *)flow_gt, valid, (const float2 *)preds, pred_stride / 2,
-                                                      n_predictions, npix, max_flow, lw, workspace);
+                                                      n_predictions, npix, max_flow, raft_pred_weights(gamma, n_predictions),
+                                                      workspace);
     RAFT_TRY(raft_launch_status());
     sequence_loss_final_kernel<<<1, 64, 0, s>>>(workspace, grid, 1.0 / ((double)npix * 2.0), loss_out);
+    return raft_launch_status();
+}
+
+extern "C" int raft_sequence_loss_grad_f32(const float *flow_gt, const unsigned char *valid, const float *preds,
+                                           int64_t pred_stride, int n_predictions, int64_t npix, double gamma, float max_flow,
+                                           float upstream, float *d_preds, void *stream) {
+    RAFT_REQUIRE_PTR(flow_gt);
+    RAFT_REQUIRE_PTR(valid);
+    RAFT_REQUIRE_PTR(preds);
+    RAFT_REQUIRE_PTR(d_preds);
+    RAFT_REQUIRE(npix > 0 && n_predictions > 0 && pred_stride >= npix * 2, RAFT_E_SHAPE);
+    RAFT_REQUIRE(n_predictions <= kMaxPredictions && (pred_stride & 1) == 0, RAFT_E_UNSUPPORTED);
+    RAFT_REQUIRE(((uintptr_t)flow_gt & 7) == 0 && ((uintptr_t)preds & 7) == 0 && ((uintptr_t)d_preds & 7) == 0, RAFT_E_ALIGN);
+    sequence_loss_grad_kernel<<<raft_ceil_div(npix, 256), 256, 0, (hipStream_t)stream>>>(
+        (const float2 *)flow_gt, valid, (const float2 *)preds, pred_stride / 2, n_predictions, npix, max_flow,
+        raft_pred_weights(gamma, n_predictions, (double)upstream, 2.0 * (double)npix), (float2 *)d_preds);
     return raft_launch_status();
 }

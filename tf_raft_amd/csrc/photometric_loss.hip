@@ -19,11 +19,10 @@
 // pixels slower for these gathers); blockIdx.y walks the images; a thread loops over the n predictions.  Everything that does
 // not depend on i is loaded or computed once per pixel: image1's three values, the mask byte, and the edge weights at (x,y),
 // (x-1,y), (x,y-1).  The five-point flow stencil of a prediction is read through the cache (neighbouring lanes and the rows
-// above and below read the same lines; not staged in LDS).  Deterministic, the scheme of metrics.hip: float64 per-thread
-// accumulators, shuffle + LDS per workgroup into one partial record, records added in index order by a one-workgroup kernel;
-// no atomics, no memset; a grid-stride outer loop bounds the number of records.  Every element of d_preds is written exactly
-// once.
-#include "common.h"
+// above and below read the same lines; not staged in LDS).  Deterministic: the reduction of loss_common.h, one record of
+// kVals sums per workgroup, the number of records bounded by the grid-stride loops.  Every element of d_preds is written
+// exactly once.
+#include "loss_common.h"
 
 #pragma clang fp contract(off)
 
@@ -31,14 +30,9 @@
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = 256;         // (what raft_block_sum_store and raft_record_grid take a workgroup to be)
 constexpr int kMaxRecords = 1024;     // partial records (4 workgroups per CU)
 constexpr int kVals = 4;              // sum_i w_i * PH_i, sum_i w_i * SM_i, PH_{n-1}, SM_{n-1} (sums before normalisation)
-constexpr int kMaxPred = 64;
-
-struct PredWeights {
-    float w[kMaxPred];
-};
 
 struct LossConsts {
     float smooth_weight, edge_weight, eps2, upstream;
@@ -52,12 +46,6 @@ __device__ __forceinline__ float edge_weight_of(const float (&p)[3], const float
     const float s = 1.0f / 255.0f;
     const float m = ((fabsf(s * (q[0] - p[0])) + fabsf(s * (q[1] - p[1]))) + fabsf(s * (q[2] - p[2]))) / 3.0f;
     return expf(-edge_weight * m);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 template <bool GRAD, bool MASK>
@@ -157,38 +145,19 @@ __global__ void __launch_bounds__(kThreads) photometric_loss_kernel(const float 
             }
         }
     }
-    // one partial record per workgroup, numbered along x then y
-    __shared__ double sh[kThreads / 64][kVals];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int v = 0; v < kVals; ++v) {
-        const double r = wave_sum(acc[v]);
-        if (lane == 0) sh[wv][v] = r;
-    }
-    __syncthreads();
-    if (threadIdx.x < kVals) {
-        const int64_t rec = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-        part[rec * kVals + threadIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
-    }
+    raft_block_sum_store(acc, part);
 }
 
 __global__ void __launch_bounds__(64) photometric_loss_final_kernel(const double *__restrict__ part, int nparts, double inv3, double inv2,
                                                                     double smooth_weight, float *__restrict__ out3) {
     __shared__ double tot[kVals];
-    if (threadIdx.x < kVals) {
-        double s = 0.0;
-        for (int r = 0; r < nparts; ++r) s += part[(int64_t)r * kVals + threadIdx.x];
-        tot[threadIdx.x] = s;
-    }
-    __syncthreads();
+    raft_sum_records(part, nparts, tot);
     if (threadIdx.x == 0) {
         out3[0] = (float)(tot[0] * inv3 + smooth_weight * (tot[1] * inv2));
         out3[1] = (float)(tot[2] * inv3);
         out3[2] = (float)(tot[3] * inv2);
     }
 }
-
-bool finite_nonneg(double v) { return v >= 0.0 && v <= 3.402823466e38; }      // (a NaN fails)
 
 }   // namespace
 
@@ -203,32 +172,22 @@ extern "C" int raft_photometric_loss_f32(const float *image1, const float *image
     RAFT_REQUIRE_PTR(preds);
     RAFT_REQUIRE_PTR(out3);
     RAFT_REQUIRE_PTR(workspace);
-    RAFT_REQUIRE(n_predictions > 0 && B > 0 && H > 0 && W > 0, RAFT_E_SHAPE);
-    const int64_t limit = ((int64_t)1 << 31) - 1;
-    RAFT_REQUIRE((int64_t)B <= limit / H && (int64_t)B * H <= limit / W && (int64_t)B * H * W <= limit / 3, RAFT_E_SHAPE);
+    RAFT_REQUIRE(raft_loss_shape_ok(n_predictions, B, H, W), RAFT_E_SHAPE);
     const int64_t npix = (int64_t)B * H * W;
     RAFT_REQUIRE(pred_stride >= 2 * npix, RAFT_E_SHAPE);
-    RAFT_REQUIRE(n_predictions <= kMaxPred && (pred_stride & 1) == 0, RAFT_E_UNSUPPORTED);
+    RAFT_REQUIRE(n_predictions <= kMaxPredictions && (pred_stride & 1) == 0, RAFT_E_UNSUPPORTED);
     const float eps2 = eps * eps;                 // rho(0) = sqrtf(eps2) divides the gradient: it must be positive and finite
     RAFT_REQUIRE(eps > 0.f && eps2 > 0.f && eps2 <= 3.402823466e38f, RAFT_E_SHAPE);      // (a NaN fails)
-    RAFT_REQUIRE(finite_nonneg(gamma) && finite_nonneg(smooth_weight) && finite_nonneg(edge_weight), RAFT_E_SHAPE);
-    RAFT_REQUIRE(upstream >= -3.402823466e38f && upstream <= 3.402823466e38f, RAFT_E_SHAPE);
+    RAFT_REQUIRE(raft_finite_nonneg(gamma) && raft_finite_nonneg(smooth_weight) && raft_finite_nonneg(edge_weight), RAFT_E_SHAPE);
+    RAFT_REQUIRE(raft_finite_f32(upstream), RAFT_E_SHAPE);
     RAFT_REQUIRE(((((uintptr_t)preds) | ((uintptr_t)d_preds) | ((uintptr_t)workspace)) & 7u) == 0, RAFT_E_ALIGN);   // float2 / double
 
-    PredWeights pw = {};
-    for (int i = 0; i < n_predictions; ++i) {     // gamma ** (n - i - 1) in double, rounded to fp32 once: as raft_sequence_loss_f32
-        double w = 1.0;
-        for (int j = 0; j < n_predictions - i - 1; ++j) w *= gamma;
-        pw.w[i] = (float)w;
-    }
+    const PredWeights pw = raft_pred_weights(gamma, n_predictions);
     LossConsts k;
     k.smooth_weight = smooth_weight, k.edge_weight = edge_weight, k.eps2 = eps2, k.upstream = upstream;
     const double inv3 = 1.0 / ((double)npix * 3.0), inv2 = 1.0 / ((double)npix * 2.0);
     k.inv3 = (float)inv3, k.inv2 = (float)inv2;
-    const int gy = B < kMaxRecords ? B : kMaxRecords;
-    const int64_t blocks = ((int64_t)H * W + kThreads - 1) / kThreads, cap = kMaxRecords / gy;
-    const int gx = (int)(blocks < cap ? blocks : cap);
-    const dim3 grid((unsigned)gx, (unsigned)gy);
+    const dim3 grid = raft_record_grid(B, (int64_t)H * W, kMaxRecords);
     hipStream_t s = (hipStream_t)stream;
     const float2 *pr = (const float2 *)preds;
     float2 *dp = (float2 *)d_preds;
@@ -242,6 +201,6 @@ extern "C" int raft_photometric_loss_f32(const float *image1, const float *image
     }
 #undef RAFT_PH_LAUNCH
     RAFT_TRY(raft_launch_status());
-    photometric_loss_final_kernel<<<1, 64, 0, s>>>(workspace, gx * gy, inv3, inv2, (double)smooth_weight, out3);
+    photometric_loss_final_kernel<<<1, 64, 0, s>>>(workspace, (int)(grid.x * grid.y), inv3, inv2, (double)smooth_weight, out3);
     return raft_launch_status();
 }

@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _dev, packing
+from . import _dev, losses, packing
 from ._ffi import check
 
 
@@ -212,17 +212,15 @@ def _dgrad_kernel_any(kernel):
 def sequence_loss_grad(y_true, y_pred, gamma=0.8, max_flow=400, upstream=1.0):
     """d ``sequence_loss(y_true, y_pred)`` / d ``y_pred[i]`` for every i (reference losses.py:4-21): list of tensors shaped
     like the predictions."""
-    flow_gt, valid = y_true
-    flow_gt = _f32(flow_gt)
-    valid = torch.as_tensor(np.asarray(valid) if not isinstance(valid, torch.Tensor) else valid)
-    valid = (valid != 0).to(device=flow_gt.device, dtype=torch.uint8).contiguous()
-    preds = torch.stack([_f32(p) for p in y_pred], dim=0).contiguous()
-    n = preds.shape[0]
-    if tuple(preds.shape[1:]) != tuple(flow_gt.shape) or tuple(valid.shape) != tuple(flow_gt.shape[:-1]):
-        raise ValueError('predictions / flow_gt / valid shapes disagree')
+    flow_gt, valid = losses._truth(y_true)
+    preds = [losses._prediction(p, flow_gt) for p in y_pred]
+    n = len(preds)
+    if n == 0:
+        raise ValueError('sequence_loss_grad: no predictions')
     npix = flow_gt.numel() // 2
-    out = torch.empty_like(preds)
-    check(_dev.lib().raft_sequence_loss_grad_f32(_dev.ptr(flow_gt), _dev.ptr(valid), _dev.ptr(preds), 2 * npix, n, npix,
+    stacked = losses._stacked(preds, 2 * npix)
+    out = torch.empty((n,) + tuple(flow_gt.shape), dtype=torch.float32, device=flow_gt.device)
+    check(_dev.lib().raft_sequence_loss_grad_f32(_dev.ptr(flow_gt), _dev.ptr(valid), _dev.ptr(stacked), 2 * npix, n, npix,
                                                  float(gamma), float(max_flow), float(upstream), _dev.ptr(out),
                                                  _dev.stream_ptr()), 'sequence_loss_grad')
     return [_dev.wrap(out[i]) for i in range(n)]
@@ -234,7 +232,6 @@ def photometric_sequence_loss_value_and_grad(y_true, y_pred, gamma=0.8, smooth_w
     ``{'loss', 'photometric', 'smoothness'}`` and ``grads[i]`` = ``upstream * d loss / d y_pred[i]``, shaped like the predictions.
     ``y_true = (image1, image2)`` or ``(image1, image2, mask)``.  With ``census_weight > 0`` the census entry follows on the same
     stream and adds its share to both (section 18); ``terms`` then has ``'census'`` too."""
-    from . import losses
     out, d = losses._photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, upstream=upstream, want_grad=True,
                                         census_weight=census_weight)
     return losses._photometric_terms(out), [] if d is None else [_dev.wrap(d[i]) for i in range(d.shape[0])]

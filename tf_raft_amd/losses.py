@@ -24,16 +24,39 @@ import torch
 from . import _dev
 from ._ffi import check
 
-_WS = {}
+_WORKSPACES = {}
 
 
-def _workspace(device):
-    key = (device.type, device.index)
-    ws = _WS.get(key)
-    if ws is None:
-        ws = torch.empty((int(_dev.lib().raft_metrics_workspace_doubles()),), dtype=torch.float64, device=device)
-        _WS[key] = ws
+def _workspace(device, nbytes):
+    """The kernels' partial records (and the census planes): one grow-only buffer per device AND stream.  The launches of one
+    stream are ordered, so one buffer serves all of them in turn; two streams of a device would overwrite each other's records.
+    ``nbytes`` comes from the library's ``raft_*_workspace_*`` entry points."""
+    key = (device.index, _dev.stream_ptr())
+    ws = _WORKSPACES.get(key)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=device)
+        _WORKSPACES[key] = ws
     return ws
+
+
+def _metrics_workspace(device):
+    return _workspace(device, 8 * int(_dev.lib().raft_metrics_workspace_doubles()))
+
+
+def _photometric_workspace(device):
+    return _workspace(device, 8 * int(_dev.lib().raft_photometric_loss_workspace_doubles()))
+
+
+_census_workspace = _workspace      # (device, raft_census_loss_workspace_bytes(...)): the name the direct callers of the entry use
+
+
+def _stacked(preds, stride):
+    """The device fp32 predictions as ONE buffer with ``stride`` floats from one to the next.  The model returns views of one
+    (iters, bs, H, W, 2) buffer: those are used in place (the first view is returned); any other list is gathered once."""
+    base = preds[0]
+    if all(p.is_contiguous() and p.data_ptr() == base.data_ptr() + 4 * stride * i for i, p in enumerate(preds)):
+        return base
+    return torch.stack([p.contiguous() for p in preds])
 
 
 def _truth(y_true):
@@ -68,31 +91,17 @@ def sequence_loss(y_true, y_pred, gamma=0.8, max_flow=400):
     if n > 64:
         raise ValueError(f'sequence_loss: at most 64 predictions, got {n}')
     npix = flow_gt.numel() // 2
-    # the model returns views of one (iters, bs, H, W, 2) buffer: use it in place, otherwise gather the list once
     stride = npix * 2
-    base = preds[0]
-    in_place = all(p.is_contiguous() and p.data_ptr() == base.data_ptr() + 4 * stride * i for i, p in enumerate(preds))
-    stacked = base if in_place else torch.stack([p.contiguous() for p in preds])
+    stacked = _stacked(preds, stride)
     out = torch.empty((), dtype=torch.float32, device=flow_gt.device)
     check(_dev.lib().raft_sequence_loss_f32(_dev.ptr(flow_gt), _dev.ptr(valid), _dev.ptr(stacked), stride, n, npix,
-                                            float(gamma), float(max_flow), _dev.ptr(out), _dev.ptr(_workspace(out.device)),
+                                            float(gamma), float(max_flow), _dev.ptr(out), _dev.ptr(_metrics_workspace(out.device)),
                                             _dev.stream_ptr()), 'sequence_loss')
     return _dev.wrap(out)
 
 
 # ---------------------------------------------------------------- self-supervised: photometric + smoothness
 _F32_MAX = 3.402823466e38
-_PHOTOMETRIC_WS = {}
-_CENSUS_WS = {}
-
-
-def _photometric_workspace(device):
-    key = (device.type, device.index)
-    ws = _PHOTOMETRIC_WS.get(key)
-    if ws is None:
-        ws = torch.empty((int(_dev.lib().raft_photometric_loss_workspace_doubles()),), dtype=torch.float64, device=device)
-        _PHOTOMETRIC_WS[key] = ws
-    return ws
 
 
 def _real(name, v):
@@ -176,16 +185,6 @@ def _mask_to_device(mask, device):
     return (mask != 0).to(device=device, dtype=torch.uint8).contiguous()
 
 
-def _census_workspace(device, nbytes):
-    """One grow-only buffer per device (the launches of a stream are ordered, so one buffer serves them all)."""
-    key = (device.type, device.index)
-    ws = _CENSUS_WS.get(key)
-    if ws is None or ws.numel() * 8 < nbytes:
-        ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=device)
-        _CENSUS_WS[key] = ws
-    return ws
-
-
 def _photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, upstream=1.0, want_grad=False, census_weight=0.0):
     """One raft_photometric_loss_f32 call: ``(out, d_preds)`` -- ``out`` maps 'loss', 'photometric', 'smoothness' to elements of
     one device buffer (the last two of the LAST prediction), d_preds is the stacked gradients ``(n, B, H, W, 2)`` or None.
@@ -209,20 +208,21 @@ def _photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, 
     if n == 0:
         return out, None
     preds = [_dev.to_device(p).as_subclass(torch.Tensor).to(torch.float32) for p in preds]
-    # the model returns views of one (iters, bs, H, W, 2) buffer: use it in place, otherwise gather the list once
     stride = B * H * W * 2
-    base = preds[0]
-    in_place = all(p.is_contiguous() and p.data_ptr() == base.data_ptr() + 4 * stride * i for i, p in enumerate(preds))
-    stacked = base if in_place else torch.stack([p.contiguous() for p in preds])
+    stacked = _stacked(preds, stride)
     d_preds = torch.empty((n, B, H, W, 2), dtype=torch.float32, device=image1.device) if want_grad else None
     lib = _dev.lib()
+    # one buffer for both entries: the census launches follow the photometric ones on the stream
+    need = 8 * int(lib.raft_photometric_loss_workspace_doubles())
+    if census:
+        need = max(need, int(lib.raft_census_loss_workspace_bytes(n, B, H, W)))
+    ws = _workspace(buf.device, need)
     check(lib.raft_photometric_loss_f32(_dev.ptr(image1), _dev.ptr(image2), _dev.ptr(mask) if mask is not None else None,
                                         _dev.ptr(stacked), stride, n, B, H, W, gamma, smooth_weight, edge_weight, eps,
                                         upstream, _dev.ptr(buf), _dev.ptr(d_preds) if want_grad else None,
-                                        _dev.ptr(_photometric_workspace(buf.device)), _dev.stream_ptr()),
+                                        _dev.ptr(ws), _dev.stream_ptr()),
           'photometric_loss')
     if census:
-        ws = _census_workspace(buf.device, int(lib.raft_census_loss_workspace_bytes(n, B, H, W)))
         check(lib.raft_census_loss_f32(_dev.ptr(image1), _dev.ptr(image2), _dev.ptr(mask) if mask is not None else None,
                                        _dev.ptr(stacked), stride, n, B, H, W, gamma, census_weight, upstream, _dev.ptr(buf),
                                        _dev.ptr(buf[3:]), _dev.ptr(d_preds) if want_grad else None, 1, _dev.ptr(ws),
@@ -274,7 +274,7 @@ def _metrics(y_true, y_pred, max_flow):
     pred = _prediction(y_pred, flow_gt).contiguous()
     out = torch.empty((5,), dtype=torch.float32, device=flow_gt.device)
     check(_dev.lib().raft_flow_metrics_f32(_dev.ptr(flow_gt), _dev.ptr(valid), _dev.ptr(pred), flow_gt.numel() // 2,
-                                           float(max_flow), _dev.ptr(out), _dev.ptr(_workspace(out.device)),
+                                           float(max_flow), _dev.ptr(out), _dev.ptr(_metrics_workspace(out.device)),
                                            _dev.stream_ptr()), 'flow_metrics')
     return out
 
