@@ -714,6 +714,30 @@ int raft_census_loss_f32(const float *image1, const float *image2, const uint8_t
                          int n_predictions, int B, int H, int W, double gamma, float census_weight, float upstream,
                          const float *add_to, float *out2, float *d_preds, int accumulate, void *workspace, void *stream);
 
+/* SSIM term of the self-supervised loss and its gradient (csrc/ssim_loss.hip).  Arguments, checks, error
+ * codes and their precedence are raft_census_loss_f32's, with ssim_weight in the place of census_weight.  g1 and w_i as there; over
+ * the 3x3 window of z (rows first, x = g1), with C1 = (0.01f*255.f)^2, C2 = (0.03f*255.f)^2,
+ * interior(z) = 1 <= zx <= W-2 && 1 <= zy <= H-2 and M_i = mask && inside_i && interior:
+ *   mx = (sum x) / 9.f, mw = (sum w_i) / 9.f, sxx = (sum (x-mx)^2) / 9.f, sww = (sum (w_i-mw)^2) / 9.f, sxw = (sum (x-mx)*(w_i-mw)) / 9.f
+ *   S(z) = ((2*mx*mw + C1) * (2*sxw + C2)) / ((mx*mx + mw*mw + C1) * (sxx + sww + C2)),      D(z) = (1 - S(z)) / 2
+ *   ssim_i = sum_z M_i(z) * D(z) / (B*H*W),     w_i = (float)gamma^(n-i-1)
+ *   out2[0] = (add_to ? *add_to : 0) + ssim_weight * sum_i w_i * ssim_i  (formed in double, rounded once; add_to may be out2);
+ *   out2[1] = ssim_{n-1}
+ * d_preds: NULL (value only), or the layout of preds; every element is touched exactly once with
+ * upstream * ssim_weight * w_i * d ssim_i -- stored (accumulate == 0) or added to what is there with one float32 addition
+ * (accumulate == 1); gaps of a pred_stride larger than 2*B*H*W are not touched.  mask and inside are constants of the gradient; a
+ * pixel outside the interior receives gradient from the interior windows that contain it.
+ * Deterministic (no atomics, no memset).  `workspace`: raft_ssim_loss_workspace_bytes(n_predictions, B, H, W) bytes (the census
+ * entry's layout and size; 0 for sizes the entry refuses).
+ * RAFT_E_NULL: image1, image2, preds, out2 or workspace NULL.  RAFT_E_SHAPE: a non-positive size, pred_stride < 2*B*H*W,
+ * B*H*W*3 of 2^31 or more, gamma / ssim_weight negative or not finite, upstream not finite, accumulate not 0 or 1.
+ * RAFT_E_UNSUPPORTED: n_predictions > 64 or an odd pred_stride.  RAFT_E_ALIGN: preds, d_preds or workspace not 8-byte aligned.
+ * All checks precede the first launch. */
+int64_t raft_ssim_loss_workspace_bytes(int n_predictions, int B, int H, int W);
+int raft_ssim_loss_f32(const float *image1, const float *image2, const uint8_t *mask, const float *preds, int64_t pred_stride,
+                       int n_predictions, int B, int H, int W, double gamma, float ssim_weight, float upstream,
+                       const float *add_to, float *out2, float *d_preds, int accumulate, void *workspace, void *stream);
+
 /* Backward of raft_corr_lookup_f32 (CorrBlock.retrieve + bilinear_sampler, corr.py:116-152, 28-69), with TensorFlow's
  * gradient conventions: floor / ceil contribute nothing, clip_by_value passes the gradient on [0, size - 1].
  * d_out: (B, h, w, ld_out) upstream gradient of the lookup output (first levels*(2r+1)^2 channels used).

@@ -244,6 +244,24 @@ def photometric_sequence_loss_grad(y_true, y_pred, gamma=0.8, smooth_weight=0.1,
     return photometric_sequence_loss_value_and_grad(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, upstream, census_weight)[1]
 
 
+def ssim_sequence_loss_value_and_grad(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, upstream=1.0,
+                                      census_weight=0.0, ssim_weight=0.0):
+    """``(terms, grads)`` of ``losses.SSIMSequenceLoss``: ``photometric_sequence_loss_value_and_grad`` with the SSIM term
+    (DESIGN.md section 19).  With ``ssim_weight > 0`` the SSIM entry follows the photometric one (and the census one when it is
+    on) on the same stream and adds its share to the loss and to the gradients; ``terms`` then has ``'ssim'`` between ``'census'``
+    and ``'smoothness'``."""
+    loss = losses.SSIMSequenceLoss(gamma, smooth_weight, edge_weight, eps, census_weight, ssim_weight)
+    return loss.value_and_grad(y_true, y_pred, upstream)
+
+
+def ssim_sequence_loss_grad(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, upstream=1.0,
+                            census_weight=0.0, ssim_weight=0.0):
+    """``upstream * d SSIMSequenceLoss(...)(y_true, y_pred) / d y_pred[i]`` for every i: list of tensors shaped like the
+    predictions."""
+    return ssim_sequence_loss_value_and_grad(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, upstream, census_weight,
+                                             ssim_weight)[1]
+
+
 def corr_lookup_backward(corr_block, coords, d_out, d_pyramid=None, want_pyramid_grad=True):
     """Backward of ``corr_block.retrieve(coords)`` (reference corr.py:116-152) for the upstream gradient ``d_out``
     (bs, h, w, levels*(2r+1)^2).  Returns ``(d_coords, d_pyramid)``: ``d_coords`` (bs, h, w, 2) and the gradient w.r.t.

@@ -7,6 +7,7 @@
 and the self-supervised loss the reference does not have (csrc/photometric_loss.hip):
 
     PhotometricSequenceLoss(gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, census_weight=0.0)
+    SSIMSequenceLoss(gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, census_weight=0.0, ssim_weight=0.0)
     photometric_sequence_loss(y_true, y_pred, ...)                y_true = (image1, image2) or (image1, image2, mask)
 
 ``y_true = (flow_gt, valid)`` with ``flow_gt`` (bs, H, W, 2) float and ``valid`` (bs, H, W) bool; ``y_pred`` is the list
@@ -121,6 +122,14 @@ def _census_weight(census_weight):
     return v
 
 
+def _ssim_weight(ssim_weight):
+    """``ssim_weight`` as raft_ssim_loss_f32 checks it: finite and >= 0."""
+    v = _real('ssim_weight', ssim_weight)
+    if not 0.0 <= v <= _F32_MAX:
+        raise ValueError(f'ssim_weight must be finite and >= 0, got {v!r}')
+    return v
+
+
 def _photometric_params(gamma, smooth_weight, edge_weight, eps, upstream=1.0):
     """The checks raft_photometric_loss_f32 makes on its parameters: finite non-negative weights, ``eps > 0``, finite upstream."""
     out = []
@@ -185,25 +194,32 @@ def _mask_to_device(mask, device):
     return (mask != 0).to(device=device, dtype=torch.uint8).contiguous()
 
 
-def _photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, upstream=1.0, want_grad=False, census_weight=0.0):
+def _photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, upstream=1.0, want_grad=False, census_weight=0.0,
+                        ssim_weight=0.0):
     """One raft_photometric_loss_f32 call: ``(out, d_preds)`` -- ``out`` maps 'loss', 'photometric', 'smoothness' to elements of
     one device buffer (the last two of the LAST prediction), d_preds is the stacked gradients ``(n, B, H, W, 2)`` or None.
     With ``census_weight > 0`` a raft_census_loss_f32 call follows on the same stream: it adds its term
-    to the loss and its gradient to d_preds on the device, and ``out`` gains 'census'."""
+    to the loss and its gradient to d_preds on the device, and ``out`` gains 'census'.  With ``ssim_weight > 0`` a
+    raft_ssim_loss_f32 call follows those in the same way (section 19), and ``out`` gains 'ssim'."""
     gamma, smooth_weight, edge_weight, eps, upstream = _photometric_params(gamma, smooth_weight, edge_weight, eps, upstream)
     census_weight = _census_weight(census_weight)
+    ssim_weight = _ssim_weight(ssim_weight)
     image1, image2, mask, preds, (B, H, W) = _check_unlabelled(y_true, y_pred)
     image1 = _dev.to_device(image1).as_subclass(torch.Tensor)
     image2 = _dev.to_device(image2).as_subclass(torch.Tensor)
     if mask is not None:
         mask = _mask_to_device(mask, image1.device)
     n = len(preds)
-    census = census_weight > 0.0
-    # [loss, photometric, smoothness], and behind them [loss with the census term, census]
-    buf = torch.zeros((5 if census else 3,), dtype=torch.float32, device=image1.device)
-    out = {'loss': buf[3] if census else buf[0], 'photometric': buf[1]}
+    census, ssim = census_weight > 0.0, ssim_weight > 0.0
+    # [loss, photometric, smoothness], and behind them, per windowed term that is on, [loss with that term too, the term]
+    at_census, at_ssim = 3, 5 if census else 3
+    last = at_ssim if ssim else at_census if census else 0
+    buf = torch.zeros((3 + 2 * census + 2 * ssim,), dtype=torch.float32, device=image1.device)
+    out = {'loss': buf[last], 'photometric': buf[1]}
     if census:
-        out['census'] = buf[4]
+        out['census'] = buf[at_census + 1]
+    if ssim:
+        out['ssim'] = buf[at_ssim + 1]
     out['smoothness'] = buf[2]
     if n == 0:
         return out, None
@@ -212,10 +228,12 @@ def _photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, 
     stacked = _stacked(preds, stride)
     d_preds = torch.empty((n, B, H, W, 2), dtype=torch.float32, device=image1.device) if want_grad else None
     lib = _dev.lib()
-    # one buffer for both entries: the census launches follow the photometric ones on the stream
+    # one buffer for all entries: the census and SSIM launches follow the photometric ones on the stream
     need = 8 * int(lib.raft_photometric_loss_workspace_doubles())
     if census:
         need = max(need, int(lib.raft_census_loss_workspace_bytes(n, B, H, W)))
+    if ssim:
+        need = max(need, int(lib.raft_ssim_loss_workspace_bytes(n, B, H, W)))
     ws = _workspace(buf.device, need)
     check(lib.raft_photometric_loss_f32(_dev.ptr(image1), _dev.ptr(image2), _dev.ptr(mask) if mask is not None else None,
                                         _dev.ptr(stacked), stride, n, B, H, W, gamma, smooth_weight, edge_weight, eps,
@@ -227,6 +245,11 @@ def _photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, 
                                        _dev.ptr(stacked), stride, n, B, H, W, gamma, census_weight, upstream, _dev.ptr(buf),
                                        _dev.ptr(buf[3:]), _dev.ptr(d_preds) if want_grad else None, 1, _dev.ptr(ws),
                                        _dev.stream_ptr()), 'census_loss')
+    if ssim:
+        check(lib.raft_ssim_loss_f32(_dev.ptr(image1), _dev.ptr(image2), _dev.ptr(mask) if mask is not None else None,
+                                     _dev.ptr(stacked), stride, n, B, H, W, gamma, ssim_weight, upstream,
+                                     _dev.ptr(buf[at_census if census else 0:]), _dev.ptr(buf[at_ssim:]),
+                                     _dev.ptr(d_preds) if want_grad else None, 1, _dev.ptr(ws), _dev.stream_ptr()), 'ssim_loss')
     return out, d_preds
 
 
@@ -262,6 +285,28 @@ class PhotometricSequenceLoss:
 
     def __call__(self, y_true, y_pred):
         return self.terms(y_true, y_pred)['loss']
+
+    def value_and_grad(self, y_true, y_pred, upstream=1.0):
+        """``(terms, grads)`` from one pass: ``terms()`` and ``grads[i] = upstream * d loss / d y_pred[i]``, shaped like the
+        predictions.  What ``train_step`` calls, so that a subclass with further terms serves it unchanged."""
+        out, d = _photometric_launch(y_true, y_pred, upstream=upstream, want_grad=True, **self._params())
+        return _photometric_terms(out), [] if d is None else [_dev.wrap(d[i]) for i in range(d.shape[0])]
+
+
+class SSIMSequenceLoss(PhotometricSequenceLoss):
+    """``PhotometricSequenceLoss`` with a structural-similarity data term, the third part of the data term of
+    ARFlow-style recipes: ``ssim_weight > 0`` adds ``ssim_weight * ssim_i`` to every prediction's term, ``ssim_i`` the mean over all
+    pixels of ``(1 - SSIM) / 2`` between frame 1 and the warped frame 2 (3x3 windows of gray values on 0..255, Wang et al.'s
+    constants for L = 255) where the pixel is in ``mask``, its vector in frame and its window in the picture.
+    ``ssim_weight`` has no tuned default (0 = the term is off, and the loss is the parent's launch for launch and bit for bit),
+    and nothing is claimed about accuracy on real footage: nothing here was trained on any."""
+
+    def __init__(self, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, census_weight=0.0, ssim_weight=0.0):
+        super().__init__(gamma, smooth_weight, edge_weight, eps, census_weight)
+        self.ssim_weight = _ssim_weight(ssim_weight)
+
+    def _params(self):
+        return dict(super()._params(), ssim_weight=self.ssim_weight)
 
 
 def photometric_sequence_loss(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, census_weight=0.0):

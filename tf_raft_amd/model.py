@@ -681,7 +681,8 @@ class RAFT:
         """reference model.py:111-124.  ``loss`` / ``epe`` default to ``tf_raft_amd.losses.sequence_loss`` /
         ``end_point_error``; ``loss=losses.PhotometricSequenceLoss(...)`` makes ``train_step`` take unlabelled pairs
         ``(image1, image2)`` or ``(image1, image2, mask)`` and report ``loss`` / ``photometric`` / ``smoothness`` (DESIGN.md
-        section 17; ``test_step`` still wants ground truth), and ``census`` when the loss has ``census_weight > 0`` (section 18).  ``trainable``: which weights ``train_step`` updates -- ``'all'``
+        section 17; ``test_step`` still wants ground truth), and ``census`` when the loss has ``census_weight > 0`` (section 18);
+        ``losses.SSIMSequenceLoss(..., ssim_weight > 0)`` adds ``ssim`` (section 19).  ``trainable``: which weights ``train_step`` updates -- ``'all'``
         (the reference's behaviour: encoders, norms and update block) or ``'update_block'`` (encoders frozen, run by the
         inference kernels)."""
         from . import losses
@@ -704,7 +705,8 @@ class RAFT:
 
     def _unlabelled_keys(self):
         """What ``train_step`` reports under a PhotometricSequenceLoss."""
-        return ('loss', 'photometric', 'census', 'smoothness') if self.loss.census_weight > 0 else ('loss', 'photometric', 'smoothness')
+        on = [k for k in ('census', 'ssim') if getattr(self.loss, k + '_weight', 0.0) > 0]
+        return ('loss', 'photometric', *on, 'smoothness')
 
     BN_MOMENTUM = 0.99      # Keras BatchNormalization default (extractor.py:10 passes none)
 
@@ -796,8 +798,8 @@ class RAFT:
         prefix = 'update_block'
         ub = {k: v for k, v in wts.items() if k.startswith(prefix)}
         preds, tape = grad.loop_forward(ub, correlation, net0, inp, self.iters, prefix, self.variant, tape_dtype=self.tape_dtype)
-        if photometric:                             # value and gradient share the gathers: one launch
-            terms, d_preds = grad.photometric_sequence_loss_value_and_grad(y_true, preds, **self.loss._params())
+        if photometric:                             # value and gradient share the gathers: one launch per term
+            terms, d_preds = self.loss.value_and_grad(y_true, preds)
         else:
             loss = self.loss([flow, valid], preds)
             d_preds = grad.sequence_loss_grad((flow, valid), preds)
