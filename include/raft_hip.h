@@ -298,6 +298,22 @@ int raft_warp_u8_f32(const uint8_t *src, const float *flow, float *dst, uint8_t 
 int raft_flow_consistency_f32(const float *flow_a, const float *flow_b, uint8_t *occluded_a, uint8_t *occluded_b, int N, int H, int W,
                               float alpha, float beta, void *stream);
 
+/* The consistency test inside a bidirectional training step: `flows` (2N, H, W, 2) holds N forward flows
+ * and, behind them, the N backward flows of the same pairs.  Slice s < N is tested against slice s + N, slice s >= N against
+ * slice s - N, by the test of raft_flow_consistency_f32 (one device function serves both entries), and
+ *     visible[s, y, x] = (mask == NULL || mask[s, y, x] != 0) && (!apply || !occluded) ? 1 : 0
+ * mask: NULL (all ones) or uint8 (2N, H, W); visible: uint8 (2N, H, W), or NULL when only the count is wanted; the two must not
+ * overlap.  occluded_fraction[0] = float(count / (2 * N * H * W)), count the number of occluded pixels of all 2N slices whatever
+ * `apply` and `mask` are; the division is done in double and rounded once.  Deterministic (no atomics, no memset): float64
+ * partial records in `workspace` (raft_flow_visibility_workspace_doubles() doubles, 8-byte aligned), summed in index order by a
+ * one-workgroup launch, so two launches on `stream`.  Errors, in this order: RAFT_E_NULL for a NULL flows, occluded_fraction or
+ * workspace; RAFT_E_SHAPE for a non-positive size, 2N * H * W * 2 of 2^31 elements or more, a negative or non-finite alpha or
+ * beta, `apply` other than 0 or 1; RAFT_E_ALIGN for flows or a workspace that is not 8-byte aligned.  All checks precede the
+ * first launch. */
+int64_t raft_flow_visibility_workspace_doubles(void);
+int raft_flow_visibility_f32(const float *flows, const uint8_t *mask, uint8_t *visible, float *occluded_fraction, int N, int H, int W,
+                             float alpha, float beta, int apply, double *workspace, void *stream);
+
 /* ------------------------------------------------------------------ training augmentation */
 
 /* FlowAugmentor (reference tf_raft/datasets/augmentor.py:9-129, used at dataset.py:87-91) composed into one gather (the sparse

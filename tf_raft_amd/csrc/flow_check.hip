@@ -4,6 +4,8 @@
 //   raft_warp_f32 / raft_warp_u8_f32   dst[n, y, x, c] = src[n, :, :, c] sampled at (x + u, y + v), zero outside the frame
 //   raft_flow_consistency_f32          occluded = !(in frame && |f + s|^2 <= alpha * (|f|^2 + |s|^2) + beta), s the OTHER flow
 //                                      sampled at (x + u, y + v); both directions in one launch (Meister et al. 2018, UnFlow)
+//   raft_flow_visibility_f32           the same test on the 2N flows of a bidirectional training step, as the mask of its loss:
+//                                      visible = mask && !(apply && occluded), and the occluded share
 //
 // Both share one definition of the sample.  For the pixel at integer (x, y) with vector (u, v): sx = float(x) + u and
 // sy = float(y) + v, ONE float32 addition each; the pixel is in frame iff 0 <= sx <= W - 1 and 0 <= sy <= H - 1 (a NaN fails);
@@ -25,6 +27,7 @@
 #pragma clang fp contract(off)
 
 #include "flow_sample.h"      // Taps, flow_taps, bilinear: shared with photometric_loss.hip
+#include "loss_common.h"      // the deterministic reduction of raft_flow_visibility_f32's count
 
 namespace {
 
@@ -112,6 +115,57 @@ __global__ void __launch_bounds__(kFlowCheckThreads) flow_consistency_kernel(con
     }
 }
 
+// The in-step form of the test: the 2N flows of a bidirectional training step in ONE tensor, slice s
+// against slice s + N (s < N) or s - N, the result inverted and ANDed with the caller's mask, and the occluded pixels counted.
+// The same one-thread-per-pixel walk as above; where the record grid is smaller than the picture a workgroup strides over
+// 256-pixel runs, so a wave still reads consecutive vectors.  The count is a per-thread float64 (exact for integers), one
+// record per workgroup.  The final launch reads the records as rows of kVisibilityColumns and lets raft_sum_records add the
+// columns side by side, 16 records per thread instead of 1024 behind one another in one (docs/NOTEBOOK.md section 30);
+// workgroup (0, 0) zeroes the tail of the last row, so every record that is read was written by this launch.
+constexpr int kVisibilityRecords = 1024;
+constexpr int kVisibilityColumns = 64;
+static_assert(kVisibilityRecords % kVisibilityColumns == 0 && kVisibilityColumns <= 64, "rows of records, one column per final thread");
+
+template <bool PAIR>
+__global__ void __launch_bounds__(kFlowCheckThreads) flow_visibility_kernel(const float2 *__restrict__ flows,
+                                                                            const uint8_t *__restrict__ mask,
+                                                                            uint8_t *__restrict__ visible, int N, int H, int W,
+                                                                            float alpha, float beta, int apply,
+                                                                            double *__restrict__ part) {
+    const int HW = H * W;
+    double acc[1] = {0.0};
+    for (int s = blockIdx.y; s < 2 * N; s += gridDim.y) {
+        const int64_t base = (int64_t)s * HW;
+        const float2 *own = flows + base;
+        const float2 *other = flows + (int64_t)(s >= N ? s - N : s + N) * HW;      // wave-uniform
+        for (int64_t q = (int64_t)blockIdx.x * kFlowCheckThreads + threadIdx.x; q < HW; q += (int64_t)gridDim.x * kFlowCheckThreads) {
+            const int p = (int)q, y = p / W, x = p - y * W;
+            const uint32_t occ = occluded_at<PAIR>(other, own[p], x, y, H, W, alpha, beta);
+            acc[0] += (double)occ;
+            if (visible != nullptr) {
+                const bool use = mask == nullptr || mask[base + p] != 0;
+                visible[base + p] = (use && !(apply && occ)) ? 1 : 0;
+            }
+        }
+    }
+    raft_block_sum_store(acc, part);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < kVisibilityColumns) {
+        const int nparts = (int)(gridDim.x * gridDim.y), tail = nparts + (int)threadIdx.x;      // (at most kVisibilityRecords records)
+        if (tail < (nparts + kVisibilityColumns - 1) / kVisibilityColumns * kVisibilityColumns) part[tail] = 0.0;
+    }
+}
+
+__global__ void __launch_bounds__(64) flow_visibility_final_kernel(const double *__restrict__ part, int rows, double total,
+                                                                   float *__restrict__ occluded_fraction) {
+    __shared__ double tot[kVisibilityColumns];
+    raft_sum_records(part, rows, tot);
+    if (threadIdx.x == 0) {
+        double count = 0.0;
+        for (int k = 0; k < kVisibilityColumns; ++k) count += tot[k];
+        occluded_fraction[0] = (float)(count / total);
+    }
+}
+
 // what both entries ask of their sizes: positive, W * C in an int, fewer than 2^31 elements in the largest tensor
 int flow_check_sizes(int N, int H, int W, int C) {
     RAFT_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0, RAFT_E_SHAPE);
@@ -173,5 +227,31 @@ extern "C" int raft_flow_consistency_f32(const float *flow_a, const float *flow_
         flow_consistency_kernel<true><<<grid, kFlowCheckThreads, 0, s>>>(fa, fb, occluded_a, occluded_b, N, H, W, slices, alpha, beta);
     else
         flow_consistency_kernel<false><<<grid, kFlowCheckThreads, 0, s>>>(fa, fb, occluded_a, occluded_b, N, H, W, slices, alpha, beta);
+    return raft_launch_status();
+}
+
+extern "C" int64_t raft_flow_visibility_workspace_doubles(void) { return kVisibilityRecords; }
+
+extern "C" int raft_flow_visibility_f32(const float *flows, const uint8_t *mask, uint8_t *visible, float *occluded_fraction, int N,
+                                        int H, int W, float alpha, float beta, int apply, double *workspace, void *stream) {
+    RAFT_REQUIRE_PTR(flows);
+    RAFT_REQUIRE_PTR(occluded_fraction);
+    RAFT_REQUIRE_PTR(workspace);
+    RAFT_REQUIRE(N > 0 && N < (1 << 29), RAFT_E_SHAPE);              // (2 * N below stays an int)
+    RAFT_TRY(flow_check_sizes(2 * N, H, W, 2));
+    RAFT_REQUIRE(alpha >= 0.f && alpha <= 3.402823466e38f && beta >= 0.f && beta <= 3.402823466e38f, RAFT_E_SHAPE);   // (a NaN fails)
+    RAFT_REQUIRE(apply == 0 || apply == 1, RAFT_E_SHAPE);
+    RAFT_REQUIRE(((((uintptr_t)flows) | ((uintptr_t)workspace)) & 7u) == 0, RAFT_E_ALIGN);      // read as float2; doubles
+    const int64_t HW = (int64_t)H * W;
+    const dim3 grid = raft_record_grid(2 * N, HW, kVisibilityRecords);
+    hipStream_t s = (hipStream_t)stream;
+    const float2 *f = (const float2 *)flows;
+    if (W >= 2)
+        flow_visibility_kernel<true><<<grid, kFlowCheckThreads, 0, s>>>(f, mask, visible, N, H, W, alpha, beta, apply, workspace);
+    else
+        flow_visibility_kernel<false><<<grid, kFlowCheckThreads, 0, s>>>(f, mask, visible, N, H, W, alpha, beta, apply, workspace);
+    RAFT_TRY(raft_launch_status());
+    const int rows = ((int)(grid.x * grid.y) + kVisibilityColumns - 1) / kVisibilityColumns;
+    flow_visibility_final_kernel<<<1, 64, 0, s>>>(workspace, rows, (double)(2 * N) * (double)HW, occluded_fraction);
     return raft_launch_status();
 }

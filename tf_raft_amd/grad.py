@@ -802,6 +802,26 @@ def corr_build_backward(corr_block, d_pyramid):
     return _dev.wrap(d1), _dev.wrap(d2)
 
 
+def mirror_feature_maps(fout, N):
+    """The volume operands of a bidirectional step from ``fnet``'s output on ``[image1 | image2]``,
+    ``(2N, h, w, C)``: ``(fmap1m, fmap2m)`` with ``fmap1m = fout`` and ``fmap2m = [fout[N:] | fout[:N]]``, so that pair ``s`` of
+    the doubled batch is frame 1 against frame 2 for ``s < N`` and frame 2 against frame 1 behind.  Data movement only."""
+    fout = _f32(fout)
+    if fout.dim() != 4 or fout.shape[0] != 2 * int(N) or int(N) < 1:
+        raise ValueError(f'mirror_feature_maps expects (2N, h, w, C) with N = {N}, got {tuple(fout.shape)}')
+    return fout, torch.cat([fout[N:], fout[:N]], dim=0)
+
+
+def mirror_feature_maps_backward(d_fmap1m, d_fmap2m, N):
+    """Adjoint of ``mirror_feature_maps``: every frame's features served in two roles, so its gradient is their sum,
+    ``d_fout[:N] = d_fmap1m[:N] + d_fmap2m[N:]`` and ``d_fout[N:] = d_fmap1m[N:] + d_fmap2m[:N]`` -- one float32 addition per
+    element (``raft_axpby_f32``)."""
+    d1, d2 = _f32(d_fmap1m), _f32(d_fmap2m)
+    if d1.dim() != 4 or d1.shape[0] != 2 * int(N) or int(N) < 1 or d2.shape != d1.shape:
+        raise ValueError(f'mirror_feature_maps_backward expects two (2N, h, w, C) with N = {N}, got {tuple(d1.shape)} / {tuple(d2.shape)}')
+    return _axpby(1.0, d1, 1.0, torch.cat([d2[N:], d2[:N]], dim=0))
+
+
 def prepare_state_backward(net0, inp, d_net0, d_inp):
     """Backward of ``net = tanh(cnet[..., :hdim]); inp = relu(cnet[..., hdim:])`` (reference model.py:84-86): ``d_cnet``."""
     net0, inp, d_net0, d_inp = (_f32(t) for t in (net0, inp, d_net0, d_inp))

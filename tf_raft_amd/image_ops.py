@@ -30,7 +30,9 @@ through the same crop-or-pad window, so a prediction leaves the device as a 3-by
 
 ``warp`` / ``flow_consistency`` say where a prediction can be trusted: the backward warp of frames along a
 flow, and the forward-backward test of two flows that marks occluded and out-of-frame pixels, one launch each (``raft_warp_*`` /
-``raft_flow_consistency_f32``, tf_raft_amd/csrc/flow_check.hip).
+``raft_flow_consistency_f32``, tf_raft_amd/csrc/flow_check.hip).  ``flow_visibility_launch`` is that test inside a bidirectional
+training step: the 2N flows of the doubled batch in, the mask of the loss and the occluded share out
+(``raft_flow_visibility_f32``).
 
 ``forward_interpolate`` projects a low-resolution flow forward along itself: the start of the next pair's
 recurrence in a video stream (``raft_forward_interpolate_f32``, tf_raft_amd/csrc/flow_init.hip; ``tf_raft_amd.video``).
@@ -703,6 +705,32 @@ def flow_consistency_launch(flow_a: torch.Tensor, flow_b: torch.Tensor, alpha: f
         check(_dev.lib().raft_flow_consistency_f32(_dev.ptr(flow_a), _dev.ptr(flow_b), _dev.ptr(masks[0]), _dev.ptr(masks[1]) if both else None,
                                                    N, H, W, alpha, beta, _dev.stream_ptr()), 'flow_consistency')
     return masks[0], (masks[1] if both else None)
+
+
+def flow_visibility_launch(flows: torch.Tensor, N: int, mask=None, alpha: float = CONSISTENCY_ALPHA, beta: float = CONSISTENCY_BETA,
+                           apply: bool = True, want_visible: bool = True):
+    """The launch itself (``raft_flow_visibility_f32``): contiguous float32 device flows ``(2N, H, W, 2)``,
+    the N forward flows in front of the N backward ones, and an optional contiguous uint8 ``mask`` ``(2N, H, W)`` ->
+    ``(visible, occluded_fraction)`` on the CURRENT stream (plain tensors).  ``visible`` is uint8 ``(2N, H, W)``,
+    ``mask != 0 and not (apply and occluded)`` (None with ``want_visible=False``); ``occluded_fraction`` is the 0-d float32 share
+    of occluded pixels among all ``2N * H * W``, whatever ``apply`` and ``mask`` are."""
+    from . import losses
+    if flows.dim() != 4 or flows.shape[-1] != 2 or flows.shape[0] != 2 * int(N) or int(N) < 1:
+        raise ValueError(f'expected flows (2N, H, W, 2) with N = {N}, got {tuple(flows.shape)}')
+    _check_flow(flows, 'flow_visibility')
+    B, H, W, _ = flows.shape
+    if mask is not None:
+        mask = _check_out(mask, (B, H, W), torch.uint8, flows.device)
+    visible = torch.empty((B, H, W), device=flows.device, dtype=torch.uint8) if want_visible else None
+    fraction = torch.empty((), device=flows.device, dtype=torch.float32)
+    lib = _dev.lib()
+    with torch.cuda.device(flows.device):
+        ws = losses._workspace(flows.device, 8 * int(lib.raft_flow_visibility_workspace_doubles()))
+        check(lib.raft_flow_visibility_f32(_dev.ptr(flows), _dev.ptr(mask) if mask is not None else None,
+                                           _dev.ptr(visible) if visible is not None else None, _dev.ptr(fraction), int(N), H, W,
+                                           float(alpha), float(beta), int(bool(apply)), _dev.ptr(ws), _dev.stream_ptr()),
+              'flow_visibility')
+    return visible, fraction
 
 
 def _flow_like(flow, lead_shape, what):

@@ -186,6 +186,36 @@ def _check_unlabelled(y_true, y_pred):
     return image1, image2, mask, preds, s1[:3]
 
 
+_BIDIRECTIONAL_FORMS = '(image1, image2) or (image1, image2, (mask1, mask2))'
+
+
+def _check_bidirectional(data):
+    """What a bidirectional ``train_step`` takes, checked BEFORE anything moves to the device: ``(image1,
+    image2)`` or ``(image1, image2, (mask1, mask2))``, each mask ``(N, H, W)`` -- ``mask1`` over frame 1's pixels for the forward
+    direction, ``mask2`` over frame 2's for the backward one.  Returns ``None`` or ``(mask1, mask2)``."""
+    try:
+        items = tuple(data)
+    except TypeError as exc:
+        raise ValueError(f'a bidirectional train_step expects {_BIDIRECTIONAL_FORMS}') from exc
+    if len(items) not in (2, 3):
+        raise ValueError(f'a bidirectional train_step expects {_BIDIRECTIONAL_FORMS}, got {len(items)} items')
+    try:
+        s1 = _check_unlabelled(items[:2], ())[4]
+    except ValueError as exc:
+        raise ValueError(f'a bidirectional train_step expects {_BIDIRECTIONAL_FORMS}: {exc}') from exc
+    if 2 * s1[0] * s1[1] * s1[2] * 3 >= 2 ** 31:
+        raise ValueError(f'2*N*H*W*3 must stay below 2^31, got {s1}')
+    if len(items) == 2:
+        return None
+    masks = items[2]
+    if not isinstance(masks, (tuple, list)) or len(masks) != 2:
+        raise ValueError(f'a bidirectional train_step expects {_BIDIRECTIONAL_FORMS}: the masks come as a pair, one per direction')
+    for name, m in zip(('mask1', 'mask2'), masks):
+        if _shape_of(m) != s1:
+            raise ValueError(f'a bidirectional train_step expects {_BIDIRECTIONAL_FORMS} with {name} {s1}, got {_shape_of(m)}')
+    return tuple(masks)
+
+
 def _mask_to_device(mask, device):
     """nonzero = use the pixel -> contiguous uint8 0/1 on ``device``."""
     mask = mask.as_subclass(torch.Tensor) if isinstance(mask, torch.Tensor) else torch.as_tensor(mask)

@@ -677,14 +677,23 @@ class RAFT:
         return np.concatenate(results, axis=0)
 
     # ---- evaluation plumbing (reference model.py:111-170)
-    def compile(self, optimizer=None, clip_norm=None, loss=None, epe=None, trainable='all', tape_dtype='f32', **kwargs):
+    def compile(self, optimizer=None, clip_norm=None, loss=None, epe=None, trainable='all', tape_dtype='f32', bidirectional=False,
+                occlusion=True, alpha=image_ops.CONSISTENCY_ALPHA, beta=image_ops.CONSISTENCY_BETA, **kwargs):
         """reference model.py:111-124.  ``loss`` / ``epe`` default to ``tf_raft_amd.losses.sequence_loss`` /
         ``end_point_error``; ``loss=losses.PhotometricSequenceLoss(...)`` makes ``train_step`` take unlabelled pairs
         ``(image1, image2)`` or ``(image1, image2, mask)`` and report ``loss`` / ``photometric`` / ``smoothness`` (DESIGN.md
         section 17; ``test_step`` still wants ground truth), and ``census`` when the loss has ``census_weight > 0`` (section 18);
         ``losses.SSIMSequenceLoss(..., ssim_weight > 0)`` adds ``ssim`` (section 19).  ``trainable``: which weights ``train_step`` updates -- ``'all'``
         (the reference's behaviour: encoders, norms and update block) or ``'update_block'`` (encoders frozen, run by the
-        inference kernels)."""
+        inference kernels).
+
+        ``bidirectional=True`` (needs a ``PhotometricSequenceLoss``) makes ``train_step`` train both
+        directions of every pair in one step -- ``(image1, image2)`` or ``(image1, image2, (mask1, mask2))``, the loss the mean
+        of the two directions -- and, while ``model.occlusion`` is true, leave out of the data terms the pixels that fail the
+        forward-backward test of the step's own last predictions (``alpha`` / ``beta`` as in ``image_ops.flow_consistency``;
+        the defaults are UnFlow's constants, not tuned here).  ``occlusion`` sets ``model.occlusion``, a plain bool that may be
+        flipped between steps; the step also reports ``occluded``, the running mean of the occluded share, whether or not the
+        mask is applied, and keeps its ``(2N, H, W)`` uint8 mask in ``model.last_visibility``."""
         from . import losses
         if kwargs:
             raise TypeError(f'unexpected keyword arguments {sorted(kwargs)}')
@@ -692,6 +701,14 @@ class RAFT:
             raise ValueError(f"trainable must be 'all' or 'update_block', got {trainable!r}")
         if tape_dtype not in ('f32', 'bf16'):     # bf16: the loop's activation tape is STORED as bf16 (BASELINE configs[4]), fp32 arithmetic
             raise ValueError(f"tape_dtype must be 'f32' or 'bf16', got {tape_dtype!r}")
+        if not isinstance(bidirectional, (bool, np.bool_)) or not isinstance(occlusion, (bool, np.bool_)):
+            raise ValueError(f'bidirectional and occlusion must be True or False, got {bidirectional!r} / {occlusion!r}')
+        if bidirectional and not isinstance(loss, losses.PhotometricSequenceLoss):
+            raise ValueError(f'bidirectional=True trains on unlabelled pairs: it needs loss=losses.PhotometricSequenceLoss(...) '
+                             f'(or a subclass), got {loss!r}')
+        self.consistency = self._check_consistency(alpha, beta)
+        self.bidirectional, self.occlusion = bool(bidirectional), bool(occlusion)
+        self.last_visibility = None
         self.optimizer = optimizer
         self.clip_norm = clip_norm
         self.loss = loss if loss is not None else losses.sequence_loss
@@ -704,9 +721,9 @@ class RAFT:
             self.flow_metrics.update((k, losses.Mean(name=k)) for k in self._unlabelled_keys()[1:])
 
     def _unlabelled_keys(self):
-        """What ``train_step`` reports under a PhotometricSequenceLoss."""
+        """What ``train_step`` reports under a PhotometricSequenceLoss (``occluded``: in bidirectional mode)."""
         on = [k for k in ('census', 'ssim') if getattr(self.loss, k + '_weight', 0.0) > 0]
-        return ('loss', 'photometric', *on, 'smoothness')
+        return ('loss', 'photometric', *on, 'smoothness') + (('occluded',) if getattr(self, 'bidirectional', False) else ())
 
     BN_MOMENTUM = 0.99      # Keras BatchNormalization default (extractor.py:10 passes none)
 
@@ -718,7 +735,10 @@ class RAFT:
         ``compile(..., trainable='update_block')`` the encoders stay frozen and run on the inference kernels.
         The step is orchestrated from Python; the updated master weights are re-packed for the kernels ON THE DEVICE, one launch
         per layer and use (``raft_pack_train_conv_f32``).  It is the functional path (parity-tested against autograd on the
-        oracle), not yet a tuned one.  RAFT and SmallRAFT."""
+        oracle), not yet a tuned one.  RAFT and SmallRAFT.
+        After ``compile(..., bidirectional=True)`` the step runs the doubled batch ``[image1 | image2]``
+        against ``[image2 | image1]`` with the feature encoder once per frame, and the mask of the loss comes from one
+        ``raft_flow_visibility_f32`` launch on its own last prediction."""
         from . import grad, losses
         if not hasattr(self, 'flow_metrics'):
             raise RuntimeError('call compile() before train_step()')
@@ -726,7 +746,10 @@ class RAFT:
         if not photometric and self.loss is not losses.sequence_loss:
             raise NotImplementedError('train_step differentiates tf_raft_amd.losses.sequence_loss and '
                                       'tf_raft_amd.losses.PhotometricSequenceLoss only')
-        if photometric and len(data) not in (2, 3):
+        bidirectional = photometric and self.bidirectional
+        if bidirectional:                           # arity and shapes, before anything is enqueued
+            pair_masks = losses._check_bidirectional(data)
+        elif photometric and len(data) not in (2, 3):
             raise ValueError(f'train_step with PhotometricSequenceLoss expects (image1, image2) or (image1, image2, mask), '
                              f'got {len(data)} items')
         if not photometric and len(data) != 4:
@@ -737,7 +760,7 @@ class RAFT:
                                '(tf_raft_amd.training.AdamW)')
         if photometric:
             image1, image2, flow, valid = data[0], data[1], None, None
-            unlabelled = losses._check_unlabelled(data, ())[:3]       # shapes, before anything is enqueued
+            unlabelled = None if bidirectional else losses._check_unlabelled(data, ())[:3]       # shapes, before anything is enqueued
         else:
             image1, image2, flow, valid = data
         image1 = _dev.to_device(image1).as_subclass(torch.Tensor).to(torch.float32)
@@ -745,7 +768,14 @@ class RAFT:
         # the ground truth goes to the device NOW: an upload from pageable host memory waits for everything already queued on
         # the stream, and in front of the loss that is the whole forward pass (the host would enqueue the backward only after
         # the GPU had drained: 20 ms of a 85 ms step)
-        if photometric:                             # (the mask is uploaded now for the same reason)
+        if bidirectional:
+            # the doubled batch [image1 | image2] against [image2 | image1]; everything below sees 2N pairs
+            pairs = image1.shape[0]
+            user_mask = None
+            if pair_masks is not None:
+                user_mask = torch.cat([losses._mask_to_device(m, image1.device) for m in pair_masks], dim=0).contiguous()
+            image1, image2 = torch.cat([image1, image2], dim=0), torch.cat([image2, image1], dim=0)
+        elif photometric:                           # (the mask is uploaded now for the same reason)
             y_true = (image1, image2) if unlabelled[2] is None else (image1, image2, losses._mask_to_device(unlabelled[2], image1.device))
         else:
             flow, valid = losses._truth((flow, valid))
@@ -766,8 +796,11 @@ class RAFT:
         if full:
             ones = torch.ones_like(image1)
             x1 = grad._axpby(2.0 / 255.0, image1.contiguous(), -1.0, ones)            # model.py:70-71
-            x2 = grad._axpby(2.0 / 255.0, image2.contiguous(), -1.0, ones)
-            fout, ftape = grad.encoder_forward(wts, 'fnet', torch.cat([x1, x2], dim=0), training=True)     # model.py:74
+            if bidirectional:                       # x1 already holds every frame once: both roles of a frame share its features
+                frames = x1
+            else:
+                frames = torch.cat([x1, grad._axpby(2.0 / 255.0, image2.contiguous(), -1.0, ones)], dim=0)
+            fout, ftape = grad.encoder_forward(wts, 'fnet', frames, training=True)     # model.py:74
             fout = fout.as_subclass(torch.Tensor)
             cnet, ctape = grad.encoder_forward(wts, 'cnet', x1, training=True)         # model.py:82
             cnet = cnet.as_subclass(torch.Tensor)
@@ -782,12 +815,16 @@ class RAFT:
                 fout, mf = grad.dropout_forward(fout, self.drop_rate, seed=base)
                 cnet, mc = grad.dropout_forward(cnet, self.drop_rate, seed=base + 1)
                 drop_masks = [mf, mc]
-            fmap1, fmap2 = fout[:B].contiguous(), fout[B:].contiguous()
+            fmap1, fmap2 = grad.mirror_feature_maps(fout, pairs) if bidirectional else (fout[:B].contiguous(), fout[B:].contiguous())
         else:
             if self.drop_rate:
                 raise NotImplementedError("drop_rate > 0 with trainable='update_block': dropout sits on the (frozen) encoder "
                                           "outputs; train all weights or use drop_rate=0")
-            fmap1, fmap2 = self.fnet([image1, image2], training=False, _raw_images=True)
+            if bidirectional:
+                halves = self.fnet([image1[:pairs], image1[pairs:]], training=False, _raw_images=True)
+                fmap1, fmap2 = grad.mirror_feature_maps(torch.cat([t.as_subclass(torch.Tensor) for t in halves], dim=0), pairs)
+            else:
+                fmap1, fmap2 = self.fnet([image1, image2], training=False, _raw_images=True)
             cnet = self.cnet(image1, training=False, _raw_images=True)
         correlation = CorrBlock(fmap1, fmap2, num_levels=self.corr_levels, radius=self.corr_radius)   # model.py:77
         st = self._get_state(B, h, w, image1.device)
@@ -798,8 +835,17 @@ class RAFT:
         prefix = 'update_block'
         ub = {k: v for k, v in wts.items() if k.startswith(prefix)}
         preds, tape = grad.loop_forward(ub, correlation, net0, inp, self.iters, prefix, self.variant, tape_dtype=self.tape_dtype)
+        if bidirectional:
+            # the mask of the loss from THIS forward pass's last prediction: a constant of the gradient.  Without occlusion
+            # and without user masks it is all ones and the loss kernels' "no mask" specialisation runs.
+            last = preds[-1].as_subclass(torch.Tensor).contiguous()
+            visible, occluded = image_ops.flow_visibility_launch(last, pairs, user_mask, *self.consistency, apply=self.occlusion)
+            self.last_visibility = _dev.wrap(visible)
+            y_true = (image1, image2, visible) if (self.occlusion or user_mask is not None) else (image1, image2)
         if photometric:                             # value and gradient share the gathers: one launch per term
             terms, d_preds = self.loss.value_and_grad(y_true, preds)
+            if bidirectional:
+                terms = dict(terms, occluded=_dev.wrap(occluded))
         else:
             loss = self.loss([flow, valid], preds)
             d_preds = grad.sequence_loss_grad((flow, valid), preds)
@@ -807,7 +853,10 @@ class RAFT:
         stats = {}
         if full:
             d_f1, d_f2 = grad.corr_build_backward(correlation, d_pyr)
-            d_fout = torch.cat([d_f1.as_subclass(torch.Tensor), d_f2.as_subclass(torch.Tensor)], dim=0).contiguous()
+            if bidirectional:                       # the sum of a frame's two roles
+                d_fout = grad.mirror_feature_maps_backward(d_f1, d_f2, pairs)
+            else:
+                d_fout = torch.cat([d_f1.as_subclass(torch.Tensor), d_f2.as_subclass(torch.Tensor)], dim=0).contiguous()
             d_cnet = grad.prepare_state_backward(net0, inp, d_net0, d_inp)
             if drop_masks:
                 d_fout = grad.dropout_backward(d_fout, drop_masks[0])
