@@ -314,6 +314,36 @@ int64_t raft_flow_visibility_workspace_doubles(void);
 int raft_flow_visibility_f32(const float *flows, const uint8_t *mask, uint8_t *visible, float *occluded_fraction, int N, int H, int W,
                              float alpha, float beta, int apply, double *workspace, void *stream);
 
+/* The range map of a flow (Wang et al. 2018): a forward splat of the flow itself, the second occlusion test.
+ * The source pixel at integer (x, y) with vector (u, v) has the sample position sx = float(x) + u, sy = float(y) + v of above.  It
+ * contributes iff -1 < sx < float(W) and -1 < sy < float(H), compared on the floats (a NaN, an infinity or 1e30 fails).  Then
+ * x0 = floor(sx), a = sx - x0 in float32, qa = (int)rintf(a * 4096.0f) in 0 .. 4096, likewise y0, b, qb, and the corner
+ * (x0 + dx, y0 + dy) receives the integer weight (dx ? qa : 4096 - qa) * (dy ? qb : 4096 - qb); the four sum to exactly 2^24.  A
+ * corner outside the frame or of weight 0 receives nothing.  acc[n, cy, cx] is the uint64 sum of the weights that land there:
+ * exact in any arrival order, so every entry below repeats bit for bit.
+ *   raft_flow_range_map_f32: range[n, y, x] = float(double(acc) * 2^-24), (N, H, W) floats; 1.0 under zero flow.
+ *   raft_flow_range_occlusion_f32: with acc_ba the sums of flow_b (it lives on frame B's grid and lands on frame A's) and
+ *         T = (uint64)ceil(double(threshold) * 2^24), compared on the integers,
+ *         occluded_a = acc_ba < T || !(flow_a's pixel IN FRAME)
+ *     so a mask means what raft_flow_consistency_f32's means: 1 = occluded or out of frame.  occluded_b: NULL (then only flow_b
+ *     is splatted), or the same with the roles swapped.  Masks are uint8 (N, H, W).
+ *   raft_flow_range_visibility_f32: raft_flow_visibility_f32 with this test: `flows` (2N, H, W, 2), slice s against the sums of
+ *     slice s + N (s < N) or s - N; mask, visible, occluded_fraction and `apply` as there.  `records`:
+ *     raft_flow_visibility_workspace_doubles() doubles.
+ * `workspace` holds the sums: raft_flow_range_workspace_bytes(slices, H, W) bytes, 8-byte aligned, with slices = N for the map
+ * and for occluded_b == NULL, else 2N (0: the sizes are refused).  Three phases on `stream`: the sums are zeroed, one thread per
+ * source pixel adds up to four weights with 64-bit integer atomics, one thread per destination pixel writes the result (the
+ * visibility entry adds its one-workgroup sum of the records).  Errors, in this order: RAFT_E_NULL for a NULL required pointer;
+ * RAFT_E_SHAPE for a non-positive size, N * H * W * 2 (2N for the visibility entry) of 2^31 elements or more, H * W above 2^28,
+ * a threshold outside (0, 1] or NaN, `apply` other than 0 or 1; RAFT_E_ALIGN for a flow, a workspace or records that are not
+ * 8-byte aligned.  All checks precede the first launch. */
+int64_t raft_flow_range_workspace_bytes(int slices, int H, int W);
+int raft_flow_range_map_f32(const float *flow, float *range, int N, int H, int W, void *workspace, void *stream);
+int raft_flow_range_occlusion_f32(const float *flow_a, const float *flow_b, uint8_t *occluded_a, uint8_t *occluded_b, int N, int H, int W,
+                                  float threshold, void *workspace, void *stream);
+int raft_flow_range_visibility_f32(const float *flows, const uint8_t *mask, uint8_t *visible, float *occluded_fraction, int N, int H,
+                                   int W, float threshold, int apply, void *workspace, double *records, void *stream);
+
 /* ------------------------------------------------------------------ training augmentation */
 
 /* FlowAugmentor (reference tf_raft/datasets/augmentor.py:9-129, used at dataset.py:87-91) composed into one gather (the sparse

@@ -32,7 +32,9 @@ through the same crop-or-pad window, so a prediction leaves the device as a 3-by
 flow, and the forward-backward test of two flows that marks occluded and out-of-frame pixels, one launch each (``raft_warp_*`` /
 ``raft_flow_consistency_f32``, tf_raft_amd/csrc/flow_check.hip).  ``flow_visibility_launch`` is that test inside a bidirectional
 training step: the 2N flows of the doubled batch in, the mask of the loss and the occluded share out
-(``raft_flow_visibility_f32``).
+(``raft_flow_visibility_f32``).  ``range_map`` / ``range_occlusion`` are the second occlusion test: every
+vector splatted forward with integer bilinear weights, a pixel that receives too little is occluded (``raft_flow_range_*``,
+tf_raft_amd/csrc/flow_splat.hip); ``range_visibility_launch`` is its in-step form.
 
 ``forward_interpolate`` projects a low-resolution flow forward along itself: the start of the next pair's
 recurrence in a video stream (``raft_forward_interpolate_f32``, tf_raft_amd/csrc/flow_init.hip; ``tf_raft_amd.video``).
@@ -768,6 +770,129 @@ def flow_consistency(flow_forward, flow_backward, alpha=CONSISTENCY_ALPHA, beta=
     t, f4, _, _ = _flow_4d(flow_forward, None)
     b = _flow_like(flow_backward, t.shape[:-1], 'flow_consistency')
     occ_f, occ_b = flow_consistency_launch(f4, b.reshape(f4.shape), alpha, beta)
+    return _dev.wrap(occ_f.view(t.shape[:-1])), _dev.wrap(occ_b.view(t.shape[:-1]))
+
+
+# ------------------------------------------------------------------------------------------ range map: the second occlusion test
+RANGE_THRESHOLD = 0.5      # a choice, not a tuned value
+OCCLUSION_TESTS = ('consistency', 'range')
+
+
+def check_range_threshold(threshold):
+    """``threshold`` of the range-map test as a float: a number (no bool) whose float32 value lies in ``(0, 1]``."""
+    if isinstance(threshold, (bool, np.bool_)) or not isinstance(threshold, (int, float, np.integer, np.floating)):
+        raise ValueError(f'threshold must be a number, got {threshold!r}')
+    try:
+        with np.errstate(over='ignore'):
+            t = float(np.float32(threshold))
+    except OverflowError:
+        t = float('inf')
+    if not 0.0 < t <= 1.0:
+        raise ValueError(f'threshold must lie in (0, 1] as a float32, got {threshold!r}')
+    return t
+
+
+def check_occlusion_test(occlusion_test):
+    """``'consistency'`` (the forward-backward test) or ``'range'`` (the range map, section 21)."""
+    if not isinstance(occlusion_test, str) or occlusion_test not in OCCLUSION_TESTS:
+        raise ValueError(f"occlusion_test must be 'consistency' or 'range', got {occlusion_test!r}")
+    return occlusion_test
+
+
+def _range_workspace(device, slices, H, W, records=0):
+    """The uint64 sums of ``slices`` frames (and ``records`` doubles behind them) in the stream's grow-only workspace."""
+    from . import losses
+    nbytes = int(_dev.lib().raft_flow_range_workspace_bytes(int(slices), int(H), int(W)))
+    if nbytes <= 0:
+        raise ValueError(f'the range map takes frames of up to 2^28 pixels and flows of fewer than 2^31 floats, got {slices} x {H} x {W}')
+    ws = losses._workspace(device, nbytes + 8 * int(records))
+    return ws, _dev.ptr(ws) + nbytes
+
+
+def range_map_launch(flow: torch.Tensor, out=None) -> torch.Tensor:
+    """The launches themselves (``raft_flow_range_map_f32``): a contiguous float32 device flow ``(N, H, W, 2)`` -> its range map,
+    float32 ``(N, H, W)`` on the CURRENT stream (a plain tensor), written into ``out`` when given."""
+    if flow.dim() != 4 or flow.shape[-1] != 2:
+        raise ValueError(f'expected a flow (N, H, W, 2), got {tuple(flow.shape)}')
+    _check_flow(flow, 'range_map')
+    N, H, W, _ = flow.shape
+    out = _check_out(out, (N, H, W), torch.float32, flow.device)
+    with torch.cuda.device(flow.device):
+        ws, _ = _range_workspace(flow.device, N, H, W)
+        check(_dev.lib().raft_flow_range_map_f32(_dev.ptr(flow), _dev.ptr(out), N, H, W, _dev.ptr(ws), _dev.stream_ptr()), 'range_map')
+    return out
+
+
+def range_occlusion_launch(flow_a: torch.Tensor, flow_b: torch.Tensor, threshold: float = RANGE_THRESHOLD, both: bool = True):
+    """The launches themselves (``raft_flow_range_occlusion_f32``): two contiguous float32 device flows ``(N, H, W, 2)`` -> the
+    uint8 masks ``(occluded_a, occluded_b)``, each ``(N, H, W)`` with 1 = occluded, on the CURRENT stream (plain tensors;
+    ``both=False``: direction a alone, only ``flow_b`` is splatted and ``occluded_b`` is None)."""
+    if flow_a.dim() != 4 or flow_a.shape[-1] != 2 or flow_a.shape != flow_b.shape or flow_a.device != flow_b.device:
+        raise ValueError(f'expected two flows (N, H, W, 2) of one shape and device, got {tuple(flow_a.shape)} on {flow_a.device} / '
+                         f'{tuple(flow_b.shape)} on {flow_b.device}')
+    _check_flow(flow_a, 'range_occlusion')
+    _check_flow(flow_b, 'range_occlusion')
+    N, H, W, _ = flow_a.shape
+    masks = torch.empty((2 if both else 1, N, H, W), device=flow_a.device, dtype=torch.uint8)
+    with torch.cuda.device(flow_a.device):
+        ws, _ = _range_workspace(flow_a.device, 2 * N if both else N, H, W)
+        check(_dev.lib().raft_flow_range_occlusion_f32(_dev.ptr(flow_a), _dev.ptr(flow_b), _dev.ptr(masks[0]),
+                                                       _dev.ptr(masks[1]) if both else None, N, H, W, float(threshold), _dev.ptr(ws),
+                                                       _dev.stream_ptr()), 'range_occlusion')
+    return masks[0], (masks[1] if both else None)
+
+
+def range_visibility_launch(flows: torch.Tensor, N: int, mask=None, threshold: float = RANGE_THRESHOLD, apply: bool = True,
+                            want_visible: bool = True):
+    """``flow_visibility_launch`` with the range-map test (``raft_flow_range_visibility_f32``): contiguous
+    float32 device flows ``(2N, H, W, 2)``, the N forward flows in front of the N backward ones, and an optional contiguous uint8
+    ``mask`` ``(2N, H, W)`` -> ``(visible, occluded_fraction)`` on the CURRENT stream (plain tensors), with the same meaning."""
+    if flows.dim() != 4 or flows.shape[-1] != 2 or flows.shape[0] != 2 * int(N) or int(N) < 1:
+        raise ValueError(f'expected flows (2N, H, W, 2) with N = {N}, got {tuple(flows.shape)}')
+    _check_flow(flows, 'range_visibility')
+    B, H, W, _ = flows.shape
+    if mask is not None:
+        mask = _check_out(mask, (B, H, W), torch.uint8, flows.device)
+    visible = torch.empty((B, H, W), device=flows.device, dtype=torch.uint8) if want_visible else None
+    fraction = torch.empty((), device=flows.device, dtype=torch.float32)
+    lib = _dev.lib()
+    with torch.cuda.device(flows.device):
+        ws, records = _range_workspace(flows.device, B, H, W, lib.raft_flow_visibility_workspace_doubles())
+        check(lib.raft_flow_range_visibility_f32(_dev.ptr(flows), _dev.ptr(mask) if mask is not None else None,
+                                                 _dev.ptr(visible) if visible is not None else None, _dev.ptr(fraction), int(N), H, W,
+                                                 float(threshold), int(bool(apply)), _dev.ptr(ws), records, _dev.stream_ptr()),
+              'range_visibility')
+    return visible, fraction
+
+
+def range_map(flow) -> torch.Tensor:
+    """The range map of a float32 flow ``(..., H, W, 2)`` (NumPy or torch, host or device; Wang et al. 2018):
+    a float32 device tensor ``(..., H, W)`` that says how much of the flow's own grid lands on each pixel when every vector is
+    splatted forward with bilinear weights -- 1 under zero flow, 0 where no vector ends, above 1 where several do.  The weights are
+    quantised to 1 / 4096 per axis and summed as integers, so the result does not depend on the order of the adds: it repeats bit for
+    bit.  A vector that ends outside ``(-1, W) x (-1, H)`` or is not finite contributes nothing."""
+    shape = tuple(flow.shape) if hasattr(flow, 'shape') else np.shape(flow)
+    if len(shape) < 3 or shape[-1] != 2:
+        raise ValueError(f'range_map expects a flow (..., H, W, 2), got {shape}')
+    if 0 in shape:
+        raise ValueError(f'empty input {shape}')
+    t = _on_device(flow)
+    if t.dtype != torch.float32:
+        raise TypeError(f'a flow is float32, got {t.dtype}')
+    return _dev.wrap(range_map_launch(t.reshape((-1,) + shape[-3:])).view(shape[:-1]))
+
+
+def range_occlusion(flow_forward, flow_backward, threshold=RANGE_THRESHOLD):
+    """The range-map occlusion test of two float32 flows ``(H, W, 2)`` or ``(N, H, W, 2)`` (NumPy or torch, host or device):
+    ``(occluded_forward, occluded_backward)``, uint8 device tensors ``(..., H, W)`` with 1 where a vector cannot be trusted.  A pixel
+    of frame 1 is occluded when less than ``threshold`` of frame 2's grid lands on it under ``flow_backward`` (``range_map``; no
+    pixel of frame 2 came from there) or when its own vector leaves the frame, so the masks mean what ``flow_consistency``'s do.
+    ``threshold`` lies in ``(0, 1]``; the comparison is made on the integer sums.  A local expansion by a factor ``s`` thins the
+    range to about ``1 / s^2``: under a zoom of more than about 1.4 the default marks everything."""
+    threshold = check_range_threshold(threshold)
+    t, f4, _, _ = _flow_4d(flow_forward, None)
+    b = _flow_like(flow_backward, t.shape[:-1], 'range_occlusion')
+    occ_f, occ_b = range_occlusion_launch(f4, b.reshape(f4.shape), threshold)
     return _dev.wrap(occ_f.view(t.shape[:-1])), _dev.wrap(occ_b.view(t.shape[:-1]))
 
 

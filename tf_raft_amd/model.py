@@ -543,7 +543,8 @@ class RAFT:
         image1, image2, *_ = data
         return self._predict_final(image1, image2, pipelined=_pipelined)
 
-    def predict_step_bidirectional(self, data, alpha=image_ops.CONSISTENCY_ALPHA, beta=image_ops.CONSISTENCY_BETA):
+    def predict_step_bidirectional(self, data, alpha=image_ops.CONSISTENCY_ALPHA, beta=image_ops.CONSISTENCY_BETA,
+                                   occlusion_test='consistency', range_threshold=image_ops.RANGE_THRESHOLD):
         """The flow in both directions with occlusion masks: ``BidirectionalFlow(forward, backward, occluded_forward,
         occluded_backward)`` of device tensors for ``data = (image1, image2)`` -- ``forward`` what ``predict_step((image1,
         image2))`` predicts, ``backward`` what ``predict_step((image2, image1))`` does, both ``(N, H, W, 2)`` float32 at the
@@ -554,12 +555,20 @@ class RAFT:
         on the caller's stream (a model with pipelined loops in flight joins them first, as a training-mode call does), then one
         consistency launch on the flows that are returned: with a ``target_size`` the call's route takes the 2N predictions back
         to the frames' size first (``fit='tile'``: 2N * K tiles blend to 2N frames).  Cost: the memory and time of ``__call__``
-        on 2N pairs (docs/NOTEBOOK.md section 21 has the measurement)."""
+        on 2N pairs (docs/NOTEBOOK.md section 21 has the measurement).
+
+        ``occlusion_test='range'`` takes the masks from the range map instead (``image_ops.range_occlusion(forward, backward,
+        range_threshold)``), on the same returned flows; ``alpha`` / ``beta`` are then checked and unused."""
         alpha, beta = self._check_consistency(alpha, beta)
+        occlusion_test = image_ops.check_occlusion_test(occlusion_test)
+        range_threshold = image_ops.check_range_threshold(range_threshold)
         image1, image2, *_ = data
         flows = self._predict_final(image1, image2, pipelined=False, mirror=True).as_subclass(torch.Tensor)
         N = flows.shape[0] // 2
-        occ_f, occ_b = image_ops.flow_consistency_launch(flows[:N], flows[N:], alpha, beta)
+        if occlusion_test == 'range':
+            occ_f, occ_b = image_ops.range_occlusion_launch(flows[:N], flows[N:], range_threshold)
+        else:
+            occ_f, occ_b = image_ops.flow_consistency_launch(flows[:N], flows[N:], alpha, beta)
         return BidirectionalFlow(_dev.wrap(flows[:N]), _dev.wrap(flows[N:]), _dev.wrap(occ_f), _dev.wrap(occ_b))
 
     @staticmethod
@@ -582,7 +591,8 @@ class RAFT:
             batches = itertools.islice(batches, int(steps))
         return ((b[0], b[1]) for b in batches), (n if steps is None else None)
 
-    def predict_bidirectional(self, x, batch_size=None, steps=None, alpha=image_ops.CONSISTENCY_ALPHA, beta=image_ops.CONSISTENCY_BETA):
+    def predict_bidirectional(self, x, batch_size=None, steps=None, alpha=image_ops.CONSISTENCY_ALPHA, beta=image_ops.CONSISTENCY_BETA,
+                              occlusion_test='consistency', range_threshold=image_ops.RANGE_THRESHOLD):
         """``predict_step_bidirectional`` over all pairs of ``x`` (as for ``predict()``: ``[image1, image2]`` arrays split into
         batches of ``batch_size``, Keras' default 32, or an iterable of ``(image1, image2, ...)`` batches; ``steps`` limits the
         number of batches): the same named tuple as host arrays, flows ``(N, H, W, 2)`` float32 and masks ``(N, H, W)`` uint8.
@@ -590,11 +600,13 @@ class RAFT:
         copied back synchronously."""
         from .prefetch import prefetch_to_device
         alpha, beta = self._check_consistency(alpha, beta)
+        occlusion_test = image_ops.check_occlusion_test(occlusion_test)
+        range_threshold = image_ops.check_range_threshold(range_threshold)
         dev = _dev.require_gpu()
         batches, _ = self._pair_batches(x, batch_size, steps)
         parts = [[], [], [], []]
         for image1, image2 in prefetch_to_device(batches, buffer_size=1, device=dev):
-            for acc, t in zip(parts, self.predict_step_bidirectional((image1, image2), alpha, beta)):
+            for acc, t in zip(parts, self.predict_step_bidirectional((image1, image2), alpha, beta, occlusion_test, range_threshold)):
                 acc.append(t.as_subclass(torch.Tensor).cpu().numpy())
         if not parts[0]:
             raise ValueError('predict_bidirectional() received no batches')
@@ -678,7 +690,8 @@ class RAFT:
 
     # ---- evaluation plumbing (reference model.py:111-170)
     def compile(self, optimizer=None, clip_norm=None, loss=None, epe=None, trainable='all', tape_dtype='f32', bidirectional=False,
-                occlusion=True, alpha=image_ops.CONSISTENCY_ALPHA, beta=image_ops.CONSISTENCY_BETA, **kwargs):
+                occlusion=True, alpha=image_ops.CONSISTENCY_ALPHA, beta=image_ops.CONSISTENCY_BETA, occlusion_test='consistency',
+                range_threshold=image_ops.RANGE_THRESHOLD, **kwargs):
         """reference model.py:111-124.  ``loss`` / ``epe`` default to ``tf_raft_amd.losses.sequence_loss`` /
         ``end_point_error``; ``loss=losses.PhotometricSequenceLoss(...)`` makes ``train_step`` take unlabelled pairs
         ``(image1, image2)`` or ``(image1, image2, mask)`` and report ``loss`` / ``photometric`` / ``smoothness`` (DESIGN.md
@@ -693,7 +706,9 @@ class RAFT:
         forward-backward test of the step's own last predictions (``alpha`` / ``beta`` as in ``image_ops.flow_consistency``;
         the defaults are UnFlow's constants, not tuned here).  ``occlusion`` sets ``model.occlusion``, a plain bool that may be
         flipped between steps; the step also reports ``occluded``, the running mean of the occluded share, whether or not the
-        mask is applied, and keeps its ``(2N, H, W)`` uint8 mask in ``model.last_visibility``."""
+        mask is applied, and keeps its ``(2N, H, W)`` uint8 mask in ``model.last_visibility``.  ``occlusion_test='range'``
+        (with ``bidirectional=True`` only) takes that mask from the range map of the same predictions instead (DESIGN.md
+        section 21; ``range_threshold`` as in ``image_ops.range_occlusion``); everything else about the step stays."""
         from . import losses
         if kwargs:
             raise TypeError(f'unexpected keyword arguments {sorted(kwargs)}')
@@ -707,6 +722,10 @@ class RAFT:
             raise ValueError(f'bidirectional=True trains on unlabelled pairs: it needs loss=losses.PhotometricSequenceLoss(...) '
                              f'(or a subclass), got {loss!r}')
         self.consistency = self._check_consistency(alpha, beta)
+        self.occlusion_test = image_ops.check_occlusion_test(occlusion_test)
+        self.range_threshold = image_ops.check_range_threshold(range_threshold)
+        if self.occlusion_test == 'range' and not bidirectional:
+            raise ValueError("occlusion_test='range' is the mask of a bidirectional step: it needs bidirectional=True")
         self.bidirectional, self.occlusion = bool(bidirectional), bool(occlusion)
         self.last_visibility = None
         self.optimizer = optimizer
@@ -738,7 +757,8 @@ class RAFT:
         oracle), not yet a tuned one.  RAFT and SmallRAFT.
         After ``compile(..., bidirectional=True)`` the step runs the doubled batch ``[image1 | image2]``
         against ``[image2 | image1]`` with the feature encoder once per frame, and the mask of the loss comes from one
-        ``raft_flow_visibility_f32`` launch on its own last prediction."""
+        ``raft_flow_visibility_f32`` launch on its own last prediction (``occlusion_test='range'``:
+        ``raft_flow_range_visibility_f32``)."""
         from . import grad, losses
         if not hasattr(self, 'flow_metrics'):
             raise RuntimeError('call compile() before train_step()')
@@ -839,7 +859,10 @@ class RAFT:
             # the mask of the loss from THIS forward pass's last prediction: a constant of the gradient.  Without occlusion
             # and without user masks it is all ones and the loss kernels' "no mask" specialisation runs.
             last = preds[-1].as_subclass(torch.Tensor).contiguous()
-            visible, occluded = image_ops.flow_visibility_launch(last, pairs, user_mask, *self.consistency, apply=self.occlusion)
+            if self.occlusion_test == 'range':
+                visible, occluded = image_ops.range_visibility_launch(last, pairs, user_mask, self.range_threshold, apply=self.occlusion)
+            else:
+                visible, occluded = image_ops.flow_visibility_launch(last, pairs, user_mask, *self.consistency, apply=self.occlusion)
             self.last_visibility = _dev.wrap(visible)
             y_true = (image1, image2, visible) if (self.occlusion or user_mask is not None) else (image1, image2)
         if photometric:                             # value and gradient share the gathers: one launch per term
