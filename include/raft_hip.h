@@ -784,6 +784,36 @@ int raft_ssim_loss_f32(const float *image1, const float *image2, const uint8_t *
                        int n_predictions, int B, int H, int W, double gamma, float ssim_weight, float upstream,
                        const float *add_to, float *out2, float *d_preds, int accumulate, void *workspace, void *stream);
 
+/* Self-supervision term and its gradient (csrc/selfsup_loss.hip): the predictions of a student pass over a
+ * crop against the flow of a teacher pass over the full frames, held constant.
+ *   teacher (B, Ht, Wt, 2) float; teacher_visible NULL or uint8 (B, Ht, Wt), nonzero = the teacher is trusted there.  Both are read
+ *   IN PLACE through the window: student pixel (y, x) of slice b faces teacher pixel (y + oy, x + ox).
+ *   student_visible NULL or uint8 (B, H, W), nonzero = the student sees the pixel itself: it is left out.
+ *   preds: n_predictions flows (B, H, W, 2), prediction i at preds + i * pred_stride (floats).
+ * With eps2 = eps*eps rounded once to float32, rho(d) = sqrtf(d*d + eps2), w_i = (float)gamma^(n-i-1) as raft_sequence_loss_f32
+ * builds it, t the teacher vector a pixel faces:
+ *   used = (teacher_visible == NULL || teacher_visible != 0 there) && (student_visible == NULL || student_visible == 0 there)
+ *          && both components of t finite
+ *   dist_i  = sum_used sum_k rho(p_i[k] - t[k]) / (B*H*W*2)                     (the divisor counts ALL elements)
+ *   out3[0] = (add_to ? *add_to : 0) + weight * sum_i w_i * dist_i  (formed in double, rounded once; add_to may be out3);
+ *   out3[1] = dist_{n-1};      out3[2] = (float)(#used / (B*H*W))  (an exact count, divided in double)
+ * d_preds: NULL (value only), or the layout of preds; every element is touched exactly once with
+ * ((upstream * weight) * w_i) * ((d / rho(d)) * (float)(1 / (B*H*W*2))) where used, else 0 -- stored (accumulate == 0) or added to
+ * what is there with one float32 addition (accumulate == 1); gaps of a pred_stride larger than 2*B*H*W are not touched.  The
+ * teacher and both masks are constants of the gradient.
+ * Deterministic (no atomics, no memset): float64 partial records in `workspace` (raft_selfsup_loss_workspace_doubles()
+ * doubles), added in index order by a second one-workgroup launch; the count of used pixels goes through the same records.
+ * In this order: RAFT_E_NULL: teacher, preds, out3 or workspace NULL.  RAFT_E_SHAPE: a non-positive size, a window that does not
+ * lie inside the teacher (oy < 0, ox < 0, oy + H > Ht, ox + W > Wt), B*Ht*Wt*3 of 2^31 or more, pred_stride < 2*B*H*W, gamma /
+ * weight negative or not finite, eps or eps*eps (in float32) not positive and finite, upstream not finite, accumulate not 0 or 1.
+ * RAFT_E_UNSUPPORTED: n_predictions > 64 or an odd pred_stride.  RAFT_E_ALIGN: teacher, preds, d_preds or workspace not 8-byte
+ * aligned.  All checks precede the first launch. */
+int64_t raft_selfsup_loss_workspace_doubles(void);
+int raft_selfsup_loss_f32(const float *teacher, const uint8_t *teacher_visible, int Ht, int Wt, int oy, int ox,
+                          const uint8_t *student_visible, const float *preds, int64_t pred_stride, int n_predictions, int B, int H,
+                          int W, double gamma, float weight, float eps, float upstream, const float *add_to, float *out3,
+                          float *d_preds, int accumulate, double *workspace, void *stream);
+
 /* Backward of raft_corr_lookup_f32 (CorrBlock.retrieve + bilinear_sampler, corr.py:116-152, 28-69), with TensorFlow's
  * gradient conventions: floor / ceil contribute nothing, clip_by_value passes the gradient on [0, size - 1].
  * d_out: (B, h, w, ld_out) upstream gradient of the lookup output (first levels*(2r+1)^2 channels used).

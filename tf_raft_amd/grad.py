@@ -262,6 +262,24 @@ def ssim_sequence_loss_grad(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_w
                                              ssim_weight)[1]
 
 
+def selfsup_loss_value_and_grad(teacher, preds, origin=(0, 0), teacher_visible=None, student_visible=None, gamma=0.8, weight=0.3,
+                                eps=0.001, upstream=1.0):
+    """``(terms, grads)`` of ``losses.SelfSupervisionLoss`` from ONE launch: ``terms`` is ``{'loss',
+    'selfsup', 'selfsup_used'}`` and ``grads[i]`` = ``upstream * d loss / d preds[i]``, shaped like the student's predictions.
+    The teacher flow ``(B, Ht, Wt, 2)`` and both masks are constants; student pixel ``(y, x)`` faces teacher pixel
+    ``(y + origin[0], x + origin[1])``."""
+    return losses.SelfSupervisionLoss(gamma, weight, eps).value_and_grad(teacher, preds, origin, teacher_visible, student_visible,
+                                                                         upstream)
+
+
+def add_gradients(first, second):
+    """``first[k] + second[k]`` per tensor, one float32 addition each in that order (``raft_axpby_f32``): the summed gradient of a
+    step that ran two graded passes over the same weights.  Both map the same names to contiguous float32 device tensors."""
+    if sorted(first) != sorted(second):
+        raise ValueError('the two passes graded different tensors')
+    return {k: _axpby(1.0, first[k], 1.0, second[k]) for k in first}
+
+
 def corr_lookup_backward(corr_block, coords, d_out, d_pyramid=None, want_pyramid_grad=True):
     """Backward of ``corr_block.retrieve(coords)`` (reference corr.py:116-152) for the upstream gradient ``d_out``
     (bs, h, w, levels*(2r+1)^2).  Returns ``(d_coords, d_pyramid)``: ``d_coords`` (bs, h, w, 2) and the gradient w.r.t.

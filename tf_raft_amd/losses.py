@@ -9,6 +9,7 @@ and the self-supervised loss the reference does not have (DESIGN.md section 17; 
     PhotometricSequenceLoss(gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, census_weight=0.0)
     SSIMSequenceLoss(gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, census_weight=0.0, ssim_weight=0.0)
     photometric_sequence_loss(y_true, y_pred, ...)                y_true = (image1, image2) or (image1, image2, mask)
+    SelfSupervisionLoss(gamma=0.8, weight=0.3, eps=0.001)         student predictions on a crop against a teacher flow (section 22)
 
 ``y_true = (flow_gt, valid)`` with ``flow_gt`` (bs, H, W, 2) float and ``valid`` (bs, H, W) bool; ``y_pred`` is the list
 of flow predictions the model returns (``sequence_loss``) or one prediction (``end_point_error``).  Arrays may be
@@ -19,6 +20,7 @@ CPU fallback.
 from __future__ import annotations
 
 import math
+import numbers
 
 import torch
 
@@ -342,6 +344,113 @@ class SSIMSequenceLoss(PhotometricSequenceLoss):
 def photometric_sequence_loss(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, census_weight=0.0):
     """``PhotometricSequenceLoss(gamma, smooth_weight, edge_weight, eps, census_weight)(y_true, y_pred)``."""
     return PhotometricSequenceLoss(gamma, smooth_weight, edge_weight, eps, census_weight)(y_true, y_pred)
+
+
+# ---------------------------------------------------------------- self-supervision: student against teacher (DESIGN.md section 22)
+def _selfsup_params(gamma, weight, eps, upstream=1.0):
+    """The checks raft_selfsup_loss_f32 makes on its parameters: finite non-negative ``gamma`` / ``weight``, ``eps > 0``, finite
+    upstream."""
+    gamma, _, _, eps, upstream = _photometric_params(gamma, 0.0, 0.0, eps, upstream)
+    weight = _real('weight', weight)
+    if not 0.0 <= weight <= _F32_MAX:
+        raise ValueError(f'weight must be finite and >= 0, got {weight!r}')
+    return gamma, weight, eps, upstream
+
+
+def _index(name, v):
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral):          # (NumPy's integer scalars are Integral)
+        raise ValueError(f'{name} must be an int, got {v!r}')
+    return int(v)
+
+
+def _check_selfsup(teacher, preds, origin, teacher_visible, student_visible):
+    """Shapes of the teacher, the student's predictions, the window and the masks, checked BEFORE anything moves to the device.
+    Returns ``(preds, (B, H, W), (Ht, Wt), (oy, ox))``."""
+    ts = _shape_of(teacher)
+    if len(ts) != 4 or ts[-1] != 2 or min(ts) < 1:
+        raise ValueError(f'teacher must be (B, Ht, Wt, 2), got {ts}')
+    if ts[0] * ts[1] * ts[2] * 3 >= 2 ** 31:
+        raise ValueError(f'B*Ht*Wt*3 must stay below 2^31, got {ts}')
+    preds = list(preds)
+    if not preds:
+        raise ValueError('self-supervision needs at least one student prediction')
+    if len(preds) > 64:
+        raise ValueError(f'at most 64 predictions, got {len(preds)}')
+    ps = _shape_of(preds[0])
+    if len(ps) != 4 or ps[-1] != 2 or min(ps) < 1 or ps[0] != ts[0]:
+        raise ValueError(f'prediction must be ({ts[0]}, H, W, 2), got {ps}')
+    for p in preds[1:]:
+        if _shape_of(p) != ps:
+            raise ValueError(f'prediction must be {ps}, got {_shape_of(p)}')
+    try:
+        oy, ox = origin
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f'origin must be the pair (oy, ox), got {origin!r}') from exc
+    oy, ox = _index('origin[0]', oy), _index('origin[1]', ox)
+    if oy < 0 or ox < 0 or oy + ps[1] > ts[1] or ox + ps[2] > ts[2]:
+        raise ValueError(f'the window {ps[1]} x {ps[2]} at origin ({oy}, {ox}) does not lie inside the teacher {ts[1]} x {ts[2]}')
+    if teacher_visible is not None and _shape_of(teacher_visible) != ts[:3]:
+        raise ValueError(f'teacher_visible must be {ts[:3]}, got {_shape_of(teacher_visible)}')
+    if student_visible is not None and _shape_of(student_visible) != ps[:3]:
+        raise ValueError(f'student_visible must be {ps[:3]}, got {_shape_of(student_visible)}')
+    return preds, ps[:3], ts[1:3], (oy, ox)
+
+
+def _selfsup_launch(teacher, preds, origin, teacher_visible, student_visible, gamma, weight, eps, upstream=1.0, want_grad=False,
+                    add_to=None):
+    """One raft_selfsup_loss_f32 call: ``(out, d_preds)`` -- ``out`` maps 'loss', 'selfsup', 'selfsup_used' to the elements of one
+    device buffer, d_preds is the stacked gradients ``(n, B, H, W, 2)`` or None.  ``add_to``: a 0-d float32 device tensor the
+    loss is added to on the device (``train_step``: the first pass's loss)."""
+    gamma, weight, eps, upstream = _selfsup_params(gamma, weight, eps, upstream)
+    preds, (B, H, W), (Ht, Wt), (oy, ox) = _check_selfsup(teacher, preds, origin, teacher_visible, student_visible)
+    teacher = _dev.to_device(teacher).as_subclass(torch.Tensor).to(torch.float32).contiguous()
+    tv = _mask_to_device(teacher_visible, teacher.device) if teacher_visible is not None else None
+    sv = _mask_to_device(student_visible, teacher.device) if student_visible is not None else None
+    preds = [_dev.to_device(p).as_subclass(torch.Tensor).to(torch.float32) for p in preds]
+    n, stride = len(preds), B * H * W * 2
+    stacked = _stacked(preds, stride)
+    buf = torch.empty((3,), dtype=torch.float32, device=teacher.device)
+    d_preds = torch.empty((n, B, H, W, 2), dtype=torch.float32, device=teacher.device) if want_grad else None
+    lib = _dev.lib()
+    ws = _workspace(buf.device, 8 * int(lib.raft_selfsup_loss_workspace_doubles()))
+    check(lib.raft_selfsup_loss_f32(_dev.ptr(teacher), _dev.ptr(tv) if tv is not None else None, Ht, Wt, oy, ox,
+                                    _dev.ptr(sv) if sv is not None else None, _dev.ptr(stacked), stride, n, B, H, W, gamma, weight,
+                                    eps, upstream, _dev.ptr(add_to) if add_to is not None else None, _dev.ptr(buf),
+                                    _dev.ptr(d_preds) if want_grad else None, 0, _dev.ptr(ws), _dev.stream_ptr()), 'selfsup_loss')
+    return {'loss': buf[0], 'selfsup': buf[1], 'selfsup_used': buf[2]}, d_preds
+
+
+class SelfSupervisionLoss:
+    """Self-supervision, also called self-distillation: the predictions of a *student* pass over a crop of
+    the frames are trained to reproduce the flow of the *teacher* pass over the full frames, read through the crop's window and
+    held constant: ``weight * sum_i gamma**(n-i-1) * dist_i`` with ``dist_i`` the Charbonnier distance ``sqrt(d*d + eps*eps)``
+    between prediction i and the teacher, summed over the used pixels and both components and divided by ALL ``B*H*W*2``
+    elements.  A pixel is used where ``teacher_visible`` (if given) is nonzero, ``student_visible`` (if given) is ZERO -- nonzero
+    says the student sees the pixel itself, UFlow's rule -- and the teacher's vector is finite.
+    ``weight = 0.3`` and ``eps = 0.001`` are UFlow's constants, not tuned here: nothing here was trained on real footage.
+    ``RAFT.compile(..., selfsup_crop=(cy, cx))`` makes ``train_step`` use it."""
+
+    def __init__(self, gamma=0.8, weight=0.3, eps=0.001):
+        self.gamma, self.weight, self.eps, _ = _selfsup_params(gamma, weight, eps)
+
+    def _params(self):
+        return dict(gamma=self.gamma, weight=self.weight, eps=self.eps)
+
+    def terms(self, teacher, preds, origin=(0, 0), teacher_visible=None, student_visible=None):
+        """``{'loss', 'selfsup', 'selfsup_used'}``: the weighted loss, the distance of the LAST prediction, and the share of
+        used pixels (0-d device scalars).  ``teacher`` is ``(B, Ht, Wt, 2)``, ``preds`` flows ``(B, H, W, 2)``; student pixel
+        ``(y, x)`` faces teacher pixel ``(y + origin[0], x + origin[1])``."""
+        return _photometric_terms(_selfsup_launch(teacher, preds, origin, teacher_visible, student_visible, **self._params())[0])
+
+    def __call__(self, teacher, preds, origin=(0, 0), teacher_visible=None, student_visible=None):
+        return self.terms(teacher, preds, origin, teacher_visible, student_visible)['loss']
+
+    def value_and_grad(self, teacher, preds, origin=(0, 0), teacher_visible=None, student_visible=None, upstream=1.0, _add_to=None):
+        """``(terms, grads)`` from one launch: ``terms()`` and ``grads[i] = upstream * d loss / d preds[i]``, shaped like the
+        predictions.  The teacher and both masks are constants."""
+        out, d = _selfsup_launch(teacher, preds, origin, teacher_visible, student_visible, upstream=upstream, want_grad=True,
+                                 add_to=_add_to, **self._params())
+        return _photometric_terms(out), [_dev.wrap(d[i]) for i in range(d.shape[0])]
 
 
 def _metrics(y_true, y_pred, max_flow):

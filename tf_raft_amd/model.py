@@ -691,7 +691,8 @@ class RAFT:
     # ---- evaluation plumbing (reference model.py:111-170)
     def compile(self, optimizer=None, clip_norm=None, loss=None, epe=None, trainable='all', tape_dtype='f32', bidirectional=False,
                 occlusion=True, alpha=image_ops.CONSISTENCY_ALPHA, beta=image_ops.CONSISTENCY_BETA, occlusion_test='consistency',
-                range_threshold=image_ops.RANGE_THRESHOLD, **kwargs):
+                range_threshold=image_ops.RANGE_THRESHOLD, selfsup_crop=None, selfsup_weight=0.3, selfsup_eps=0.001,
+                selfsup_mask='teacher', **kwargs):
         """reference model.py:111-124.  ``loss`` / ``epe`` default to ``tf_raft_amd.losses.sequence_loss`` /
         ``end_point_error``; ``loss=losses.PhotometricSequenceLoss(...)`` makes ``train_step`` take unlabelled pairs
         ``(image1, image2)`` or ``(image1, image2, mask)`` and report ``loss`` / ``photometric`` / ``smoothness`` (DESIGN.md
@@ -708,7 +709,17 @@ class RAFT:
         flipped between steps; the step also reports ``occluded``, the running mean of the occluded share, whether or not the
         mask is applied, and keeps its ``(2N, H, W)`` uint8 mask in ``model.last_visibility``.  ``occlusion_test='range'``
         (with ``bidirectional=True`` only) takes that mask from the range map of the same predictions instead (DESIGN.md
-        section 21; ``range_threshold`` as in ``image_ops.range_occlusion``); everything else about the step stays."""
+        section 21; ``range_threshold`` as in ``image_ops.range_occlusion``); everything else about the step stays.
+
+        ``selfsup_crop=(cy, cx)`` (with ``bidirectional=True`` only) adds self-supervision: after the pass
+        over the full frames (the teacher) the step runs the network again on the frames with ``cy`` rows and ``cx`` columns
+        removed from each side (the student), trains the student's predictions to reproduce the teacher's last flow read through
+        that window and held constant (``losses.SelfSupervisionLoss(gamma of the loss, selfsup_weight, selfsup_eps)``), and
+        applies the sum of both passes' gradients once.  ``selfsup_mask='teacher'`` uses every pixel the teacher is trusted at
+        (``last_visibility``); ``'occluded'`` is UFlow's rule: of those, the pixels that fail the student's own occlusion test
+        (its mask is kept in ``model.last_student_visibility``).  ``model.selfsup_weight`` is a plain float that may be changed
+        between steps (the recipes ramp it up after a warm-up); at 0 the second pass is skipped.  The step also reports
+        ``selfsup`` and ``selfsup_used``.  0.3 and 0.001 are UFlow's constants, not tuned here."""
         from . import losses
         if kwargs:
             raise TypeError(f'unexpected keyword arguments {sorted(kwargs)}')
@@ -726,8 +737,24 @@ class RAFT:
         self.range_threshold = image_ops.check_range_threshold(range_threshold)
         if self.occlusion_test == 'range' and not bidirectional:
             raise ValueError("occlusion_test='range' is the mask of a bidirectional step: it needs bidirectional=True")
+        if selfsup_crop is not None:
+            if not bidirectional:
+                raise ValueError('selfsup_crop: the teacher is the bidirectional step\'s pass, it needs bidirectional=True')
+            try:
+                cy, cx = selfsup_crop
+                cy, cx = losses._index('selfsup_crop[0]', cy), losses._index('selfsup_crop[1]', cx)
+            except (TypeError, ValueError) as exc:
+                raise ValueError(f'selfsup_crop must be None or a pair of ints (cy, cx), got {selfsup_crop!r}') from exc
+            if cy < 0 or cx < 0 or (cy == 0 and cx == 0):
+                raise ValueError(f'selfsup_crop must be non-negative and not (0, 0), got {selfsup_crop!r}')
+            selfsup_crop = (cy, cx)
+        if selfsup_mask not in ('teacher', 'occluded'):
+            raise ValueError(f"selfsup_mask must be 'teacher' or 'occluded', got {selfsup_mask!r}")
+        _, selfsup_weight, selfsup_eps, _ = losses._selfsup_params(0.0, selfsup_weight, selfsup_eps)
+        self.selfsup_crop, self.selfsup_weight, self.selfsup_eps, self.selfsup_mask = selfsup_crop, selfsup_weight, selfsup_eps, selfsup_mask
         self.bidirectional, self.occlusion = bool(bidirectional), bool(occlusion)
         self.last_visibility = None
+        self.last_student_visibility = None
         self.optimizer = optimizer
         self.clip_norm = clip_norm
         self.loss = loss if loss is not None else losses.sequence_loss
@@ -740,9 +767,11 @@ class RAFT:
             self.flow_metrics.update((k, losses.Mean(name=k)) for k in self._unlabelled_keys()[1:])
 
     def _unlabelled_keys(self):
-        """What ``train_step`` reports under a PhotometricSequenceLoss (``occluded``: in bidirectional mode)."""
+        """What ``train_step`` reports under a PhotometricSequenceLoss (``occluded``: in bidirectional mode; ``selfsup`` and
+        ``selfsup_used``: with ``selfsup_crop``)."""
         on = [k for k in ('census', 'ssim') if getattr(self.loss, k + '_weight', 0.0) > 0]
-        return ('loss', 'photometric', *on, 'smoothness') + (('occluded',) if getattr(self, 'bidirectional', False) else ())
+        return (('loss', 'photometric', *on, 'smoothness') + (('occluded',) if getattr(self, 'bidirectional', False) else ())
+                + (('selfsup', 'selfsup_used') if getattr(self, 'selfsup_crop', None) is not None else ()))
 
     BN_MOMENTUM = 0.99      # Keras BatchNormalization default (extractor.py:10 passes none)
 
@@ -758,7 +787,11 @@ class RAFT:
         After ``compile(..., bidirectional=True)`` the step runs the doubled batch ``[image1 | image2]``
         against ``[image2 | image1]`` with the feature encoder once per frame, and the mask of the loss comes from one
         ``raft_flow_visibility_f32`` launch on its own last prediction (``occlusion_test='range'``:
-        ``raft_flow_range_visibility_f32``)."""
+        ``raft_flow_range_visibility_f32``).
+        After ``compile(..., selfsup_crop=(cy, cx))`` a second graded pass follows on the centre crops of the
+        frames, its loss ``raft_selfsup_loss_f32`` against the first pass's last prediction; the two passes' gradients are added
+        and applied once, and the batch-norm moving statistics are updated with each pass's batch statistics in turn.  The
+        forward and backward of one pass is ``_graded_pass``, whatever the loss."""
         from . import grad, losses
         if not hasattr(self, 'flow_metrics'):
             raise RuntimeError('call compile() before train_step()')
@@ -769,6 +802,14 @@ class RAFT:
         bidirectional = photometric and self.bidirectional
         if bidirectional:                           # arity and shapes, before anything is enqueued
             pair_masks = losses._check_bidirectional(data)
+            crop = self.selfsup_crop
+            if crop is not None:
+                _, Hf, Wf, _ = losses._shape_of(data[0])
+                Hs, Ws = Hf - 2 * crop[0], Wf - 2 * crop[1]
+                if Hs % 8 or Ws % 8 or Hs < self.MIN_SIDE or Ws < self.MIN_SIDE:
+                    raise ValueError(f'selfsup_crop={crop} leaves a student of {Hs} x {Ws} from frames of {Hf} x {Wf}: both sides must be '
+                                     f'multiples of 8 and at least {self.MIN_SIDE}')
+                weight2 = losses._selfsup_params(0.0, self.selfsup_weight, self.selfsup_eps)[1]   # (it may have been changed since compile)
         elif photometric and len(data) not in (2, 3):
             raise ValueError(f'train_step with PhotometricSequenceLoss expects (image1, image2) or (image1, image2, mask), '
                              f'got {len(data)} items')
@@ -802,7 +843,6 @@ class RAFT:
         B, H, W, _ = image1.shape
         if H % 8 or W % 8:
             raise ValueError(f'H and W must be multiples of 8 (got {H}x{W})')
-        h, w = H // 8, W // 8
         full = self.trainable == 'all'
         # Master copies of EVERY weight (and the batch-norm moving statistics) live on the device from the first step on and
         # are updated in place; grad.* packs them for the convolution kernels on the device too.  Nothing of a step crosses
@@ -812,6 +852,120 @@ class RAFT:
                         for k, v in self._weights.items()}
         wts = self._dw
         grad.clear_pack_cache()                     # packed copies of last step's weights
+        drop_seed = None
+        if full and self.drop_rate:
+            # mask seeds: a different stream per data-parallel rank (ranks see different shards), per model seed and per
+            # optimizer step.  save_weights / load_weights persist the WEIGHTS only (as the reference's
+            # ModelCheckpoint(save_weights_only=True) does, train_sintel.py:104-107): a caller that resumes a run must restore
+            # optimizer.iterations itself, otherwise the mask sequence (and the LR schedule) restarts at step 1
+            step = int(getattr(getattr(self, 'optimizer', None), 'iterations', 0) or 0)
+            self._drop_step = max(getattr(self, '_drop_step', 0) + 1, step + 1)
+            drop_seed = _dropout_seed(getattr(self, 'seed', 0), _rank_of_this_process(), self._drop_step)
+
+        def first_loss(preds):
+            """The loss of the first (or only) pass and its gradient: ``(d_preds, (terms or loss, last prediction, mask))``."""
+            visible = None
+            if bidirectional:
+                # the mask of the loss from THIS forward pass's last prediction: a constant of the gradient.  Without occlusion
+                # and without user masks it is all ones and the loss kernels' "no mask" specialisation runs.
+                last = preds[-1].as_subclass(torch.Tensor).contiguous()
+                if self.occlusion_test == 'range':
+                    visible, occluded = image_ops.range_visibility_launch(last, pairs, user_mask, self.range_threshold, apply=self.occlusion)
+                else:
+                    visible, occluded = image_ops.flow_visibility_launch(last, pairs, user_mask, *self.consistency, apply=self.occlusion)
+                self.last_visibility = _dev.wrap(visible)
+                truth = (image1, image2, visible) if (self.occlusion or user_mask is not None) else (image1, image2)
+            if photometric:                         # value and gradient share the gathers: one launch per term
+                terms, d_preds = self.loss.value_and_grad(truth if bidirectional else y_true, preds)
+                if bidirectional:
+                    terms = dict(terms, occluded=_dev.wrap(occluded))
+                return d_preds, (terms, preds[-1], visible)
+            loss = self.loss([flow, valid], preds)
+            return grad.sequence_loss_grad((flow, valid), preds), (loss, preds[-1], None)
+
+        def flat(grads):
+            return {k: grads[k].as_subclass(torch.Tensor).reshape(wts[k].shape).contiguous() for k in sorted(grads)}
+
+        # the first pass's tape and all but its last prediction die with the call, before a second pass allocates
+        grads, stats, (terms, last_pred, visible1) = self._graded_pass(wts, image1, image2, pairs if bidirectional else None, drop_seed,
+                                                                       first_loss)
+        gt, all_stats = flat(grads), [stats]
+        if bidirectional and crop is not None:
+            self.last_student_visibility = None
+        if bidirectional and crop is not None and weight2 > 0.0:
+            # DESIGN.md section 22: the student pass on the centre crops [c1 | c2] against [c2 | c1]; the teacher is the first
+            # pass's last prediction, read through the window and held constant
+            Hs, Ws = H - 2 * crop[0], W - 2 * crop[1]
+            crop1, crop2 = image_ops.window_copy(image1.contiguous(), Hs, Ws), image_ops.window_copy(image2.contiguous(), Hs, Ws)
+            teacher = last_pred.as_subclass(torch.Tensor).contiguous()
+
+            def student_loss(preds):
+                student_visible = None
+                if self.selfsup_mask == 'occluded':     # UFlow's rule: only where the student fails its own occlusion test
+                    last = preds[-1].as_subclass(torch.Tensor).contiguous()
+                    if self.occlusion_test == 'range':
+                        student_visible, _ = image_ops.range_visibility_launch(last, pairs, None, self.range_threshold, apply=True)
+                    else:
+                        student_visible, _ = image_ops.flow_visibility_launch(last, pairs, None, *self.consistency, apply=True)
+                    self.last_student_visibility = _dev.wrap(student_visible)
+                selfsup = losses.SelfSupervisionLoss(self.loss.gamma, weight2, self.selfsup_eps)
+                terms2, d_preds = selfsup.value_and_grad(teacher, preds, crop, visible1, student_visible,
+                                                         _add_to=terms['loss'].as_subclass(torch.Tensor))
+                return d_preds, terms2
+
+            grads2, stats2, terms2 = self._graded_pass(wts, crop1, crop2, pairs, None if drop_seed is None else drop_seed + 2, student_loss)
+            gt = grad.add_gradients(gt, flat(grads2))               # g1 + g2, one float32 addition per element
+            all_stats.append(stats2)
+            terms = dict(terms, **terms2)                           # ('loss': the first pass's plus the weighted term)
+        names = sorted(gt)
+        self._train_vars = {k: wts[k] for k in names}          # views of the device master copies (updated in place)
+        from .parallel import all_reduce_gradients, all_reduce_mean_
+        all_reduce_gradients(gt)                    # data-parallel training: one bucketed RCCL all-reduce (no-op on one rank)
+        self.optimizer.apply_gradients(gt, self._train_vars, clip_norm=self.clip_norm)
+        # Keras BatchNormalization moving statistics (momentum 0.99), in place on the device.  TF 2.3's fused kernel feeds the
+        # moving variance with the UNBIASED batch variance; that detail cannot be checked here (no TensorFlow) and is stated in
+        # DESIGN.md.  Data-parallel: the batch statistics are averaged over the ranks first (one small all-reduce), so that
+        # every rank keeps the same moving statistics and a checkpoint does not depend on which rank writes it.
+        # A step with a student pass updates them twice, with the first pass's statistics and then the second's: what two
+        # training-mode calls inside one Keras train_step do.
+        for stats in all_stats:
+            if not stats:
+                continue
+            order = sorted(stats)
+            all_reduce_mean_([t for name in order for t in (stats[name][0], stats[name][1])])
+            for name in order:
+                mean, var, cnt = stats[name]
+                mm, mv = wts[f'{name}/moving_mean'], wts[f'{name}/moving_variance']
+                mm.copy_(grad._axpby(self.BN_MOMENTUM, mm, 1.0 - self.BN_MOMENTUM, mean.contiguous()))
+                mv.copy_(grad._axpby(self.BN_MOMENTUM, mv, (1.0 - self.BN_MOMENTUM) * cnt / max(cnt - 1.0, 1.0), var.contiguous()))
+        if any(all_stats):
+            grad.bump_pack_version()                     # parameters written outside the optimizer: packed copies are stale
+        # the NumPy dictionary and the inference kernels' re-packed (Winograd-transformed, N-fused) copies are refreshed
+        # lazily: by get_weights_dict / save_weights, and by the next forward call
+        self._host_stale = True
+        self._inference_stale = True
+        if photometric:
+            for k in self._unlabelled_keys():
+                if k in terms:                      # ('selfsup' / 'selfsup_used': only by a step that ran the student pass)
+                    self.flow_metrics[k].update_state(terms[k])
+            return {k: self.flow_metrics[k].result() for k in self._unlabelled_keys()}
+        info = self.epe([flow, valid], last_pred)
+        self.flow_metrics['loss'].update_state(terms)
+        for k in ('epe', 'u1', 'u3', 'u5'):
+            self.flow_metrics[k].update_state(info[k])
+        return {k: m.result() for k, m in self.flow_metrics.items()}
+
+    def _graded_pass(self, wts, image1, image2, pairs, drop_seed, loss_of):
+        """Forward and backward of one pass of ``train_step`` over ``(B, H, W, 3)`` float32 device frames: the encoders, the
+        volume, the loop, ``loss_of(preds) -> (d_preds, result)``, and back to the gradient of every trained tensor.  ``pairs``:
+        None, or N of a bidirectional pass whose frames are the doubled batch (the feature encoder then runs once per frame).
+        ``drop_seed``: the seed of the first of the pass's two dropout masks.  Returns ``(grads, batch-norm statistics, result)``;
+        the tape and the predictions ``loss_of`` did not keep are released on return."""
+        from . import grad
+        bidirectional = pairs is not None
+        B, H, W, _ = image1.shape
+        h, w = H // 8, W // 8
+        full = self.trainable == 'all'
         drop_masks = []
         if full:
             ones = torch.ones_like(image1)
@@ -825,15 +979,8 @@ class RAFT:
             cnet, ctape = grad.encoder_forward(wts, 'cnet', x1, training=True)         # model.py:82
             cnet = cnet.as_subclass(torch.Tensor)
             if self.drop_rate:     # extractor.py:109-111, 127-128: Dropout on the encoder outputs while training
-                # mask seeds: a different stream per data-parallel rank (ranks see different shards), per model seed and per
-                # optimizer step.  save_weights / load_weights persist the WEIGHTS only (as the reference's
-                # ModelCheckpoint(save_weights_only=True) does, train_sintel.py:104-107): a caller that resumes a run must restore
-                # optimizer.iterations itself, otherwise the mask sequence (and the LR schedule) restarts at step 1
-                step = int(getattr(getattr(self, 'optimizer', None), 'iterations', 0) or 0)
-                self._drop_step = max(getattr(self, '_drop_step', 0) + 1, step + 1)
-                base = _dropout_seed(getattr(self, 'seed', 0), _rank_of_this_process(), self._drop_step)
-                fout, mf = grad.dropout_forward(fout, self.drop_rate, seed=base)
-                cnet, mc = grad.dropout_forward(cnet, self.drop_rate, seed=base + 1)
+                fout, mf = grad.dropout_forward(fout, self.drop_rate, seed=drop_seed)
+                cnet, mc = grad.dropout_forward(cnet, self.drop_rate, seed=drop_seed + 1)
                 drop_masks = [mf, mc]
             fmap1, fmap2 = grad.mirror_feature_maps(fout, pairs) if bidirectional else (fout[:B].contiguous(), fout[B:].contiguous())
         else:
@@ -855,23 +1002,7 @@ class RAFT:
         prefix = 'update_block'
         ub = {k: v for k, v in wts.items() if k.startswith(prefix)}
         preds, tape = grad.loop_forward(ub, correlation, net0, inp, self.iters, prefix, self.variant, tape_dtype=self.tape_dtype)
-        if bidirectional:
-            # the mask of the loss from THIS forward pass's last prediction: a constant of the gradient.  Without occlusion
-            # and without user masks it is all ones and the loss kernels' "no mask" specialisation runs.
-            last = preds[-1].as_subclass(torch.Tensor).contiguous()
-            if self.occlusion_test == 'range':
-                visible, occluded = image_ops.range_visibility_launch(last, pairs, user_mask, self.range_threshold, apply=self.occlusion)
-            else:
-                visible, occluded = image_ops.flow_visibility_launch(last, pairs, user_mask, *self.consistency, apply=self.occlusion)
-            self.last_visibility = _dev.wrap(visible)
-            y_true = (image1, image2, visible) if (self.occlusion or user_mask is not None) else (image1, image2)
-        if photometric:                             # value and gradient share the gathers: one launch per term
-            terms, d_preds = self.loss.value_and_grad(y_true, preds)
-            if bidirectional:
-                terms = dict(terms, occluded=_dev.wrap(occluded))
-        else:
-            loss = self.loss([flow, valid], preds)
-            d_preds = grad.sequence_loss_grad((flow, valid), preds)
+        d_preds, result = loss_of(preds)
         d_net0, d_inp, d_pyr, grads = grad.loop_backward(ub, correlation, tape, d_preds, prefix)
         stats = {}
         if full:
@@ -889,38 +1020,7 @@ class RAFT:
             grads = dict(grads)
             grads.update(gf)
             grads.update(gc)
-        names = sorted(grads)
-        self._train_vars = {k: wts[k] for k in names}          # views of the device master copies (updated in place)
-        gt = {k: grads[k].as_subclass(torch.Tensor).reshape(wts[k].shape).contiguous() for k in names}
-        from .parallel import all_reduce_gradients, all_reduce_mean_
-        all_reduce_gradients(gt)                    # data-parallel training: one bucketed RCCL all-reduce (no-op on one rank)
-        self.optimizer.apply_gradients(gt, self._train_vars, clip_norm=self.clip_norm)
-        # Keras BatchNormalization moving statistics (momentum 0.99), in place on the device.  TF 2.3's fused kernel feeds the
-        # moving variance with the UNBIASED batch variance; that detail cannot be checked here (no TensorFlow) and is stated in
-        # DESIGN.md.  Data-parallel: the batch statistics are averaged over the ranks first (one small all-reduce), so that
-        # every rank keeps the same moving statistics and a checkpoint does not depend on which rank writes it.
-        if stats:
-            order = sorted(stats)
-            all_reduce_mean_([t for name in order for t in (stats[name][0], stats[name][1])])
-            for name in order:
-                mean, var, cnt = stats[name]
-                mm, mv = wts[f'{name}/moving_mean'], wts[f'{name}/moving_variance']
-                mm.copy_(grad._axpby(self.BN_MOMENTUM, mm, 1.0 - self.BN_MOMENTUM, mean.contiguous()))
-                mv.copy_(grad._axpby(self.BN_MOMENTUM, mv, (1.0 - self.BN_MOMENTUM) * cnt / max(cnt - 1.0, 1.0), var.contiguous()))
-            grad.bump_pack_version()                     # parameters written outside the optimizer: packed copies are stale
-        # the NumPy dictionary and the inference kernels' re-packed (Winograd-transformed, N-fused) copies are refreshed
-        # lazily: by get_weights_dict / save_weights, and by the next forward call
-        self._host_stale = True
-        self._inference_stale = True
-        if photometric:
-            for k in self._unlabelled_keys():
-                self.flow_metrics[k].update_state(terms[k])
-            return {k: self.flow_metrics[k].result() for k in self._unlabelled_keys()}
-        info = self.epe([flow, valid], preds[-1])
-        self.flow_metrics['loss'].update_state(loss)
-        for k in ('epe', 'u1', 'u3', 'u5'):
-            self.flow_metrics[k].update_state(info[k])
-        return {k: m.result() for k, m in self.flow_metrics.items()}
+        return grads, stats, result
 
     def test_step(self, data):
         """reference model.py:146-158: forward prediction, then EPE / u1 / u3 / u5 of ``flow_predictions[-1]`` against
