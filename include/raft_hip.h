@@ -814,6 +814,44 @@ int raft_selfsup_loss_f32(const float *teacher, const uint8_t *teacher_visible, 
                           int W, double gamma, float weight, float eps, float upstream, const float *add_to, float *out3,
                           float *d_preds, int accumulate, double *workspace, void *stream);
 
+/* The student's view (csrc/student_view.hip): the frames of a self-supervised step, and the teacher's flow
+ * with its trust mask, seen through one affine map per slice.  The record of slice b maps the student's pixel indices q = (x, y)
+ * to the teacher's, p = M q + o:
+ *     px = (m[0] * float(x) + m[1] * float(y)) + o[0],     py = (m[2] * float(x) + m[3] * float(y)) + o[1]
+ * every operation rounded on its own.  The student pixel is IN FRAME iff 0 <= px <= Wt - 1 and 0 <= py <= Ht - 1 (a NaN fails), and
+ * a map is sampled at (px, py) by the bilinear rule of raft_warp_f32 above.  The host inverts M in double and rounds each
+ * element of both once (tf_raft_amd/augment.py). */
+typedef struct {
+    float m[4];              /* M, row-major: student index -> teacher position */
+    float o[2];              /* o = (ox, oy) */
+    float inv[4];            /* M^-1, row-major: a teacher vector seen by the student */
+    float gain[3], bias[3];  /* per channel (channels beyond the third take the third's), read when colour != 0 */
+    int32_t colour;          /* nonzero: v -> min(max(v * gain + bias, 0), 255) */
+} RaftViewParams;
+
+/* sizeof(RaftViewParams): the binding checks its mirror against it.  Host-only. */
+int raft_view_params_bytes(void);
+
+/*   raft_view_frames_f32: dst[b, y, x, c] = src[b, :, :, c] sampled at the pixel's position, 0.0f in every channel of a pixel out
+ *     of frame; then, where the record's colour != 0, min(max(v * gain[c] + bias[c], 0), 255) as two rounded operations and the
+ *     clamp (out-of-frame pixels included); with colour == 0 the value is stored as sampled.  src (B, Ht, Wt, C), dst (B, H, W, C).
+ *   raft_view_flow_f32: with f = (u, v) the flow (B, Ht, Wt, 2) sampled at the pixel's position,
+ *         target[b, y, x] = (inv[0] * u + inv[1] * v, inv[2] * u + inv[3] * v)
+ *     (a point the student sees at q lies at p, moves to p + f and is seen at q + M^-1 f).  A tap's weight is the product of its
+ *     factors (1 - a or a, 1 - b or b); a tap of weight exactly zero (the x1 side with a == 0, the y1 side with b == 0) counts as
+ *     0 and its trust is not asked.  target_visible[b, y, x] (uint8, (B, H, W)) = 1 iff the pixel is in frame, every tap of
+ *     nonzero weight has teacher_visible != 0 (uint8 (B, Ht, Wt); NULL = all ones) and both components of the target are finite;
+ *     where it is 0 the target is (0, 0).  Under M = I with an integer o both entries copy the window at o.
+ * params: B records in DEVICE memory.  The student may be larger than the teacher.  One launch on `stream` each, no atomics, no
+ * memset, every output element written exactly once; tap indices are clamped into the teacher whatever a record holds.
+ * Errors, in this order: RAFT_E_NULL for a NULL src / flow, params, dst / target or target_visible; RAFT_E_SHAPE for a
+ * non-positive size, B * Ht * Wt * C or B * H * W * C (C = 2 for the flow) of 2^31 elements or more, or H above 8 * 65535;
+ * RAFT_E_ALIGN for a flow or target that is not 8-byte aligned (read and written as float2).  All checks precede the launch. */
+int raft_view_frames_f32(const float *src, const RaftViewParams *params, float *dst, int B, int Ht, int Wt, int H, int W, int C,
+                         void *stream);
+int raft_view_flow_f32(const float *flow, const uint8_t *teacher_visible, const RaftViewParams *params, float *target,
+                       uint8_t *target_visible, int B, int Ht, int Wt, int H, int W, void *stream);
+
 /* Backward of raft_corr_lookup_f32 (CorrBlock.retrieve + bilinear_sampler, corr.py:116-152, 28-69), with TensorFlow's
  * gradient conventions: floor / ceil contribute nothing, clip_by_value passes the gradient on [0, size - 1].
  * d_out: (B, h, w, ld_out) upstream gradient of the lookup output (first levels*(2r+1)^2 channels used).

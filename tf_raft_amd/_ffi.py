@@ -88,12 +88,18 @@ class AugmentParams(C.Structure):
                 ('rect', (C.c_int32 * 4) * 2)]
 
 
+class ViewParams(C.Structure):
+    """``RaftViewParams``: one slice's student view (tf_raft_amd/augment.py ``StudentView``; include/raft_hip.h has the field notes)."""
+    _fields_ = [('m', C.c_float * 4), ('o', C.c_float * 2), ('inv', C.c_float * 4), ('gain', C.c_float * 3), ('bias', C.c_float * 3),
+                ('colour', C.c_int32)]
+
+
 AUGMENT_SUM_BLOCKS = _CONSTANTS['RAFT_AUGMENT_SUM_BLOCKS']
 
 _SCALARS = {'int': C.c_int, 'float': C.c_float, 'double': C.c_double, 'int64_t': C.c_int64, 'uint64_t': C.c_uint64,
             'uint32_t': C.c_uint32, 'size_t': C.c_size_t}
-# Structs that cross the ABI by value or as HOST pointers.  RaftAugmentParams is absent on purpose: its records lie in device
-# memory, so a pointer to them travels as void* like every other device pointer.
+# Structs that cross the ABI by value or as HOST pointers.  RaftAugmentParams and RaftViewParams are absent on purpose: their
+# records lie in device memory, so a pointer to them travels as void* like every other device pointer.
 _STRUCTS = {'raft_conv_weights': ConvWeights, 'raft_basic_update_weights': BasicUpdateWeights,
             'raft_small_update_weights': SmallUpdateWeights, 'raft_encoder_weights': EncoderWeights, 'raft_state': State,
             'RaftTileOrigins': TileOrigins}
@@ -199,6 +205,8 @@ def load_library():
             fn.argtypes = args
         if lib.raft_augment_params_bytes() != C.sizeof(AugmentParams):
             raise RuntimeError(f'{path}: RaftAugmentParams is {lib.raft_augment_params_bytes()} bytes, its mirror {C.sizeof(AugmentParams)}')
+        if lib.raft_view_params_bytes() != C.sizeof(ViewParams):
+            raise RuntimeError(f'{path}: RaftViewParams is {lib.raft_view_params_bytes()} bytes, its mirror {C.sizeof(ViewParams)}')
         if lib.raft_version() != ABI_VERSION:
             raise RuntimeError(f'{path} reports ABI {lib.raft_version()}, this binding mirrors ABI {ABI_VERSION}: '
                                'rebuild the library (python -m tf_raft_amd.build --force)')

@@ -13,6 +13,9 @@ The sparse augmentor shares the host code and the frame path; its flow resize, a
 
 The colour-jitter parameters are ``albumentations``' own draws in the reference and do not come from ``np.random``; here they
 come from a second generator, ``photo_rng``, by the protocol of ``draw_photo`` -- the first sequence stays aligned.
+
+``StudentView`` / ``StudentTransform`` are not the reference's: they describe and draw the affine view the student pass of a
+self-supervised step sees (the gathers are ``image_ops.view_frames`` / ``view_flow``).
 """
 from __future__ import annotations
 
@@ -22,10 +25,10 @@ import numpy as np
 import torch
 
 from . import _dev
-from ._ffi import AUGMENT_SUM_BLOCKS, AugmentParams, check
+from ._ffi import AUGMENT_SUM_BLOCKS, AugmentParams, ViewParams, check
 from .image_ops import _on_device
 
-__all__ = ['FlowAugmentor', 'SparseFlowAugmentor', 'PhotoAug', 'draw_photo']
+__all__ = ['FlowAugmentor', 'SparseFlowAugmentor', 'PhotoAug', 'draw_photo', 'StudentView', 'StudentTransform']
 
 
 class PhotoAug:
@@ -391,3 +394,156 @@ class SparseFlowAugmentor(_Augmentor):
 
     def __call__(self, img1, img2, flow, valid):
         return self.batch(img1, img2, flow, valid)
+
+
+# ---------------------------------------------------------------- the student's view of a self-supervised step
+class StudentView:
+    """N affine views, one per pair: ``theta`` ``(N, 2, 3)`` float64 holds ``[M | o]``, the map from the student's pixel indices
+    ``q = (x, y)`` to the teacher's, ``p = M q + o``.  ``gain`` / ``bias``: None (the frames are stored as sampled), or ``(N, 2,
+    3)`` float64 -- index 0 is frame 1, index 1 frame 2, then the channel -- for ``clip(v * gain + bias, 0, 255)``.  Everything
+    is held in float64; ``records`` inverts ``M`` in float64 and rounds each number once to float32 for the device."""
+
+    def __init__(self, theta, gain=None, bias=None):
+        theta = np.array(theta, dtype=np.float64)
+        if theta.ndim != 3 or theta.shape[1:] != (2, 3) or theta.shape[0] < 1:
+            raise ValueError(f'theta must be (N, 2, 3), got {theta.shape}')
+        if not np.isfinite(theta).all():
+            raise ValueError('theta must be finite')
+        det = theta[:, 0, 0] * theta[:, 1, 1] - theta[:, 0, 1] * theta[:, 1, 0]
+        if not (np.abs(det) > 0).all():
+            raise ValueError(f'every view needs an invertible M, got determinants {det}')
+        if (gain is None) != (bias is None):
+            raise ValueError('gain and bias come together')
+        if gain is not None:
+            gain, bias = np.array(gain, dtype=np.float64), np.array(bias, dtype=np.float64)
+            want = (theta.shape[0], 2, 3)
+            if gain.shape != want or bias.shape != want or not (np.isfinite(gain).all() and np.isfinite(bias).all()):
+                raise ValueError(f'gain and bias must be finite arrays {want}, got {gain.shape} / {bias.shape}')
+        self.theta, self.gain, self.bias = theta, gain, bias
+
+    def __len__(self):
+        return self.theta.shape[0]
+
+    def __repr__(self):
+        return f'StudentView(N={len(self)}, colour={self.gain is not None})'
+
+    @classmethod
+    def identity(cls, N, crop):
+        """The view of section 22's centre crop: ``M = I``, ``o = (cx, cy)`` for ``crop = (cy, cx)``, no colour change.  Both
+        gathers are then exact copies through the window."""
+        cy, cx = crop
+        theta = np.tile(np.array([[1.0, 0.0, float(cx)], [0.0, 1.0, float(cy)]]), (int(N), 1, 1))
+        return cls(theta)
+
+    def matrix(self):
+        """``M``, ``(N, 2, 2)`` float64."""
+        return self.theta[:, :, :2].copy()
+
+    def inverse(self):
+        """``M^-1`` in float64, ``(N, 2, 2)``: a teacher vector ``f`` is seen by the student as ``M^-1 f``."""
+        return np.linalg.inv(self.theta[:, :, :2])
+
+    def records(self, doubled=False):
+        """The ``RaftViewParams`` records (a ctypes array on the host), each number rounded once to float32: ``N`` records with frame
+        1's colour, or (``doubled``) the ``2N`` of a training step's doubled batch -- record ``n`` is view ``n`` with frame 1's
+        colour, record ``n + N`` the same view with frame 2's."""
+        N = len(self)
+        with np.errstate(over='ignore'):            # (a number float32 cannot hold becomes infinite: image_ops refuses the record)
+            m, o, inv = (a.astype(np.float32) for a in (self.theta[:, :, :2].reshape(N, 4), self.theta[:, :, 2], self.inverse().reshape(N, 4)))
+            gain, bias = (None, None) if self.gain is None else (self.gain.astype(np.float32), self.bias.astype(np.float32))
+        recs = (ViewParams * (2 * N if doubled else N))()
+        for k, r in enumerate(recs):
+            n, frame = k % N, k // N
+            r.m[:], r.o[:], r.inv[:] = m[n].tolist(), o[n].tolist(), inv[n].tolist()
+            if gain is not None:
+                r.gain[:], r.bias[:] = gain[n, frame].tolist(), bias[n, frame].tolist()
+                r.colour = 1
+            else:
+                r.gain[:], r.bias[:], r.colour = [1.0] * 3, [0.0] * 3, 0
+        return recs
+
+
+def _range(name, v, lowest=None):
+    try:
+        lo, hi = (float(x) for x in v)
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f'{name} must be a pair (low, high), got {v!r}') from exc
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi) or (lowest is not None and not lo > lowest):
+        raise ValueError(f'{name} must be a finite pair low <= high{"" if lowest is None else f" above {lowest:g}"}, got {v!r}')
+    return lo, hi
+
+
+class StudentTransform:
+    """Draws the ``StudentView`` of a step: ``M = (1 / s) R(angle) diag(+-1, +-1)`` about the frames' centres,
+    ``p - c_t - shift = M (q - c_s)`` with ``c = ((W - 1) / 2, (H - 1) / 2)`` and ``R(t) = [[cos t, -sin t], [sin t, cos t]]``.
+
+    ``flip_x`` / ``flip_y``: the probabilities of the two mirrors; ``zoom = (low, high)``: ``s`` uniform in it (``s > 1`` shows the
+    student a magnified, smaller part of the scene); ``rotate``: the angle uniform in ``[-rotate, rotate]`` degrees; ``translate``:
+    a transformed view is shifted uniformly within the slack that keeps the student's four corners inside the teacher, per axis
+    (an axis without slack stays centred; what then falls outside is zero-filled and unused).  ``gain`` / ``bias``: ranges of one
+    gain and one bias per frame for ``clip(v * gain + bias, 0, 255)``, the same for the three channels; with probability
+    ``asymmetric`` frame 2 draws its own pair, else it shares frame 1's.
+
+    The draws of one sample, in this order, from ``rng`` (a ``np.random.RandomState``; None: the global ``np.random``, as
+    ``FlowAugmentor``): ``rand()`` flip_x, ``rand()`` flip_y, ``uniform(*zoom)``, ``uniform(-rotate, rotate)``; if ``translate`` and
+    the transform can change the geometry at all (a flip probability, a zoom range other than (1, 1) or ``rotate`` is set):
+    ``rand()`` for the shift along x and ``rand()`` along y; if the ranges can change a colour at all (``gain != (1, 1)`` or
+    ``bias != (0, 0)``): ``uniform(*gain)``, ``uniform(*bias)``, ``rand()`` asymmetric, and if that fires ``uniform(*gain)``,
+    ``uniform(*bias)`` for frame 2.  A batch is drawn sample after sample.
+
+    The defaults change nothing: the default object draws ``StudentView.identity`` -- the centre crop of DESIGN.md section 22 --
+    which is why a transform that cannot change the geometry draws no shift either.  Every default and range is a choice, not a
+    tuned value; nothing here was trained on real footage."""
+
+    def __init__(self, flip_x=0.0, flip_y=0.0, zoom=(1.0, 1.0), rotate=0.0, translate=True, gain=(1.0, 1.0), bias=(0.0, 0.0),
+                 asymmetric=0.0, rng=None):
+        for name, v in (('flip_x', flip_x), ('flip_y', flip_y), ('asymmetric', asymmetric)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
+                raise ValueError(f'{name} must be a probability in [0, 1], got {v!r}')
+        if isinstance(rotate, (bool, np.bool_)) or not isinstance(rotate, (int, float, np.integer, np.floating)) \
+                or not 0.0 <= float(rotate) <= 180.0:
+            raise ValueError(f'rotate must be an angle in [0, 180] degrees, got {rotate!r}')
+        if not isinstance(translate, (bool, np.bool_)):
+            raise ValueError(f'translate must be True or False, got {translate!r}')
+        self.flip_x, self.flip_y, self.asymmetric, self.rotate = float(flip_x), float(flip_y), float(asymmetric), float(rotate)
+        self.zoom, self.gain, self.bias = _range('zoom', zoom, lowest=0.0), _range('gain', gain), _range('bias', bias)
+        self.translate, self.rng = bool(translate), rng
+
+    @property
+    def spatial(self):
+        """Whether a draw can differ from the centre crop's geometry."""
+        return self.flip_x > 0 or self.flip_y > 0 or self.zoom != (1.0, 1.0) or self.rotate > 0
+
+    @property
+    def colour(self):
+        return self.gain != (1.0, 1.0) or self.bias != (0.0, 0.0)
+
+    def draw(self, N, frame_size, student_size):
+        """The views of ``N`` pairs of ``frame_size = (H, W)`` frames for a student of ``student_size = (Hs, Ws)``; touches no
+        device."""
+        (H, W), (Hs, Ws), N = (int(v) for v in frame_size), (int(v) for v in student_size), int(N)
+        if N < 1 or min(H, W, Hs, Ws) < 1:
+            raise ValueError(f'N and the sizes must be >= 1, got {N}, {frame_size}, {student_size}')
+        rng = self.rng if self.rng is not None else np.random
+        ct, cs = np.array([(W - 1) / 2.0, (H - 1) / 2.0]), np.array([(Ws - 1) / 2.0, (Hs - 1) / 2.0])
+        theta = np.zeros((N, 2, 3))
+        gain, bias = (np.ones((N, 2, 3)), np.zeros((N, 2, 3))) if self.colour else (None, None)
+        for n in range(N):
+            fx = -1.0 if rng.rand() < self.flip_x else 1.0
+            fy = -1.0 if rng.rand() < self.flip_y else 1.0
+            s = rng.uniform(*self.zoom)
+            angle = np.deg2rad(rng.uniform(-self.rotate, self.rotate))
+            c, sn = (1.0, 0.0) if angle == 0.0 else (np.cos(angle), np.sin(angle))
+            M = np.array([[c * fx, -sn * fy], [sn * fx, c * fy]]) / s + 0.0       # (+ 0.0: no negative zeros)
+            shift = np.zeros(2)
+            if self.translate and self.spatial:
+                reach = np.abs(M) @ cs                                    # how far from its centre the student's corners land
+                slack = np.maximum(ct - reach, 0.0)
+                shift = (2.0 * np.array([rng.rand(), rng.rand()]) - 1.0) * slack
+            theta[n, :, :2] = M
+            theta[n, :, 2] = ct + shift - M @ cs
+            if self.colour:
+                g1, b1 = rng.uniform(*self.gain), rng.uniform(*self.bias)
+                g2, b2 = (rng.uniform(*self.gain), rng.uniform(*self.bias)) if rng.rand() < self.asymmetric else (g1, b1)
+                gain[n, 0], bias[n, 0], gain[n, 1], bias[n, 1] = g1, b1, g2, b2
+        return StudentView(theta, gain, bias)

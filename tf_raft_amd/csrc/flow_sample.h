@@ -1,5 +1,6 @@
 // The one definition of "the sample of a map under a flow vector" (DESIGN.md sections 15 and 17), shared by flow_check.hip (warp,
-// forward-backward consistency) and photometric_loss.hip (the self-supervised loss and its gradient).
+// forward-backward consistency), photometric_loss.hip (the self-supervised loss and its gradient) and student_view.hip (the same
+// sample at a position that an affine map gives).
 //
 // For the pixel at integer (x, y) with vector (u, v): sx = float(x) + u and sy = float(y) + v, ONE float32 addition each; the
 // pixel is in frame iff 0 <= sx <= W - 1 and 0 <= sy <= H - 1 (a NaN fails); x0 = floor(sx), x1 = min(x0 + 1, W - 1),
@@ -20,9 +21,9 @@ struct Taps {
     bool in;
 };
 
-__device__ __forceinline__ Taps flow_taps(int x, int y, float2 f, int H, int W) {
+// the taps of the sample position (sx, sy) itself (student_view.hip arrives at it by an affine map, not by a flow vector)
+__device__ __forceinline__ Taps sample_taps(float sx, float sy, int H, int W) {
 #pragma clang fp contract(off)
-    const float sx = (float)x + f.x, sy = (float)y + f.y;
     Taps t;
     t.in = sx >= 0.f && sx <= (float)(W - 1) && sy >= 0.f && sy <= (float)(H - 1);
     const float px = t.in ? sx : 0.f, py = t.in ? sy : 0.f;
@@ -32,6 +33,11 @@ __device__ __forceinline__ Taps flow_taps(int x, int y, float2 f, int H, int W) 
     t.a = px - fx, t.b = py - fy;
     t.o00 = y0 * W + x0, t.o01 = y0 * W + x1, t.o10 = y1 * W + x0, t.o11 = y1 * W + x1;
     return t;
+}
+
+__device__ __forceinline__ Taps flow_taps(int x, int y, float2 f, int H, int W) {
+#pragma clang fp contract(off)
+    return sample_taps((float)x + f.x, (float)y + f.y, H, W);
 }
 
 __device__ __forceinline__ float bilinear(const Taps &t, float g00, float g01, float g10, float g11) {

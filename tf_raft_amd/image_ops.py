@@ -39,6 +39,10 @@ tf_raft_amd/csrc/flow_splat.hip); ``range_visibility_launch`` is its in-step for
 ``forward_interpolate`` projects a low-resolution flow forward along itself: the start of the next pair's
 recurrence in a video stream (``raft_forward_interpolate_f32``, tf_raft_amd/csrc/flow_init.hip; ``tf_raft_amd.video``).
 
+``view_frames`` / ``view_flow`` cut the student's view of a self-supervised step out of the frames and carry the teacher's flow
+and trust mask into it, under one affine map per slice (``raft_view_frames_f32`` / ``raft_view_flow_f32``,
+tf_raft_amd/csrc/student_view.hip; the views are ``tf_raft_amd.augment.StudentView``).
+
 The model reaches the three ways through ONE object per call (``fit_route``: a ``CropOrPadRoute``, a ``ResizeRoute`` or a
 ``TilePlan``), which answers the same four questions whichever way it is: ``frames_in(t)`` (a frame batch -> the float32 batch
 the model runs on, one launch), ``result_size(B)`` (batch and size of the result for a model batch ``B``), ``flow_back(pred,
@@ -928,3 +932,135 @@ def forward_interpolate(flow) -> torch.Tensor:
         raise TypeError(f'a flow is float32, got {dtype}')
     t = _on_device(flow)
     return _dev.wrap(forward_interpolate_launch(t.reshape((-1,) + shape[-3:])).view(shape))
+
+
+# ------------------------------------------------------------------------------------------ the student's view
+def _view_size(size):
+    try:
+        Hs, Ws = size
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f'size must be the pair (H, W), got {size!r}') from exc
+    for v in (Hs, Ws):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f'size must be a pair of ints >= 1, got {size!r}')
+    return int(Hs), int(Ws)
+
+
+def view_host_records(views, slices: int) -> bytes:
+    """The ``RaftViewParams`` records of ``slices`` slices as bytes, checked on the host: ``views`` is an ``augment.StudentView`` of
+    N views -- ``slices == N`` gives every view with frame 1's colour, ``slices == 2N`` the doubled form of a training step, slices
+    ``n`` and ``n + N`` carrying view ``n`` with frame 1's and frame 2's colour.  Every number of a record must be finite."""
+    if not hasattr(views, 'records'):
+        raise ValueError(f'views must be an augment.StudentView, got {views!r}')
+    n = len(views)
+    if slices not in (n, 2 * n):
+        raise ValueError(f'{n} views serve {n} or {2 * n} slices, got {slices}')
+    recs = views.records(doubled=slices == 2 * n)
+    for b, r in enumerate(recs):
+        vals = [*r.m, *r.o, *r.inv] + ([*r.gain, *r.bias] if r.colour else [])
+        if not np.isfinite(np.array(vals, dtype=np.float64)).all():
+            raise ValueError(f'view record {b} holds a number that is not finite: {vals}')
+    return bytes(recs)
+
+
+_VIEW_STAGING = None          # pinned host buffers of the records' uploads (augment._Staging), made on first use
+
+
+def view_records(views, slices: int, device) -> torch.Tensor:
+    """``view_host_records`` uploaded on the current stream: the uint8 device tensor the launch forms below take (one upload serves
+    both).  The copy leaves from pinned memory and does not wait for what is queued, so the host of a training loop stays ahead."""
+    global _VIEW_STAGING
+    raw = view_host_records(views, int(slices))
+    if _VIEW_STAGING is None:
+        from .augment import _Staging
+        _VIEW_STAGING = _Staging()
+    with torch.cuda.device(device):
+        return _VIEW_STAGING.upload(raw, device)
+
+
+def _check_records(records, slices, device):
+    if (not isinstance(records, torch.Tensor) or records.dtype != torch.uint8 or records.device != device or not records.is_contiguous()
+            or records.numel() != slices * _ffi.C.sizeof(_ffi.ViewParams)):
+        raise ValueError(f'records must be the uint8 tensor of view_records() for {slices} slices on {device}')
+
+
+def view_frames_launch(t: torch.Tensor, records: torch.Tensor, size, out=None) -> torch.Tensor:
+    """The launch itself (``raft_view_frames_f32``): contiguous float32 device frames ``(B, Ht, Wt, C)`` seen through the ``B``
+    device records of ``view_records`` -> float32 ``(B, H, W, C)`` with ``size = (H, W)``, on the CURRENT stream (plain tensor)."""
+    Hs, Ws = _view_size(size)
+    if t.dim() != 4 or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f'view_frames takes contiguous float32 frames (B, Ht, Wt, C), got {t.dtype} {tuple(t.shape)}')
+    B, Ht, Wt, Cn = t.shape
+    _check_records(records, B, t.device)
+    out = _check_out(out, (B, Hs, Ws, Cn), torch.float32, t.device)
+    with torch.cuda.device(t.device):
+        check(_dev.lib().raft_view_frames_f32(_dev.ptr(t), _dev.ptr(records), _dev.ptr(out), B, Ht, Wt, Hs, Ws, Cn, _dev.stream_ptr()),
+              'view_frames')
+    return out
+
+
+def view_flow_launch(flow: torch.Tensor, records: torch.Tensor, size, visible=None):
+    """The launch itself (``raft_view_flow_f32``): a contiguous float32 device flow ``(B, Ht, Wt, 2)`` and an optional contiguous
+    uint8 trust mask ``(B, Ht, Wt)`` seen through the ``B`` device records -> ``(target (B, H, W, 2) float32, target_visible
+    (B, H, W) uint8)`` on the CURRENT stream (plain tensors)."""
+    Hs, Ws = _view_size(size)
+    if flow.dim() != 4 or flow.shape[-1] != 2:
+        raise ValueError(f'view_flow takes a flow (B, Ht, Wt, 2), got {tuple(flow.shape)}')
+    _check_flow(flow, 'view_flow')
+    B, Ht, Wt, _ = flow.shape
+    _check_records(records, B, flow.device)
+    if visible is not None:
+        visible = _check_out(visible, (B, Ht, Wt), torch.uint8, flow.device)
+    target = torch.empty((B, Hs, Ws, 2), device=flow.device, dtype=torch.float32)
+    target_visible = torch.empty((B, Hs, Ws), device=flow.device, dtype=torch.uint8)
+    with torch.cuda.device(flow.device):
+        check(_dev.lib().raft_view_flow_f32(_dev.ptr(flow), _dev.ptr(visible) if visible is not None else None, _dev.ptr(records),
+                                            _dev.ptr(target), _dev.ptr(target_visible), B, Ht, Wt, Hs, Ws, _dev.stream_ptr()), 'view_flow')
+    return target, target_visible
+
+
+def _shape_dtype(x):
+    if isinstance(x, torch.Tensor):
+        return tuple(x.shape), x.dtype
+    x = np.asarray(x)
+    return tuple(x.shape), x.dtype
+
+
+def view_frames(images, views, size):
+    """Frames ``(B, Ht, Wt, C)`` (NumPy or torch, host or device, float32; float64 narrows) cut out under the affine views
+    ``views`` (an ``augment.StudentView`` of B views, or of B / 2: the doubled batch of a training step) -> a float32 device tensor ``(B, H, W, C)`` with ``size = (H, W)``: pixel ``(y, x)`` of slice ``b`` is the
+    bilinear sample of the frame at ``M (x, y) + o``, 0 out of frame, then ``clip(v * gain + bias, 0, 255)`` where the view has a
+    gain.  One launch on the current stream; shapes and records are checked before anything moves."""
+    Hs, Ws = _view_size(size)
+    shape, dtype = _shape_dtype(images)
+    if len(shape) != 4 or 0 in shape:
+        raise ValueError(f'view_frames expects (B, Ht, Wt, C), got {shape}')
+    if str(dtype).replace('torch.', '') not in ('float32', 'float64'):
+        raise TypeError(f'view_frames takes float32 frames, got {dtype}')
+    view_host_records(views, shape[0])
+    t = _on_device(images)
+    recs = view_records(views, shape[0], t.device)
+    return _dev.wrap(view_frames_launch(t, recs, (Hs, Ws)))
+
+
+def view_flow(flow, views, size, visible=None):
+    """A flow ``(B, Ht, Wt, 2)`` float32 and an optional trust mask ``visible`` ``(B, Ht, Wt)`` (nonzero = trusted) seen through
+    the views (as for ``view_frames``) -> ``(target, target_visible)``: the float32 flow ``(B, H, W, 2)`` in the student's own
+    coordinates, ``Minv f(M q + o)``, and the uint8 mask ``(B, H, W)`` that is 1 where the pixel is in frame, every tap of
+    nonzero weight is trusted and the vector is finite; the target is (0, 0) elsewhere.  One launch on the current stream
+    (DESIGN.md section 23); shapes and records are checked before anything moves."""
+    from . import losses
+    Hs, Ws = _view_size(size)
+    shape, dtype = _shape_dtype(flow)
+    if len(shape) != 4 or shape[-1] != 2 or 0 in shape:
+        raise ValueError(f'view_flow expects a flow (B, Ht, Wt, 2), got {shape}')
+    if str(dtype).replace('torch.', '') not in ('float32', 'float64'):
+        raise TypeError(f'a flow is float32, got {dtype}')
+    if visible is not None and _shape_dtype(visible)[0] != shape[:3]:
+        raise ValueError(f'visible must be {shape[:3]}, got {_shape_dtype(visible)[0]}')
+    view_host_records(views, shape[0])
+    f = _on_device(flow)
+    recs = view_records(views, shape[0], f.device)
+    mask = losses._mask_to_device(visible, f.device) if visible is not None else None
+    target, target_visible = view_flow_launch(f, recs, (Hs, Ws), mask)
+    return _dev.wrap(target), _dev.wrap(target_visible)

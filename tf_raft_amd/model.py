@@ -692,7 +692,7 @@ class RAFT:
     def compile(self, optimizer=None, clip_norm=None, loss=None, epe=None, trainable='all', tape_dtype='f32', bidirectional=False,
                 occlusion=True, alpha=image_ops.CONSISTENCY_ALPHA, beta=image_ops.CONSISTENCY_BETA, occlusion_test='consistency',
                 range_threshold=image_ops.RANGE_THRESHOLD, selfsup_crop=None, selfsup_weight=0.3, selfsup_eps=0.001,
-                selfsup_mask='teacher', **kwargs):
+                selfsup_mask='teacher', selfsup_transform=None, **kwargs):
         """reference model.py:111-124.  ``loss`` / ``epe`` default to ``tf_raft_amd.losses.sequence_loss`` /
         ``end_point_error``; ``loss=losses.PhotometricSequenceLoss(...)`` makes ``train_step`` take unlabelled pairs
         ``(image1, image2)`` or ``(image1, image2, mask)`` and report ``loss`` / ``photometric`` / ``smoothness`` (DESIGN.md
@@ -719,7 +719,14 @@ class RAFT:
         (``last_visibility``); ``'occluded'`` is UFlow's rule: of those, the pixels that fail the student's own occlusion test
         (its mask is kept in ``model.last_student_visibility``).  ``model.selfsup_weight`` is a plain float that may be changed
         between steps (the recipes ramp it up after a warm-up); at 0 the second pass is skipped.  The step also reports
-        ``selfsup`` and ``selfsup_used``.  0.3 and 0.001 are UFlow's constants, not tuned here."""
+        ``selfsup`` and ``selfsup_used``.  0.3 and 0.001 are UFlow's constants, not tuned here.
+
+        ``selfsup_transform`` (needs ``selfsup_crop``, which keeps defining the student's size): an
+        ``augment.StudentTransform``, or any callable ``(N, (H, W), (Hs, Ws)) -> augment.StudentView``.  The student then sees
+        the frames through the step's drawn affine view (flip, zoom, rotation, shift, per-frame gain and bias) instead of the
+        centre crop, and is asked for the teacher's flow expressed in its own coordinates; the step's view is kept in
+        ``model.last_student_view`` and the ``(2N, Hs, Ws)`` uint8 mask of the student pixels that have a trusted teacher
+        vector in ``model.last_target_visibility``.  None: the centre crop, every step, key and bit as before."""
         from . import losses
         if kwargs:
             raise TypeError(f'unexpected keyword arguments {sorted(kwargs)}')
@@ -751,7 +758,16 @@ class RAFT:
         if selfsup_mask not in ('teacher', 'occluded'):
             raise ValueError(f"selfsup_mask must be 'teacher' or 'occluded', got {selfsup_mask!r}")
         _, selfsup_weight, selfsup_eps, _ = losses._selfsup_params(0.0, selfsup_weight, selfsup_eps)
+        if selfsup_transform is not None:
+            if selfsup_crop is None:
+                raise ValueError('selfsup_transform draws the view of the student pass: it needs selfsup_crop, which sets the student\'s size')
+            draw = getattr(selfsup_transform, 'draw', selfsup_transform)
+            if not callable(draw):
+                raise ValueError(f'selfsup_transform must be an augment.StudentTransform or a callable (N, (H, W), (Hs, Ws)) -> '
+                                 f'StudentView, got {selfsup_transform!r}')
         self.selfsup_crop, self.selfsup_weight, self.selfsup_eps, self.selfsup_mask = selfsup_crop, selfsup_weight, selfsup_eps, selfsup_mask
+        self.selfsup_transform = selfsup_transform
+        self.last_student_view = self.last_target_visibility = None
         self.bidirectional, self.occlusion = bool(bidirectional), bool(occlusion)
         self.last_visibility = None
         self.last_student_visibility = None
@@ -791,7 +807,10 @@ class RAFT:
         After ``compile(..., selfsup_crop=(cy, cx))`` a second graded pass follows on the centre crops of the
         frames, its loss ``raft_selfsup_loss_f32`` against the first pass's last prediction; the two passes' gradients are added
         and applied once, and the batch-norm moving statistics are updated with each pass's batch statistics in turn.  The
-        forward and backward of one pass is ``_graded_pass``, whatever the loss."""
+        forward and backward of one pass is ``_graded_pass``, whatever the loss.
+        With ``selfsup_transform`` the student's frames come from one ``raft_view_frames_f32`` launch over
+        the 2N distinct frames under the step's drawn view, and the teacher's flow and mask reach the loss through one
+        ``raft_view_flow_f32`` launch, already in the student's coordinates."""
         from . import grad, losses
         if not hasattr(self, 'flow_metrics'):
             raise RuntimeError('call compile() before train_step()')
@@ -852,6 +871,16 @@ class RAFT:
                         for k, v in self._weights.items()}
         wts = self._dw
         grad.clear_pack_cache()                     # packed copies of last step's weights
+        view_records = None
+        if bidirectional and crop is not None and weight2 > 0.0 and self.selfsup_transform is not None:
+            # the step's view is drawn and its records are uploaded NOW, for the reason given above
+            from . import augment
+            draw = getattr(self.selfsup_transform, 'draw', self.selfsup_transform)
+            view = draw(pairs, (H, W), (Hs, Ws))
+            if not isinstance(view, augment.StudentView) or len(view) != pairs:
+                raise ValueError(f'selfsup_transform must return an augment.StudentView of {pairs} views, got {view!r}')
+            view_records = image_ops.view_records(view, 2 * pairs, image1.device)
+            self.last_student_view = view
         drop_seed = None
         if full and self.drop_rate:
             # mask seeds: a different stream per data-parallel rank (ranks see different shards), per model seed and per
@@ -891,13 +920,22 @@ class RAFT:
                                                                        first_loss)
         gt, all_stats = flat(grads), [stats]
         if bidirectional and crop is not None:
-            self.last_student_visibility = None
+            self.last_student_visibility = self.last_target_visibility = None
         if bidirectional and crop is not None and weight2 > 0.0:
             # the student pass on the centre crops [c1 | c2] against [c2 | c1]; the teacher is the first
             # pass's last prediction, read through the window and held constant
-            Hs, Ws = H - 2 * crop[0], W - 2 * crop[1]
-            crop1, crop2 = image_ops.window_copy(image1.contiguous(), Hs, Ws), image_ops.window_copy(image2.contiguous(), Hs, Ws)
             teacher = last_pred.as_subclass(torch.Tensor).contiguous()
+            if view_records is None:
+                crop1, crop2 = image_ops.window_copy(image1.contiguous(), Hs, Ws), image_ops.window_copy(image2.contiguous(), Hs, Ws)
+                origin, teacher_visible = crop, visible1
+            else:
+                # the 2N distinct frames are the first operand of the doubled batch: ONE gather, then [s1 | s2] against [s2 | s1];
+                # the teacher's flow and mask in the student's coordinates by ONE more
+                crop1 = image_ops.view_frames_launch(image1.contiguous(), view_records, (Hs, Ws))
+                crop2 = torch.cat([crop1[pairs:], crop1[:pairs]], dim=0)
+                teacher, teacher_visible = image_ops.view_flow_launch(teacher, view_records, (Hs, Ws), visible1)
+                origin = (0, 0)
+                self.last_target_visibility = _dev.wrap(teacher_visible)
 
             def student_loss(preds):
                 student_visible = None
@@ -909,7 +947,7 @@ class RAFT:
                         student_visible, _ = image_ops.flow_visibility_launch(last, pairs, None, *self.consistency, apply=True)
                     self.last_student_visibility = _dev.wrap(student_visible)
                 selfsup = losses.SelfSupervisionLoss(self.loss.gamma, weight2, self.selfsup_eps)
-                terms2, d_preds = selfsup.value_and_grad(teacher, preds, crop, visible1, student_visible,
+                terms2, d_preds = selfsup.value_and_grad(teacher, preds, origin, teacher_visible, student_visible,
                                                          _add_to=terms['loss'].as_subclass(torch.Tensor))
                 return d_preds, terms2
 
