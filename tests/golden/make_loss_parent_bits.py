@@ -10,6 +10,13 @@ The cases are the smallest that reach each branch of the reduction (csrc/loss_co
     photometric (B, H, W, n)       1x3x5x1, 2x37x53x3, 1025x1x2x1 (B > kMaxRecords: the blockIdx.y loop wraps), 1x513x512x1
                                    (H*W > 1024*256: the x loop wraps)
     census, census_weight 0.5      1x7x7x1 (one interior pixel), 2x37x53x2, 769x7x7x1 (B > 768), 1x444x444x1 (H*W > 768*256)
+and, from the commit BEFORE the census and SSIM kernels came to share csrc/warped_gray.h, of the SSIM entry's sweep
+(csrc/ssim_loss.hip) and of the value-only kernels, which run only when no gradient is asked for:
+    ssim, ssim_weight 0.5          1x3x3x1 (one interior window; every pixel takes the edge path), 1x5x5x1 (one pixel takes
+    (census off)                   ssim_pixel_whole), 2x37x53x3, 769x3x3x1 (B > 768), 1x444x444x1 (H*W > 768*256); frames of
+                                   five pixels or less a side take vectors of less than a pixel, so that their windows are in frame
+    census+ssim, both 0.5          2x37x53x2: the chaining of add_to and accumulate
+    value-only, both 0.5           1x7x7x1, 2x37x53x2 through SSIMSequenceLoss.terms: scalars only
 The unlabelled cases run with and without a mask, from a list of host arrays and from views of one device buffer.
 """
 import hashlib
@@ -27,7 +34,14 @@ for p in (os.path.dirname(HERE), os.path.dirname(os.path.dirname(HERE))):
 SUPERVISED = [1, 63, 257, 1024 * 256 + 3]
 PHOTOMETRIC = [(1, 3, 5, 1), (2, 37, 53, 3), (1025, 1, 2, 1), (1, 513, 512, 1)]
 CENSUS = [(1, 7, 7, 1), (2, 37, 53, 2), (769, 7, 7, 1), (1, 444, 444, 1)]
-CASES = ([('supervised', npix) for npix in SUPERVISED] + [('photometric', s) for s in PHOTOMETRIC] + [('census', s) for s in CENSUS])
+SSIM = [(1, 3, 3, 1), (1, 5, 5, 1), (2, 37, 53, 3), (769, 3, 3, 1), (1, 444, 444, 1)]
+BOTH = [(2, 37, 53, 2)]
+VALUE_ONLY = [(1, 7, 7, 1), (2, 37, 53, 2)]
+CASES = ([('supervised', npix) for npix in SUPERVISED] + [('photometric', s) for s in PHOTOMETRIC] + [('census', s) for s in CENSUS]
+         + [('ssim', s) for s in SSIM] + [('census+ssim', s) for s in BOTH] + [('value-only', s) for s in VALUE_ONLY])
+# kind -> (census_weight, ssim_weight or None: the entries without the SSIM term, with the gradient)
+WEIGHTS = {'photometric': (0.0, None, True), 'census': (0.5, None, True), 'ssim': (0.0, 0.5, True), 'census+ssim': (0.5, 0.5, True),
+           'value-only': (0.5, 0.5, False)}
 PATH = os.path.join(HERE, 'loss_parent_bits.json')
 
 
@@ -68,15 +82,28 @@ def supervised(npix):
     return out
 
 
-def unlabelled(shape, census_weight):
-    from test_photometric_loss import DEFAULTS, make_case
-    from tf_raft_amd import grad
+def unlabelled_case(shape, with_mask, ssim=False):
+    """``make_case``; for the kinds with the SSIM term a frame of five pixels or less a side takes vectors of less than a pixel
+    (test_ssim_loss.ssim_case's rule for its one-window shape)."""
+    from test_photometric_loss import make_case
+    return make_case(*shape, with_mask=with_mask, **({'amp': 0} if ssim and min(shape[1:3]) <= 5 else {}))
+
+
+def unlabelled(shape, census_weight, ssim_weight, with_grad):
+    from test_photometric_loss import DEFAULTS
+    from tf_raft_amd import grad, losses
     out = {}
     for with_mask in (True, False):
-        image1, image2, mask, preds = make_case(*shape, with_mask=with_mask)
+        image1, image2, mask, preds = unlabelled_case(shape, with_mask, ssim_weight is not None)
         y_true = (image1, image2) if mask is None else (image1, image2, mask)
         for name, ps in (('list', preds), ('views', _views(preds))):
-            terms, grads = grad.photometric_sequence_loss_value_and_grad(y_true, ps, census_weight=census_weight, **DEFAULTS)
+            if not with_grad:
+                terms, grads = losses.SSIMSequenceLoss(census_weight=census_weight, ssim_weight=ssim_weight, **DEFAULTS).terms(y_true, ps), []
+            elif ssim_weight is None:
+                terms, grads = grad.photometric_sequence_loss_value_and_grad(y_true, ps, census_weight=census_weight, **DEFAULTS)
+            else:
+                terms, grads = grad.ssim_sequence_loss_value_and_grad(y_true, ps, census_weight=census_weight, ssim_weight=ssim_weight,
+                                                                      **DEFAULTS)
             key = f"{'mask' if with_mask else 'nomask'}/{name}"
             for k, v in terms.items():
                 out[f'{key}/{k}'] = _bits(v)
@@ -87,7 +114,7 @@ def unlabelled(shape, census_weight):
 
 def compute(case):
     kind, what = case
-    return supervised(what) if kind == 'supervised' else unlabelled(what, 0.0 if kind == 'photometric' else 0.5)
+    return supervised(what) if kind == 'supervised' else unlabelled(what, *WEIGHTS[kind])
 
 
 if __name__ == '__main__':

@@ -43,6 +43,7 @@ import torch
 
 from tf_raft_amd import _ffi
 from test_photometric_loss import (DEFAULTS, make_case, np_photometric_loss, out_of_frame_case, pred_weights, torch_photometric_loss)
+from windowed_loss import check_argument_errors
 
 # (B, H, W, n)        what it exercises on the GPU
 CASES = [(1, 6, 20, 1),           # no interior pixel: the value and every gradient element are exactly 0
@@ -58,9 +59,9 @@ OFFSETS = [(dy, dx) for dy in range(-RADIUS, RADIUS + 1) for dx in range(-RADIUS
 C_R, C_G, C_B, C_F, C_H = (float(np.float32(v)) for v in (0.299, 0.587, 0.114, 0.81, 0.1))
 
 
-def interior_mask(H, W):
+def interior_mask(H, W, radius=RADIUS):
     ys, xs = np.mgrid[0:H, 0:W]
-    return (xs >= RADIUS) & (xs <= W - 1 - RADIUS) & (ys >= RADIUS) & (ys <= H - 1 - RADIUS)
+    return (xs >= radius) & (xs <= W - 1 - radius) & (ys >= radius) & (ys <= H - 1 - radius)
 
 
 # ------------------------------------------------------------------ the yardstick: float64 torch, autograd
@@ -349,7 +350,7 @@ def test_the_census_restatement_on_the_cases_with_a_known_answer():
 # ------------------------------------------------------------------ the C entries
 def test_census_entries_are_declared_exported_and_typed():
     from tf_raft_amd import build
-    assert 'census_loss.hip' in build.SOURCES
+    assert 'census_loss.hip' in build.SOURCES and 'warped_gray.h' in build.HEADERS       # (a header outside the digest goes stale)
     _P, _I, _F = C.c_void_p, C.c_int, C.c_float
     assert _ffi._SIGNATURES['raft_census_loss_workspace_bytes'] == (C.c_int64, [_I, _I, _I, _I])
     assert _ffi._SIGNATURES['raft_census_loss_f32'] == (_I, [_P, _P, _P, _P, C.c_int64, _I, _I, _I, _I, C.c_double, _F, _F, _P, _P, _P,
@@ -365,56 +366,7 @@ def test_census_entries_are_declared_exported_and_typed():
 
 def test_census_argument_errors_are_returned_before_any_device_work():
     """No GPU here: a call that got past its checks would fail in the launch (a positive hipError_t) or crash."""
-    lib = _ffi.load_library()
-    fn = lib.raft_census_loss_f32
-    buf = (C.c_double * 64)()
-    p = C.cast(buf, C.c_void_p)
-    off = C.c_void_p(p.value + 4)
-    #       image1 image2 mask preds stride n  B  H  W  gamma cw  upstream add_to out2 d_preds accumulate ws stream
-    good = [p, p, p, p, 2 * 20, 3, 1, 4, 5, 0.8, 1.0, 1.0, p, p, p, 0, p, None]
-    for k in (0, 1, 3, 13, 16):                                             # (mask, add_to and d_preds may be NULL)
-        args = list(good)
-        args[k] = None
-        assert fn(*args) == -1, k
-    for k in (5, 6, 7, 8):
-        for v in (0, -3):
-            args = list(good)
-            args[k] = v
-            assert fn(*args) == -2, (k, v)
-    for bad in ((1, 1 << 15, 1 << 15), (1 << 10, 1 << 10, 1 << 10), (1, 1, 1 << 30), (1, 26755, 26755)):   # B*H*W*3 reaches 2^31
-        args = list(good)
-        args[6:9] = bad
-        args[4] = 1 << 40
-        assert fn(*args) == -2, bad
-    args = list(good)
-    args[4] = 2 * 20 - 2                                                    # predictions would overlap
-    assert fn(*args) == -2
-    args[4] = 2 * 20 + 1                                                    # read as float2
-    assert fn(*args) == -3
-    args = list(good)
-    args[5] = 65
-    assert fn(*args) == -3
-    for k in (9, 10):
-        for v in (-1e-3, float('nan'), float('inf'), -float('inf')):
-            args = list(good)
-            args[k] = v
-            assert fn(*args) == -2, (k, v)
-    for v in (float('nan'), float('inf')):
-        args = list(good)
-        args[11] = v
-        assert fn(*args) == -2, v
-    for v in (-1, 2):
-        args = list(good)
-        args[15] = v
-        assert fn(*args) == -2, v
-    for k in (3, 14, 16):
-        args = list(good)
-        args[k] = off
-        assert fn(*args) == -4, k
-    for m, a, d in ((None, None, None), (p, None, None), (None, p, None), (None, None, p)):      # no error of their own when NULL
-        args = list(good)
-        args[2], args[12], args[14], args[5] = m, a, d, 65
-        assert fn(*args) == -3, (m, a, d)
+    check_argument_errors(_ffi.load_library().raft_census_loss_f32)
 
 
 # ------------------------------------------------------------------ Python-side validation (nothing here reaches the device)

@@ -12,6 +12,14 @@ list and views alike; the kernel's distances equal the float32 restatement's to 
     census 769x7x7x1, census_weight 0.5         loss rel 5.9e-08, gradient / max|g| 5.2e-05
     census 1x444x444x1, census_weight 0.5       loss rel 7.2e-08, gradient / max|g| 8.3e-03
 
+The SSIM, census+ssim and value-only cases were added from the commit before the census and SSIM kernels came to share
+csrc/warped_gray.h (the SSIM sweep and the value-only kernels were pinned nowhere until then).  The two SSIM wrap cases are outside
+the shapes of test_gpu_ssim_loss.py and were measured on that commit in the same way, by that file's rule (4 x the float32
+restatement's own distance, floors 8 * 2^-24 and 16 * 2^-24 * max|g|), photometric + smoothness + 0.5 * SSIM, census off; with
+mask / without; list and views alike; the kernel's distances equal the restatement's to the printed digits, so both are inside:
+    ssim 769x3x3x1, ssim_weight 0.5             loss rel 9.8e-08 / 4.4e-08, gradient / max|g| 1.3e-06 / 1.2e-06
+    ssim 1x444x444x1, ssim_weight 0.5           loss rel 1.8e-08 / 2.7e-09, gradient / max|g| 1.2e-04 / 1.1e-04
+
 Two streams: losses on two streams of one device keep their partial records apart (losses._workspace is keyed by the stream).
 """
 import importlib.util

@@ -32,6 +32,7 @@ import pytest
 import torch
 
 from conftest import report
+from windowed_loss import entry
 from test_photometric_loss import DEFAULTS, out_of_frame_case
 from test_ssim_loss import (CASE_IDS, CASES, NO_INTERIOR, equal_frames_case, np_ssim_loss, np_ssim_total_loss, ssim_case,
                             ssim_only_distance, ssim_restatement_distance, ssim_total_yardstick, ssim_yardstick,
@@ -69,36 +70,9 @@ def _run(case, census_weight=0.0, ssim_weight=1.0, views=False, upstream=1.0, **
     return _scalars(terms), [_np(g) for g in grads]
 
 
-def _entry(case, ssim_weight=1.0, upstream=1.0, add_to=None, prefill=None, want_grad=True, gap=0, guard=0):
-    """raft_ssim_loss_f32 called directly: ``(out2 as float32 NumPy, d_preds (n, B, H, W, 2) or None, the whole slab)``.
-    ``prefill`` (with accumulate = 1) fills d_preds before the call; ``gap`` floats lie behind every prediction and ``guard``
-    floats of NaN around d_preds."""
-    from tf_raft_amd import _dev, losses
-    from tf_raft_amd._ffi import check
-    image1, image2, mask, preds = case
-    B, H, W, _ = image1.shape
-    n, npix = len(preds), B * H * W
-    stride = 2 * npix + gap
-    i1, i2 = torch.as_tensor(image1).cuda(), torch.as_tensor(image2).cuda()
-    m = None if mask is None else torch.as_tensor(mask).cuda()
-    src = torch.zeros((n * stride,), dtype=torch.float32, device='cuda')
-    for i, p in enumerate(preds):
-        src[i * stride:i * stride + 2 * npix] = torch.as_tensor(p).cuda().reshape(-1)
-    slab = torch.full((n * stride + 2 * guard,), float('nan'), dtype=torch.float32, device='cuda')
-    dst = slab[guard:guard + n * stride]
-    if prefill is not None:
-        dst.reshape(n, stride)[:, :2 * npix] = prefill
-    add = None if add_to is None else torch.tensor([add_to], dtype=torch.float32, device='cuda')
-    out = torch.full((2,), float('nan'), dtype=torch.float32, device='cuda')
-    lib = _dev.lib()
-    ws = losses._workspace(out.device, int(lib.raft_ssim_loss_workspace_bytes(n, B, H, W)))
-    check(lib.raft_ssim_loss_f32(_dev.ptr(i1), _dev.ptr(i2), None if m is None else _dev.ptr(m), _dev.ptr(src), stride, n, B, H, W,
-                                 DEFAULTS['gamma'], ssim_weight, upstream, None if add is None else _dev.ptr(add), _dev.ptr(out),
-                                 _dev.ptr(dst) if want_grad else None, 0 if prefill is None else 1, _dev.ptr(ws),
-                                 _dev.stream_ptr()), 'ssim_loss')
-    torch.cuda.synchronize()
-    d = _np(dst.reshape(n, stride)[:, :2 * npix]).reshape(n, B, H, W, 2) if want_grad else None
-    return _np(out), d, slab
+def _entry(case, ssim_weight=1.0, **kwargs):
+    """raft_ssim_loss_f32 called directly (windowed_loss.entry)."""
+    return entry('ssim', case, ssim_weight, **kwargs)
 
 
 @functools.lru_cache(maxsize=None)

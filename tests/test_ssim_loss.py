@@ -49,8 +49,10 @@ import pytest
 import torch
 
 from tf_raft_amd import _ffi
-from test_census_loss import _autograd, _distance, np_census_loss, torch_census_terms
+from test_census_loss import _autograd, _distance, _t64, np_census_loss, torch_census_terms
+from test_census_loss import interior_mask as census_interior_mask
 from test_photometric_loss import DEFAULTS, make_case, np_photometric_loss, out_of_frame_case, pred_weights, torch_photometric_loss
+from windowed_loss import check_argument_errors
 
 # (B, H, W, n)        what it exercises on the GPU
 CASES = [(1, 2, 20, 1),           # no interior pixel: the value and every gradient element are exactly 0
@@ -73,16 +75,10 @@ def ssim_case(shape, with_mask=True):
     return make_case(*shape, amp=0, with_mask=with_mask) if tuple(shape) == ONE_WINDOW else make_case(*shape, with_mask=with_mask)
 
 
-def interior_mask(H, W):
-    ys, xs = np.mgrid[0:H, 0:W]
-    return (xs >= 1) & (xs <= W - 2) & (ys >= 1) & (ys <= H - 2)
+interior_mask = functools.partial(census_interior_mask, radius=1)              # 1 <= x <= W-2 and 1 <= y <= H-2
 
 
 # ------------------------------------------------------------------ the yardstick: float64 torch, autograd
-def _t64(a):
-    return a.double() if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a), dtype=torch.float64)
-
-
 def torch_ssim_terms(image1, image2, mask, preds, gamma=0.8):
     """``(sum_i w_i * ssim_i, ssim_last)`` as 0-d float64 tensors; ``preds`` float64 tensors (B, H, W, 2) that may require grad."""
     i1, i2 = _t64(image1), _t64(image2)
@@ -401,58 +397,9 @@ def test_ssim_entries_are_declared_exported_and_typed():
 
 
 def test_ssim_argument_errors_are_returned_before_any_device_work():
-    """No GPU here: a call that got past its checks would fail in the launch (a positive hipError_t) or crash.  Index by index
+    """No GPU here: a call that got past its checks would fail in the launch (a positive hipError_t) or crash.  The body of
     tests/test_census_loss.py::test_census_argument_errors_are_returned_before_any_device_work."""
-    lib = _ffi.load_library()
-    fn = lib.raft_ssim_loss_f32
-    buf = (C.c_double * 64)()
-    p = C.cast(buf, C.c_void_p)
-    off = C.c_void_p(p.value + 4)
-    #       image1 image2 mask preds stride n  B  H  W  gamma sw  upstream add_to out2 d_preds accumulate ws stream
-    good = [p, p, p, p, 2 * 20, 3, 1, 4, 5, 0.8, 1.0, 1.0, p, p, p, 0, p, None]
-    for k in (0, 1, 3, 13, 16):                                             # (mask, add_to and d_preds may be NULL)
-        args = list(good)
-        args[k] = None
-        assert fn(*args) == -1, k
-    for k in (5, 6, 7, 8):
-        for v in (0, -3):
-            args = list(good)
-            args[k] = v
-            assert fn(*args) == -2, (k, v)
-    for bad in ((1, 1 << 15, 1 << 15), (1 << 10, 1 << 10, 1 << 10), (1, 1, 1 << 30), (1, 26755, 26755)):   # B*H*W*3 reaches 2^31
-        args = list(good)
-        args[6:9] = bad
-        args[4] = 1 << 40
-        assert fn(*args) == -2, bad
-    args = list(good)
-    args[4] = 2 * 20 - 2                                                    # predictions would overlap
-    assert fn(*args) == -2
-    args[4] = 2 * 20 + 1                                                    # read as float2
-    assert fn(*args) == -3
-    args = list(good)
-    args[5] = 65
-    assert fn(*args) == -3
-    for k in (9, 10):
-        for v in (-1e-3, float('nan'), float('inf'), -float('inf')):
-            args = list(good)
-            args[k] = v
-            assert fn(*args) == -2, (k, v)
-    for v in (float('nan'), float('inf')):
-        args = list(good)
-        args[11] = v
-        assert fn(*args) == -2, v
-    for v in (-1, 2):
-        args = list(good)
-        args[15] = v
-        assert fn(*args) == -2, v
-    for k in (3, 14, 16):
-        args = list(good)
-        args[k] = off
-        assert fn(*args) == -4, k
-    for m, a, d in ((None, None, None), (p, None, None), (None, p, None), (None, None, p)):      # no error of their own when NULL
-        args = list(good)
-        args[2], args[12], args[14], args[5] = m, a, d, 65
-        assert fn(*args) == -3, (m, a, d)
+    check_argument_errors(_ffi.load_library().raft_ssim_loss_f32)
 
 
 # ------------------------------------------------------------------ Python-side validation (nothing here reaches the device)

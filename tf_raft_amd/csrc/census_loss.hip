@@ -16,62 +16,23 @@
 //   d cen_i / d w(y) = -S(y) / (48*B*H*W),    d/du = that * dwdu(y), d/dv = that * dwdv(y)  (the one-sided derivatives of the cell the
 //   taps come from, 0 out of frame; `inside` and `mask` are constants of the gradient)
 //
-// Mapping: three launches.  (1) census_warp_kernel, one thread per pixel and prediction: g1 once, and per prediction the warped gray
-// w_i and M_i (as 1.f / 0.f), into the workspace.  (2) census_sweep_kernel, one thread per pixel looping over the predictions: the 48
+// Mapping: the three launches of warped_gray.h.  (1) warped_gray_kernel<3>: g1 once, and per prediction the warped gray w_i and M_i
+// (as 1.f / 0.f), into the workspace.  (2) census_sweep_kernel, one thread per pixel looping over the predictions: the 48
 // values f(g1(z) - g1(y)) do not depend on the prediction and are computed once per pixel (kept in the thread's own LDS column);
 // per prediction the thread reads the 7x7 windows of w_i (and of M_i for the gradient) through the cache, as photometric_loss.hip
-// reads its stencil, forms D and S from the same 48 pairs, re-gathers the four taps of g2 for dwdu / dwdv and touches its element
-// of d_preds once.  A pixel whose window lies in the frame takes a path without tests.  (3) a one-workgroup kernel adds the
-// sweep's records and normalises.  Deterministic: the reduction of loss_common.h.
+// reads its stencil, forms D and S from the same 48 pairs, and store_grad re-gathers the four taps of g2 for dwdu / dwdv and touches
+// its element of d_preds once.  A pixel whose window lies in the frame takes a path without tests.  (3) warped_final_kernel adds
+// the sweep's records and normalises.  Deterministic: the reduction of loss_common.h.
 #include "loss_common.h"
 
 #pragma clang fp contract(off)
 
-#include "flow_sample.h"
+#include "warped_gray.h"
 
 namespace {
 
-constexpr int kThreads = 256;         // (what raft_block_sum_store and raft_record_grid take a workgroup to be)
-constexpr int kMaxRecords = 768;      // partial records of the sweep: 3 workgroups per CU, what its 49 KiB of LDS let a CU hold
-constexpr int kVals = 2;              // sum_i w_i * CEN_i, CEN_{n-1} (sums before normalisation)
 constexpr int kRadius = 3, kSide = 2 * kRadius + 1;
 static_assert(kSide * kSide - 1 == 48, "the 48 neighbours of the definition");
-
-__device__ __forceinline__ float gray(const float *__restrict__ c) { return (0.299f * c[0] + 0.587f * c[1]) + 0.114f * c[2]; }
-
-// the four taps of gray(image2) of one image for a sample
-__device__ __forceinline__ void gray_taps(const float *__restrict__ i2, const Taps &t, float (&q)[4]) {
-    q[0] = gray(i2 + (int64_t)t.o00 * 3);
-    q[1] = gray(i2 + (int64_t)t.o01 * 3);
-    q[2] = gray(i2 + (int64_t)t.o10 * 3);
-    q[3] = gray(i2 + (int64_t)t.o11 * 3);
-}
-
-template <bool MASK>
-__global__ void __launch_bounds__(kThreads) census_warp_kernel(const float *__restrict__ image1, const float *__restrict__ image2,
-                                                               const uint8_t *__restrict__ mask, const float2 *__restrict__ preds,
-                                                               int64_t stride2, int B, int H, int W, float *__restrict__ g1,
-                                                               float *__restrict__ wv, float *__restrict__ valid) {
-    const int HW = H * W;
-    const int i = blockIdx.z;
-    const int64_t npix = (int64_t)B * HW;
-    for (int n = blockIdx.y; n < B; n += gridDim.y) {
-        const int64_t base = (int64_t)n * HW;
-        const float *i2 = image2 + base * 3;
-        for (int p = (int)blockIdx.x * kThreads + (int)threadIdx.x; p < HW; p += (int)gridDim.x * kThreads) {
-            const int y = p / W, x = p - y * W;
-            if (i == 0) g1[base + p] = gray(image1 + (base + p) * 3);
-            const Taps t = flow_taps(x, y, preds[(int64_t)i * stride2 + base + p], H, W);
-            float q[4];
-            gray_taps(i2, t, q);
-            const float w2 = bilinear(t, q[0], q[1], q[2], q[3]);
-            const bool use = MASK ? mask[base + p] != 0 : true;
-            const bool interior = x >= kRadius && x <= W - 1 - kRadius && y >= kRadius && y <= H - 1 - kRadius;
-            wv[(int64_t)i * npix + base + p] = t.in ? w2 : 0.f;
-            valid[(int64_t)i * npix + base + p] = (use && t.in && interior) ? 1.f : 0.f;
-        }
-    }
-}
 
 __device__ __forceinline__ float soft_sign(float d) { return d / sqrtf(0.81f + d * d); }
 
@@ -88,38 +49,6 @@ __device__ __forceinline__ void census_pair(float d, float fg, float m, bool ok,
         const float term = (m * (((2.f * e) * 0.1f) / (q * q))) * (0.81f / (r * sr));
         S += ok ? term : 0.f;
     }
-}
-
-struct SweepArgs {
-    const float *image2;
-    const float2 *preds;
-    int64_t stride2, npix;
-    int n_pred, H, W;
-    float scale;                      // upstream * census_weight
-    float inv48n;                     // 1 / (48*B*H*W)
-    int accumulate;
-    const float *g1, *wv, *valid;         // valid: M as 1.f / 0.f, so that a window row of it loads like a row of w
-    float2 *d_preds;
-};
-
-// upstream * census_weight * w_i * d cen_i / d (u, v) of one pixel from its S: the taps of g2 are gathered again (cheaper than
-// a second and third plane per prediction in the workspace)
-__device__ __forceinline__ void census_store_grad(const SweepArgs &a, int x, int y, int64_t at, int i, float wi, float S) {
-    const int64_t n_base = at - ((int64_t)y * a.W + x);
-    const Taps t = flow_taps(x, y, a.preds[(int64_t)i * a.stride2 + at], a.H, a.W);
-    float q[4];
-    gray_taps(a.image2 + n_base * 3, t, q);
-    const float du = t.in ? (1.f - t.b) * (q[1] - q[0]) + t.b * (q[3] - q[2]) : 0.f;
-    const float dv = t.in ? (1.f - t.a) * (q[2] - q[0]) + t.a * (q[3] - q[1]) : 0.f;
-    const float gw = 0.f - (a.scale * wi) * (S * a.inv48n);
-    float2 o = make_float2(gw * du, gw * dv);
-    float2 *dst = a.d_preds + (int64_t)i * a.stride2 + at;
-    if (a.accumulate) {
-        const float2 was = *dst;
-        o.x = was.x + o.x;
-        o.y = was.y + o.y;
-    }
-    *dst = o;
 }
 
 // One row of a pixel's window: seven values of w and, for the gradient, of M.
@@ -179,7 +108,7 @@ __device__ __forceinline__ void census_pixel_whole(const SweepArgs &a, const Pre
             acc[0] += (double)pw.w[i] * (double)D;
             if (i == a.n_pred - 1) acc[1] += (double)D;
         }
-        if (GRAD) census_store_grad(a, x, y, at, i, pw.w[i], S);
+        if (GRAD) store_grad(a, x, y, at, i, pw.w[i], S);
     }
 }
 
@@ -204,7 +133,7 @@ __device__ __forceinline__ void census_pixel_edge(const SweepArgs &a, const Pred
                 census_pair<true>(wp[z] - wc, soft_sign(a.g1[img + z] - gc), vp[z], ok, hs, S);
             }
         }
-        census_store_grad(a, x, y, at, i, pw.w[i], S);
+        store_grad(a, x, y, at, i, pw.w[i], S);
     }
 }
 
@@ -227,75 +156,28 @@ __global__ void __launch_bounds__(kThreads) census_sweep_kernel(SweepArgs a, int
     raft_block_sum_store(acc, part);
 }
 
-__global__ void __launch_bounds__(64) census_final_kernel(const double *__restrict__ part, int nparts, double inv, double census_weight,
-                                                          const float *add_to, float *out2) {
-    __shared__ double tot[kVals];
-    raft_sum_records(part, nparts, tot);
-    if (threadIdx.x == 0) {
-        const double before = add_to != nullptr ? (double)add_to[0] : 0.0;      // (read before out2 is written: they may be one address)
-        out2[0] = (float)(before + census_weight * (tot[0] * inv));
-        out2[1] = (float)(tot[1] * inv);
-    }
-}
-
-constexpr int64_t kRecordBytes = (int64_t)kMaxRecords * kVals * (int64_t)sizeof(double);
-
 }   // namespace
 
-// records | g1: B*H*W floats | w: n*B*H*W floats | M: n*B*H*W floats
 extern "C" int64_t raft_census_loss_workspace_bytes(int n_predictions, int B, int H, int W) {
-    if (!raft_loss_shape_ok(n_predictions, B, H, W) || n_predictions > kMaxPredictions) return 0;
-    const int64_t npix = (int64_t)B * H * W;
-    return kRecordBytes + 4 * npix + 8 * npix * n_predictions;
+    return warped_workspace_bytes(n_predictions, B, H, W);
 }
 
 extern "C" int raft_census_loss_f32(const float *image1, const float *image2, const uint8_t *mask, const float *preds,
                                     int64_t pred_stride, int n_predictions, int B, int H, int W, double gamma, float census_weight,
                                     float upstream, const float *add_to, float *out2, float *d_preds, int accumulate, void *workspace,
                                     void *stream) {
-    RAFT_REQUIRE_PTR(image1);
-    RAFT_REQUIRE_PTR(image2);
-    RAFT_REQUIRE_PTR(preds);
-    RAFT_REQUIRE_PTR(out2);
-    RAFT_REQUIRE_PTR(workspace);
-    RAFT_REQUIRE(raft_loss_shape_ok(n_predictions, B, H, W), RAFT_E_SHAPE);
-    const int64_t npix = (int64_t)B * H * W;
-    RAFT_REQUIRE(pred_stride >= 2 * npix, RAFT_E_SHAPE);
-    RAFT_REQUIRE(n_predictions <= kMaxPredictions && (pred_stride & 1) == 0, RAFT_E_UNSUPPORTED);
-    RAFT_REQUIRE(raft_finite_nonneg(gamma) && raft_finite_nonneg(census_weight), RAFT_E_SHAPE);
-    RAFT_REQUIRE(raft_finite_f32(upstream), RAFT_E_SHAPE);
-    RAFT_REQUIRE(accumulate == 0 || accumulate == 1, RAFT_E_SHAPE);
-    RAFT_REQUIRE(((((uintptr_t)preds) | ((uintptr_t)d_preds) | ((uintptr_t)workspace)) & 7u) == 0, RAFT_E_ALIGN);   // float2 / double
-
-    const PredWeights pw = raft_pred_weights(gamma, n_predictions);
-    double *part = (double *)workspace;
-    float *g1 = (float *)((char *)workspace + kRecordBytes);
-    float *wv = g1 + npix;
-    float *valid = wv + npix * n_predictions;
+    RAFT_TRY(warped_check_args(image1, image2, preds, pred_stride, n_predictions, B, H, W, gamma, census_weight, upstream, out2, d_preds,
+                               accumulate, workspace));
+    const WarpedPlanes p = warped_planes(workspace, (int64_t)B * H * W, n_predictions);
+    const SweepArgs a = sweep_args(image2, preds, pred_stride, n_predictions, B, H, W, upstream * census_weight, 48.0, d_preds, accumulate, p);
     hipStream_t s = (hipStream_t)stream;
-    const float2 *pr = (const float2 *)preds;
-    const int64_t stride2 = pred_stride / 2;
-    const int64_t blocks = ((int64_t)H * W + kThreads - 1) / kThreads;
-    {
-        const dim3 grid((unsigned)(blocks < 1024 ? blocks : 1024), (unsigned)(B < 64 ? B : 64), (unsigned)n_predictions);
-        if (mask != nullptr)
-            census_warp_kernel<true><<<grid, kThreads, 0, s>>>(image1, image2, mask, pr, stride2, B, H, W, g1, wv, valid);
-        else
-            census_warp_kernel<false><<<grid, kThreads, 0, s>>>(image1, image2, mask, pr, stride2, B, H, W, g1, wv, valid);
-        RAFT_TRY(raft_launch_status());
-    }
-    SweepArgs a;
-    a.image2 = image2, a.preds = pr, a.stride2 = stride2, a.npix = npix, a.n_pred = n_predictions, a.H = H, a.W = W;
-    a.scale = upstream * census_weight;
-    a.inv48n = (float)(1.0 / (48.0 * (double)npix));
-    a.accumulate = accumulate;
-    a.g1 = g1, a.wv = wv, a.valid = valid, a.d_preds = (float2 *)d_preds;
+    RAFT_TRY(launch_warped_gray<kRadius>(image1, mask, a, B, p, s));
+    const PredWeights pw = raft_pred_weights(gamma, n_predictions);
     const dim3 grid = raft_record_grid(B, (int64_t)H * W, kMaxRecords);
     if (d_preds != nullptr)
-        census_sweep_kernel<true><<<grid, kThreads, 0, s>>>(a, B, pw, part);
+        census_sweep_kernel<true><<<grid, kThreads, 0, s>>>(a, B, pw, p.part);
     else
-        census_sweep_kernel<false><<<grid, kThreads, 0, s>>>(a, B, pw, part);
+        census_sweep_kernel<false><<<grid, kThreads, 0, s>>>(a, B, pw, p.part);
     RAFT_TRY(raft_launch_status());
-    census_final_kernel<<<1, 64, 0, s>>>(part, (int)(grid.x * grid.y), 1.0 / (double)npix, (double)census_weight, add_to, out2);
-    return raft_launch_status();
+    return launch_warped_final(p, grid, a.npix, census_weight, add_to, out2, s);
 }

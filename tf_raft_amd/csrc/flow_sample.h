@@ -1,6 +1,6 @@
 // The one definition of "the sample of a map under a flow vector" (DESIGN.md sections 15 and 17), shared by flow_check.hip (warp,
-// forward-backward consistency), photometric_loss.hip (the self-supervised loss and its gradient) and student_view.hip (the same
-// sample at a position that an affine map gives).
+// forward-backward consistency), photometric_loss.hip (the self-supervised loss and its gradient), warped_gray.h (the warped gray
+// of the census and SSIM terms) and student_view.hip (the same sample at a position that an affine map gives).
 //
 // For the pixel at integer (x, y) with vector (u, v): sx = float(x) + u and sy = float(y) + v, ONE float32 addition each; the
 // pixel is in frame iff 0 <= sx <= W - 1 and 0 <= sy <= H - 1 (a NaN fails); x0 = floor(sx), x1 = min(x0 + 1, W - 1),
@@ -44,6 +44,18 @@ __device__ __forceinline__ float bilinear(const Taps &t, float g00, float g01, f
 #pragma clang fp contract(off)
     const float na = 1.f - t.a, nb = 1.f - t.b;
     return nb * (na * g00 + t.a * g01) + t.b * (na * g10 + t.a * g11);
+}
+
+// The one-sided derivatives of that value by u and by v inside the cell the taps come from (zero where x1 == x0 or y1 == y0):
+// dW/du = (1-b)*(g01-g00) + b*(g11-g10),  dW/dv = (1-a)*(g10-g00) + a*(g11-g01).  The caller drops them where !t.in.
+__device__ __forceinline__ float bilinear_du(const Taps &t, float g00, float g01, float g10, float g11) {
+#pragma clang fp contract(off)
+    return (1.f - t.b) * (g01 - g00) + t.b * (g11 - g10);
+}
+
+__device__ __forceinline__ float bilinear_dv(const Taps &t, float g00, float g01, float g10, float g11) {
+#pragma clang fp contract(off)
+    return (1.f - t.a) * (g10 - g00) + t.a * (g11 - g01);
 }
 
 }   // namespace

@@ -10,8 +10,8 @@
 //   loss = sum_i w_i * (ph_i + smooth_weight * sm_i),   out3 = {loss, ph_{n-1}, sm_{n-1}}
 //
 // The sample (position, in-frame test, taps, weights a and b) is flow_sample.h's, the one flow_check.hip uses.  `inside` and
-// `mask` are constants of the gradient; dW2/du = (1-b)*(g01-g00) + b*(g11-g10), dW2/dv = (1-a)*(g10-g00) + a*(g11-g01): the
-// one-sided derivative of the cell the taps come from (zero where x1 == x0).  The smoothness gradient is the adjoint written
+// `mask` are constants of the gradient; dW2/du = (1-b)*(g01-g00) + b*(g11-g10), dW2/dv = (1-a)*(g10-g00) + a*(g11-g01) are that
+// header's too: the one-sided derivative of the cell the taps come from (zero where x1 == x0).  The smoothness gradient is the adjoint written
 // as a gather: with tx = wx*dx/rho(dx), ty = wy*dy/rho(dy),
 //   d sm_i / d p(x,y)_k = (-tx(x,y) - ty(x,y) + tx(x-1,y) + ty(x,y-1)) / (B*H*W*2), terms that do not exist dropped.
 //
@@ -110,8 +110,8 @@ __global__ void __launch_bounds__(kThreads) photometric_loss_kernel(const float 
                     ph += r;
                     if (GRAD) {
                         const float q = (d / r) * s;
-                        const float du = (1.f - t.b) * (g[ch][1] - g[ch][0]) + t.b * (g[ch][3] - g[ch][2]);
-                        const float dv = (1.f - t.a) * (g[ch][2] - g[ch][0]) + t.a * (g[ch][3] - g[ch][1]);
+                        const float du = bilinear_du(t, g[ch][0], g[ch][1], g[ch][2], g[ch][3]);
+                        const float dv = bilinear_dv(t, g[ch][0], g[ch][1], g[ch][2], g[ch][3]);
                         gu += q * du;
                         gv += q * dv;
                     }

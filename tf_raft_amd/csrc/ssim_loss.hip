@@ -1,7 +1,7 @@
 // SSIM term of the self-supervised sequence loss (no reference counterpart): the structural-similarity data
 // term of ARFlow-style recipes, with d term / d prediction_i.  Definitions (every product and sum rounded on its own):
 //
-//   gray, g1, g2, w_i(x) = inside ? bilinear(taps of flow_sample.h under p_i, g2) : 0      exactly census_loss.hip's
+//   gray, g1, g2, w_i(x) = inside ? bilinear(taps of flow_sample.h under p_i, g2) : 0      warped_gray.h's
 //   C1 = (0.01f*255.f)^2, C2 = (0.03f*255.f)^2;  interior(z) = 1 <= zx <= W-2 && 1 <= zy <= H-2,  M_i = mask && inside_i && interior
 //   over the 3x3 window of z, rows first, x = g1:   mx = (sum x) / 9.f,  mw = (sum w) / 9.f,
 //   sxx = (sum (x-mx)*(x-mx)) / 9.f,  sww = (sum (w-mw)*(w-mw)) / 9.f,  sxw = (sum (x-mx)*(w-mw)) / 9.f
@@ -13,66 +13,27 @@
 // Gradient as a gather.  With r1 = n1/d1, r2 = n2/d2 the derivatives of S by mw, sww (twice) and sxw of a window are
 //   A = ((2.f*mx - (2.f*mw)*r1) * r2) / d1,     R = (2.f*r1) / d2,     Q2 = 0.f - R*r2
 //   G(y) = sum over z in frame, |z - y|_inf <= 1, rows first, of M(z) ? (A(z) + Q2(z)*(w(y) - mw(z))) + R(z)*(x(y) - mx(z)) : 0
-//   d ssim_i / d w(y) = -G(y) / (18*B*H*W),    d/du = that * dwdu(y), d/dv = that * dwdv(y)      (census_loss.hip's dwdu / dwdv)
+//   d ssim_i / d w(y) = -G(y) / (18*B*H*W),    d/du = that * dwdu(y), d/dv = that * dwdv(y)      (flow_sample.h's dW/du, dW/dv)
 // (equal frames at zero flow: r1 = r2 = 1, A = 0 and Q2 = -R exactly, so G is exactly 0 as S is exactly 1).  A window with M = 1 is
 // interior, so its nine pixels are in the frame: no window is ever read past a border.
 //
-// Mapping: three launches, as census_loss.hip.  (1) ssim_warp_kernel, one thread per pixel and prediction: g1 once, and per
-// prediction w_i and M_i (as 1.f / 0.f), into the workspace.  (2) ssim_sweep_kernel, one thread per pixel looping over the
+// Mapping: the three launches of warped_gray.h, as census_loss.hip.  (1) warped_gray_kernel<1>: g1 once, and per prediction w_i
+// and M_i (as 1.f / 0.f), into the workspace.  (2) ssim_sweep_kernel, one thread per pixel looping over the
 // predictions.  A pixel whose 5x5 neighbourhood lies in the frame keeps the 25 values of g1 and the mx / sxx of its nine windows in
 // registers (they do not depend on the prediction), reads per prediction the 5x5 of w_i and the 3x3 of M_i through the cache and
-// forms D and G from them; the pixels nearer the border walk their windows one at a time.  The four taps of g2 are gathered again
-// for dwdu / dwdv and the element of d_preds is touched once.  (3) a one-workgroup kernel adds the sweep's records and normalises.
+// forms D and G from them; the pixels nearer the border walk their windows one at a time.  store_grad gathers the four taps of g2
+// again for dwdu / dwdv and touches the element of d_preds once.  (3) warped_final_kernel adds the sweep's records and normalises.
 // Deterministic: the reduction of loss_common.h.
 #include "loss_common.h"
 
 #pragma clang fp contract(off)
 
-#include "flow_sample.h"
+#include "warped_gray.h"
 
 namespace {
 
-constexpr int kThreads = 256;         // (what raft_block_sum_store and raft_record_grid take a workgroup to be)
-constexpr int kMaxRecords = 768;      // partial records of the sweep (the census entry's number: the two workspaces are one size)
-constexpr int kVals = 2;              // sum_i w_i * SSIM_i, SSIM_{n-1} (sums before normalisation)
 constexpr float kC1 = (0.01f * 255.f) * (0.01f * 255.f);
 constexpr float kC2 = (0.03f * 255.f) * (0.03f * 255.f);
-
-__device__ __forceinline__ float gray(const float *__restrict__ c) { return (0.299f * c[0] + 0.587f * c[1]) + 0.114f * c[2]; }
-
-// the four taps of gray(image2) of one image for a sample
-__device__ __forceinline__ void gray_taps(const float *__restrict__ i2, const Taps &t, float (&q)[4]) {
-    q[0] = gray(i2 + (int64_t)t.o00 * 3);
-    q[1] = gray(i2 + (int64_t)t.o01 * 3);
-    q[2] = gray(i2 + (int64_t)t.o10 * 3);
-    q[3] = gray(i2 + (int64_t)t.o11 * 3);
-}
-
-template <bool MASK>
-__global__ void __launch_bounds__(kThreads) ssim_warp_kernel(const float *__restrict__ image1, const float *__restrict__ image2,
-                                                             const uint8_t *__restrict__ mask, const float2 *__restrict__ preds,
-                                                             int64_t stride2, int B, int H, int W, float *__restrict__ g1,
-                                                             float *__restrict__ wv, float *__restrict__ valid) {
-    const int HW = H * W;
-    const int i = blockIdx.z;
-    const int64_t npix = (int64_t)B * HW;
-    for (int n = blockIdx.y; n < B; n += gridDim.y) {
-        const int64_t base = (int64_t)n * HW;
-        const float *i2 = image2 + base * 3;
-        for (int p = (int)blockIdx.x * kThreads + (int)threadIdx.x; p < HW; p += (int)gridDim.x * kThreads) {
-            const int y = p / W, x = p - y * W;
-            if (i == 0) g1[base + p] = gray(image1 + (base + p) * 3);
-            const Taps t = flow_taps(x, y, preds[(int64_t)i * stride2 + base + p], H, W);
-            float q[4];
-            gray_taps(i2, t, q);
-            const float w2 = bilinear(t, q[0], q[1], q[2], q[3]);
-            const bool use = MASK ? mask[base + p] != 0 : true;
-            const bool interior = x >= 1 && x <= W - 2 && y >= 1 && y <= H - 2;
-            wv[(int64_t)i * npix + base + p] = t.in ? w2 : 0.f;
-            valid[(int64_t)i * npix + base + p] = (use && t.in && interior) ? 1.f : 0.f;
-        }
-    }
-}
 
 // ---------------------------------------------------------------- one 3x3 window (values rows first)
 __device__ __forceinline__ float mean9(const float (&v)[9]) {
@@ -113,38 +74,6 @@ __device__ __forceinline__ float ssim_of_moments(float mx, float sxx, float mw, 
 // A window's share of G at one of its pixels with values xy = x(y), wy = w(y)
 __device__ __forceinline__ float window_share(const Coefs &c, float xy, float mx, float wy, float mw) {
     return (c.A + c.Q2 * (wy - mw)) + c.R * (xy - mx);
-}
-
-struct SweepArgs {
-    const float *image2;
-    const float2 *preds;
-    int64_t stride2, npix;
-    int n_pred, H, W;
-    float scale;                      // upstream * ssim_weight
-    float inv18n;                     // 1 / (18*B*H*W)
-    int accumulate;
-    const float *g1, *wv, *valid;     // valid: M as 1.f / 0.f
-    float2 *d_preds;
-};
-
-// upstream * ssim_weight * w_i * d ssim_i / d (u, v) of one pixel from its G: the taps of g2 are gathered again (cheaper than a
-// second and third plane per prediction in the workspace)
-__device__ __forceinline__ void ssim_store_grad(const SweepArgs &a, int x, int y, int64_t at, int i, float wi, float G) {
-    const int64_t n_base = at - ((int64_t)y * a.W + x);
-    const Taps t = flow_taps(x, y, a.preds[(int64_t)i * a.stride2 + at], a.H, a.W);
-    float q[4];
-    gray_taps(a.image2 + n_base * 3, t, q);
-    const float du = t.in ? (1.f - t.b) * (q[1] - q[0]) + t.b * (q[3] - q[2]) : 0.f;
-    const float dv = t.in ? (1.f - t.a) * (q[2] - q[0]) + t.a * (q[3] - q[1]) : 0.f;
-    const float gw = 0.f - (a.scale * wi) * (G * a.inv18n);
-    float2 o = make_float2(gw * du, gw * dv);
-    float2 *dst = a.d_preds + (int64_t)i * a.stride2 + at;
-    if (a.accumulate) {
-        const float2 was = *dst;
-        o.x = was.x + o.x;
-        o.y = was.y + o.y;
-    }
-    *dst = o;
 }
 
 __device__ __forceinline__ void ssim_add_value(const SweepArgs &a, const PredWeights &pw, int i, float S, double (&acc)[kVals]) {
@@ -230,7 +159,7 @@ __device__ __forceinline__ void ssim_pixel_whole(const SweepArgs &a, const PredW
                 G = G + (m9[z] != 0.f ? share : 0.f);
                 if (z == 4 && m9[4] != 0.f) ssim_add_value(a, pw, i, S, acc);
             }
-        ssim_store_grad(a, x, y, at, i, pw.w[i], G);
+        store_grad(a, x, y, at, i, pw.w[i], G);
     }
 }
 
@@ -261,7 +190,7 @@ __device__ __forceinline__ void ssim_pixel_edge(const SweepArgs &a, const PredWe
                 if (dy == 0 && dx == 0) ssim_add_value(a, pw, i, S, acc);
             }
         }
-        ssim_store_grad(a, x, y, at, i, pw.w[i], G);
+        store_grad(a, x, y, at, i, pw.w[i], G);
     }
 }
 
@@ -284,75 +213,28 @@ __global__ void __launch_bounds__(kThreads) ssim_sweep_kernel(SweepArgs a, int B
     raft_block_sum_store(acc, part);
 }
 
-__global__ void __launch_bounds__(64) ssim_final_kernel(const double *__restrict__ part, int nparts, double inv, double ssim_weight,
-                                                        const float *add_to, float *out2) {
-    __shared__ double tot[kVals];
-    raft_sum_records(part, nparts, tot);
-    if (threadIdx.x == 0) {
-        const double before = add_to != nullptr ? (double)add_to[0] : 0.0;      // (read before out2 is written: they may be one address)
-        out2[0] = (float)(before + ssim_weight * (tot[0] * inv));
-        out2[1] = (float)(tot[1] * inv);
-    }
-}
-
-constexpr int64_t kRecordBytes = (int64_t)kMaxRecords * kVals * (int64_t)sizeof(double);
-
 }   // namespace
 
-// records | g1: B*H*W floats | w: n*B*H*W floats | M: n*B*H*W floats
 extern "C" int64_t raft_ssim_loss_workspace_bytes(int n_predictions, int B, int H, int W) {
-    if (!raft_loss_shape_ok(n_predictions, B, H, W) || n_predictions > kMaxPredictions) return 0;
-    const int64_t npix = (int64_t)B * H * W;
-    return kRecordBytes + 4 * npix + 8 * npix * n_predictions;
+    return warped_workspace_bytes(n_predictions, B, H, W);
 }
 
 extern "C" int raft_ssim_loss_f32(const float *image1, const float *image2, const uint8_t *mask, const float *preds,
                                   int64_t pred_stride, int n_predictions, int B, int H, int W, double gamma, float ssim_weight,
                                   float upstream, const float *add_to, float *out2, float *d_preds, int accumulate, void *workspace,
                                   void *stream) {
-    RAFT_REQUIRE_PTR(image1);
-    RAFT_REQUIRE_PTR(image2);
-    RAFT_REQUIRE_PTR(preds);
-    RAFT_REQUIRE_PTR(out2);
-    RAFT_REQUIRE_PTR(workspace);
-    RAFT_REQUIRE(raft_loss_shape_ok(n_predictions, B, H, W), RAFT_E_SHAPE);
-    const int64_t npix = (int64_t)B * H * W;
-    RAFT_REQUIRE(pred_stride >= 2 * npix, RAFT_E_SHAPE);
-    RAFT_REQUIRE(n_predictions <= kMaxPredictions && (pred_stride & 1) == 0, RAFT_E_UNSUPPORTED);
-    RAFT_REQUIRE(raft_finite_nonneg(gamma) && raft_finite_nonneg(ssim_weight), RAFT_E_SHAPE);
-    RAFT_REQUIRE(raft_finite_f32(upstream), RAFT_E_SHAPE);
-    RAFT_REQUIRE(accumulate == 0 || accumulate == 1, RAFT_E_SHAPE);
-    RAFT_REQUIRE(((((uintptr_t)preds) | ((uintptr_t)d_preds) | ((uintptr_t)workspace)) & 7u) == 0, RAFT_E_ALIGN);   // float2 / double
-
-    const PredWeights pw = raft_pred_weights(gamma, n_predictions);
-    double *part = (double *)workspace;
-    float *g1 = (float *)((char *)workspace + kRecordBytes);
-    float *wv = g1 + npix;
-    float *valid = wv + npix * n_predictions;
+    RAFT_TRY(warped_check_args(image1, image2, preds, pred_stride, n_predictions, B, H, W, gamma, ssim_weight, upstream, out2, d_preds,
+                               accumulate, workspace));
+    const WarpedPlanes p = warped_planes(workspace, (int64_t)B * H * W, n_predictions);
+    const SweepArgs a = sweep_args(image2, preds, pred_stride, n_predictions, B, H, W, upstream * ssim_weight, 18.0, d_preds, accumulate, p);
     hipStream_t s = (hipStream_t)stream;
-    const float2 *pr = (const float2 *)preds;
-    const int64_t stride2 = pred_stride / 2;
-    const int64_t blocks = ((int64_t)H * W + kThreads - 1) / kThreads;
-    {
-        const dim3 grid((unsigned)(blocks < 1024 ? blocks : 1024), (unsigned)(B < 64 ? B : 64), (unsigned)n_predictions);
-        if (mask != nullptr)
-            ssim_warp_kernel<true><<<grid, kThreads, 0, s>>>(image1, image2, mask, pr, stride2, B, H, W, g1, wv, valid);
-        else
-            ssim_warp_kernel<false><<<grid, kThreads, 0, s>>>(image1, image2, mask, pr, stride2, B, H, W, g1, wv, valid);
-        RAFT_TRY(raft_launch_status());
-    }
-    SweepArgs a;
-    a.image2 = image2, a.preds = pr, a.stride2 = stride2, a.npix = npix, a.n_pred = n_predictions, a.H = H, a.W = W;
-    a.scale = upstream * ssim_weight;
-    a.inv18n = (float)(1.0 / (18.0 * (double)npix));
-    a.accumulate = accumulate;
-    a.g1 = g1, a.wv = wv, a.valid = valid, a.d_preds = (float2 *)d_preds;
+    RAFT_TRY(launch_warped_gray<1>(image1, mask, a, B, p, s));
+    const PredWeights pw = raft_pred_weights(gamma, n_predictions);
     const dim3 grid = raft_record_grid(B, (int64_t)H * W, kMaxRecords);
     if (d_preds != nullptr)
-        ssim_sweep_kernel<true><<<grid, kThreads, 0, s>>>(a, B, pw, part);
+        ssim_sweep_kernel<true><<<grid, kThreads, 0, s>>>(a, B, pw, p.part);
     else
-        ssim_sweep_kernel<false><<<grid, kThreads, 0, s>>>(a, B, pw, part);
+        ssim_sweep_kernel<false><<<grid, kThreads, 0, s>>>(a, B, pw, p.part);
     RAFT_TRY(raft_launch_status());
-    ssim_final_kernel<<<1, 64, 0, s>>>(part, (int)(grid.x * grid.y), 1.0 / (double)npix, (double)ssim_weight, add_to, out2);
-    return raft_launch_status();
+    return launch_warped_final(p, grid, a.npix, ssim_weight, add_to, out2, s);
 }

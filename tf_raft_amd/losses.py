@@ -19,6 +19,7 @@ CPU fallback.
 """
 from __future__ import annotations
 
+import functools
 import math
 import numbers
 
@@ -116,20 +117,16 @@ def _real(name, v):
         raise ValueError(f'{name} must be a real number, got {v!r}') from exc
 
 
-def _census_weight(census_weight):
-    """``census_weight`` as raft_census_loss_f32 checks it: finite and >= 0."""
-    v = _real('census_weight', census_weight)
+def _term_weight(name, weight):
+    """The weight of a windowed data term as its entry (raft_census_loss_f32, raft_ssim_loss_f32) checks it: finite and >= 0."""
+    v = _real(name, weight)
     if not 0.0 <= v <= _F32_MAX:
-        raise ValueError(f'census_weight must be finite and >= 0, got {v!r}')
+        raise ValueError(f'{name} must be finite and >= 0, got {v!r}')
     return v
 
 
-def _ssim_weight(ssim_weight):
-    """``ssim_weight`` as raft_ssim_loss_f32 checks it: finite and >= 0."""
-    v = _real('ssim_weight', ssim_weight)
-    if not 0.0 <= v <= _F32_MAX:
-        raise ValueError(f'ssim_weight must be finite and >= 0, got {v!r}')
-    return v
+_census_weight = functools.partial(_term_weight, 'census_weight')
+_ssim_weight = functools.partial(_term_weight, 'ssim_weight')
 
 
 def _photometric_params(gamma, smooth_weight, edge_weight, eps, upstream=1.0):
@@ -242,16 +239,15 @@ def _photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, 
     if mask is not None:
         mask = _mask_to_device(mask, image1.device)
     n = len(preds)
-    census, ssim = census_weight > 0.0, ssim_weight > 0.0
-    # [loss, photometric, smoothness], and behind them, per windowed term that is on, [loss with that term too, the term]
-    at_census, at_ssim = 3, 5 if census else 3
-    last = at_ssim if ssim else at_census if census else 0
-    buf = torch.zeros((3 + 2 * census + 2 * ssim,), dtype=torch.float32, device=image1.device)
-    out = {'loss': buf[last], 'photometric': buf[1]}
-    if census:
-        out['census'] = buf[at_census + 1]
-    if ssim:
-        out['ssim'] = buf[at_ssim + 1]
+    # buf = [loss, photometric, smoothness], and behind them, per windowed term that is on, its out2 = [loss with that term too,
+    # the term]; a term's add_to is the loss so far: the out2 of the term before it, or buf[0].  One row per term that is on, in
+    # launch order: (key of raft_<key>_loss_f32 / raft_<key>_loss_workspace_bytes, weight, where its add_to sits, where its out2)
+    on = [(key, weight) for key, weight in (('census', census_weight), ('ssim', ssim_weight)) if weight > 0.0]
+    windowed = [(key, weight, 1 + 2 * j if j else 0, 3 + 2 * j) for j, (key, weight) in enumerate(on)]
+    buf = torch.zeros((3 + 2 * len(windowed),), dtype=torch.float32, device=image1.device)
+    out = {'loss': buf[windowed[-1][3] if windowed else 0], 'photometric': buf[1]}
+    for key, _, _, at_out2 in windowed:
+        out[key] = buf[at_out2 + 1]
     out['smoothness'] = buf[2]
     if n == 0:
         return out, None
@@ -261,27 +257,20 @@ def _photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, 
     d_preds = torch.empty((n, B, H, W, 2), dtype=torch.float32, device=image1.device) if want_grad else None
     lib = _dev.lib()
     # one buffer for all entries: the census and SSIM launches follow the photometric ones on the stream
-    need = 8 * int(lib.raft_photometric_loss_workspace_doubles())
-    if census:
-        need = max(need, int(lib.raft_census_loss_workspace_bytes(n, B, H, W)))
-    if ssim:
-        need = max(need, int(lib.raft_ssim_loss_workspace_bytes(n, B, H, W)))
+    need = max([8 * int(lib.raft_photometric_loss_workspace_doubles())]
+               + [int(getattr(lib, f'raft_{key}_loss_workspace_bytes')(n, B, H, W)) for key, _, _, _ in windowed])
     ws = _workspace(buf.device, need)
     check(lib.raft_photometric_loss_f32(_dev.ptr(image1), _dev.ptr(image2), _dev.ptr(mask) if mask is not None else None,
                                         _dev.ptr(stacked), stride, n, B, H, W, gamma, smooth_weight, edge_weight, eps,
                                         upstream, _dev.ptr(buf), _dev.ptr(d_preds) if want_grad else None,
                                         _dev.ptr(ws), _dev.stream_ptr()),
           'photometric_loss')
-    if census:
-        check(lib.raft_census_loss_f32(_dev.ptr(image1), _dev.ptr(image2), _dev.ptr(mask) if mask is not None else None,
-                                       _dev.ptr(stacked), stride, n, B, H, W, gamma, census_weight, upstream, _dev.ptr(buf),
-                                       _dev.ptr(buf[3:]), _dev.ptr(d_preds) if want_grad else None, 1, _dev.ptr(ws),
-                                       _dev.stream_ptr()), 'census_loss')
-    if ssim:
-        check(lib.raft_ssim_loss_f32(_dev.ptr(image1), _dev.ptr(image2), _dev.ptr(mask) if mask is not None else None,
-                                     _dev.ptr(stacked), stride, n, B, H, W, gamma, ssim_weight, upstream,
-                                     _dev.ptr(buf[at_census if census else 0:]), _dev.ptr(buf[at_ssim:]),
-                                     _dev.ptr(d_preds) if want_grad else None, 1, _dev.ptr(ws), _dev.stream_ptr()), 'ssim_loss')
+    for key, weight, at_add_to, at_out2 in windowed:
+        check(getattr(lib, f'raft_{key}_loss_f32')(_dev.ptr(image1), _dev.ptr(image2), _dev.ptr(mask) if mask is not None else None,
+                                                   _dev.ptr(stacked), stride, n, B, H, W, gamma, weight, upstream,
+                                                   _dev.ptr(buf[at_add_to:]), _dev.ptr(buf[at_out2:]),
+                                                   _dev.ptr(d_preds) if want_grad else None, 1, _dev.ptr(ws), _dev.stream_ptr()),
+              f'{key}_loss')
     return out, d_preds
 
 
