@@ -814,6 +814,35 @@ int raft_selfsup_loss_f32(const float *teacher, const uint8_t *teacher_visible, 
                           int W, double gamma, float weight, float eps, float upstream, const float *add_to, float *out3,
                           float *d_preds, int accumulate, double *workspace, void *stream);
 
+/* Second-order, edge-aware smoothness of the self-supervised loss and its gradient in ONE launch (csrc/smooth2_loss.hip; DESIGN.md
+ * section 24).  image1 and preds as for raft_photometric_loss_f32; image2 and the mask play no part.  s = 1/255,
+ * eps2 = eps*eps rounded once to float32, rho(d) = sqrtf(d*d + eps2) and w_i = (float)gamma^(n-i-1) are that entry's, and
+ * edge_weight and eps are the first-order term's own parameters.  For image b, prediction p = p_i, component k in {u, v}:
+ *   cx(x,y) = expf(-edge_weight * mean_c |s * (image1(x+1,y)_c - image1(x-1,y)_c)|)   for 1 <= x <= W-2 (no term otherwise)
+ *   cy(x,y) = the same along y                                                         for 1 <= y <= H-2
+ *   Dx_k(x,y) = (p(x+1,y)_k - 2*p(x,y)_k) + p(x-1,y)_k,     Dy_k likewise
+ *   sm2_i = [sum cx * rho(Dx_k) + sum cy * rho(Dy_k)] / (B*H*W*2)                      (the divisor counts ALL elements)
+ *   out2[0] = (add_to ? *add_to : 0) + smooth2_weight * sum_i w_i * sm2_i  (formed in double, rounded once; add_to may be out2);
+ *   out2[1] = sm2_{n-1}
+ * The edge weight is the central difference over two pixels (mean over the channels: ((|.| + |.|) + |.|) / 3.f).
+ * d_preds: NULL (value only), or the layout of preds.  The gradient is the adjoint written as a gather: with
+ * qx_k(x,y) = cx * (Dx_k / rho(Dx_k)), qy_k likewise, both +0 where no stencil is centred,
+ *   g_k(x,y) = ((qx_k(x-1,y) - 2*qx_k(x,y)) + qx_k(x+1,y)) + ((qy_k(x,y-1) - 2*qy_k(x,y)) + qy_k(x,y+1))
+ *   d_preds_i(x,y)_k  (= or +=)  ((upstream * smooth2_weight) * w_i) * (g_k * (float)(1.0 / (B*H*W*2)))
+ * every element touched exactly once -- stored (accumulate == 0) or added to what is there with one float32 addition
+ * (accumulate == 1); gaps of a pred_stride larger than 2*B*H*W are not touched.  Where W < 3 and H < 3 the value is add_to (or 0)
+ * and the gradient exactly zero; an affine flow has D == 0 everywhere, hence a gradient of exactly zero.
+ * Deterministic (no atomics, no memset): float64 partial records in `workspace` (raft_smooth2_loss_workspace_doubles()
+ * doubles), added in index order by a second one-workgroup launch.
+ * In this order: RAFT_E_NULL: image1, preds, out2 or workspace NULL.  RAFT_E_SHAPE: a non-positive size, B*H*W*3 of 2^31 or
+ * more, pred_stride < 2*B*H*W, gamma / smooth2_weight / edge_weight negative or not finite, eps or eps*eps (in float32) not
+ * positive and finite, upstream not finite, accumulate not 0 or 1.  RAFT_E_UNSUPPORTED: n_predictions > 64 or an odd pred_stride.
+ * RAFT_E_ALIGN: preds, d_preds or workspace not 8-byte aligned.  All checks precede the first launch. */
+int64_t raft_smooth2_loss_workspace_doubles(void);
+int raft_smooth2_loss_f32(const float *image1, const float *preds, int64_t pred_stride, int n_predictions, int B, int H, int W,
+                          double gamma, float smooth2_weight, float edge_weight, float eps, float upstream,
+                          const float *add_to, float *out2, float *d_preds, int accumulate, double *workspace, void *stream);
+
 /* The student's view (csrc/student_view.hip): the frames of a self-supervised step, and the teacher's flow
  * with its trust mask, seen through one affine map per slice.  The record of slice b maps the student's pixel indices q = (x, y)
  * to the teacher's, p = M q + o:

@@ -262,6 +262,23 @@ def ssim_sequence_loss_grad(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_w
                                              ssim_weight)[1]
 
 
+def smooth2_sequence_loss_value_and_grad(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, upstream=1.0,
+                                         census_weight=0.0, ssim_weight=0.0, smooth2_weight=0.0):
+    """``(terms, grads)`` of ``losses.Smooth2SequenceLoss``: ``ssim_sequence_loss_value_and_grad`` with the second-order smoothness
+    (DESIGN.md section 24).  With ``smooth2_weight > 0`` the second-order entry follows the photometric, census and SSIM ones on the
+    same stream and adds its share to the loss and to the gradients; ``terms`` then has ``'smoothness2'`` behind ``'smoothness'``."""
+    loss = losses.Smooth2SequenceLoss(gamma, smooth_weight, edge_weight, eps, census_weight, ssim_weight, smooth2_weight)
+    return loss.value_and_grad(y_true, y_pred, upstream)
+
+
+def smooth2_sequence_loss_grad(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, upstream=1.0,
+                               census_weight=0.0, ssim_weight=0.0, smooth2_weight=0.0):
+    """``upstream * d Smooth2SequenceLoss(...)(y_true, y_pred) / d y_pred[i]`` for every i: list of tensors shaped like the
+    predictions."""
+    return smooth2_sequence_loss_value_and_grad(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, upstream, census_weight,
+                                                ssim_weight, smooth2_weight)[1]
+
+
 def selfsup_loss_value_and_grad(teacher, preds, origin=(0, 0), teacher_visible=None, student_visible=None, gamma=0.8, weight=0.3,
                                 eps=0.001, upstream=1.0):
     """``(terms, grads)`` of ``losses.SelfSupervisionLoss`` from ONE launch: ``terms`` is ``{'loss',

@@ -8,6 +8,9 @@ and the self-supervised loss the reference does not have (DESIGN.md section 17; 
 
     PhotometricSequenceLoss(gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, census_weight=0.0)
     SSIMSequenceLoss(gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, census_weight=0.0, ssim_weight=0.0)
+    Smooth2SequenceLoss(gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, census_weight=0.0, ssim_weight=0.0,
+                        smooth2_weight=0.0)                       second-order smoothness as well (section 24)
+    smooth2_sequence_loss(y_true, y_pred, ...)                    the same as a function
     photometric_sequence_loss(y_true, y_pred, ...)                y_true = (image1, image2) or (image1, image2, mask)
     SelfSupervisionLoss(gamma=0.8, weight=0.3, eps=0.001)         student predictions on a crop against a teacher flow (section 22)
 
@@ -118,7 +121,8 @@ def _real(name, v):
 
 
 def _term_weight(name, weight):
-    """The weight of a windowed data term as its entry (raft_census_loss_f32, raft_ssim_loss_f32) checks it: finite and >= 0."""
+    """The weight of a further term as its entry (raft_census_loss_f32, raft_ssim_loss_f32, raft_smooth2_loss_f32) checks it: finite
+    and >= 0."""
     v = _real(name, weight)
     if not 0.0 <= v <= _F32_MAX:
         raise ValueError(f'{name} must be finite and >= 0, got {v!r}')
@@ -127,6 +131,7 @@ def _term_weight(name, weight):
 
 _census_weight = functools.partial(_term_weight, 'census_weight')
 _ssim_weight = functools.partial(_term_weight, 'ssim_weight')
+_smooth2_weight = functools.partial(_term_weight, 'smooth2_weight')
 
 
 def _photometric_params(gamma, smooth_weight, edge_weight, eps, upstream=1.0):
@@ -224,15 +229,18 @@ def _mask_to_device(mask, device):
 
 
 def _photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, upstream=1.0, want_grad=False, census_weight=0.0,
-                        ssim_weight=0.0):
+                        ssim_weight=0.0, smooth2_weight=0.0):
     """One raft_photometric_loss_f32 call: ``(out, d_preds)`` -- ``out`` maps 'loss', 'photometric', 'smoothness' to elements of
     one device buffer (the last two of the LAST prediction), d_preds is the stacked gradients ``(n, B, H, W, 2)`` or None.
     With ``census_weight > 0`` a raft_census_loss_f32 call follows on the same stream: it adds its term
     to the loss and its gradient to d_preds on the device, and ``out`` gains 'census'.  With ``ssim_weight > 0`` a
-    raft_ssim_loss_f32 call follows those in the same way (section 19), and ``out`` gains 'ssim'."""
+    raft_ssim_loss_f32 call follows those in the same way (section 19), and ``out`` gains 'ssim'.  With ``smooth2_weight > 0`` a
+    raft_smooth2_loss_f32 call follows all of them (section 24): the second-order smoothness, with the first-order term's
+    ``edge_weight`` and ``eps``; ``out`` gains 'smoothness2' behind 'smoothness'."""
     gamma, smooth_weight, edge_weight, eps, upstream = _photometric_params(gamma, smooth_weight, edge_weight, eps, upstream)
     census_weight = _census_weight(census_weight)
     ssim_weight = _ssim_weight(ssim_weight)
+    smooth2_weight = _smooth2_weight(smooth2_weight)
     image1, image2, mask, preds, (B, H, W) = _check_unlabelled(y_true, y_pred)
     image1 = _dev.to_device(image1).as_subclass(torch.Tensor)
     image2 = _dev.to_device(image2).as_subclass(torch.Tensor)
@@ -244,11 +252,16 @@ def _photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, 
     # launch order: (key of raft_<key>_loss_f32 / raft_<key>_loss_workspace_bytes, weight, where its add_to sits, where its out2)
     on = [(key, weight) for key, weight in (('census', census_weight), ('ssim', ssim_weight)) if weight > 0.0]
     windowed = [(key, weight, 1 + 2 * j if j else 0, 3 + 2 * j) for j, (key, weight) in enumerate(on)]
-    buf = torch.zeros((3 + 2 * len(windowed),), dtype=torch.float32, device=image1.device)
-    out = {'loss': buf[windowed[-1][3] if windowed else 0], 'photometric': buf[1]}
+    # the second-order smoothness comes last: its add_to is the loss so far, its out2 the last two elements
+    second = smooth2_weight > 0.0
+    at_loss, at_second = windowed[-1][3] if windowed else 0, 3 + 2 * len(windowed)
+    buf = torch.zeros((at_second + 2 * second,), dtype=torch.float32, device=image1.device)
+    out = {'loss': buf[at_second if second else at_loss], 'photometric': buf[1]}
     for key, _, _, at_out2 in windowed:
         out[key] = buf[at_out2 + 1]
     out['smoothness'] = buf[2]
+    if second:
+        out['smoothness2'] = buf[at_second + 1]
     if n == 0:
         return out, None
     preds = [_dev.to_device(p).as_subclass(torch.Tensor).to(torch.float32) for p in preds]
@@ -256,9 +269,10 @@ def _photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, 
     stacked = _stacked(preds, stride)
     d_preds = torch.empty((n, B, H, W, 2), dtype=torch.float32, device=image1.device) if want_grad else None
     lib = _dev.lib()
-    # one buffer for all entries: the census and SSIM launches follow the photometric ones on the stream
+    # one buffer for all entries: the census, SSIM and second-order launches follow the photometric ones on the stream
     need = max([8 * int(lib.raft_photometric_loss_workspace_doubles())]
-               + [int(getattr(lib, f'raft_{key}_loss_workspace_bytes')(n, B, H, W)) for key, _, _, _ in windowed])
+               + [int(getattr(lib, f'raft_{key}_loss_workspace_bytes')(n, B, H, W)) for key, _, _, _ in windowed]
+               + [8 * int(lib.raft_smooth2_loss_workspace_doubles()) * second])
     ws = _workspace(buf.device, need)
     check(lib.raft_photometric_loss_f32(_dev.ptr(image1), _dev.ptr(image2), _dev.ptr(mask) if mask is not None else None,
                                         _dev.ptr(stacked), stride, n, B, H, W, gamma, smooth_weight, edge_weight, eps,
@@ -271,6 +285,11 @@ def _photometric_launch(y_true, y_pred, gamma, smooth_weight, edge_weight, eps, 
                                                    _dev.ptr(buf[at_add_to:]), _dev.ptr(buf[at_out2:]),
                                                    _dev.ptr(d_preds) if want_grad else None, 1, _dev.ptr(ws), _dev.stream_ptr()),
               f'{key}_loss')
+    if second:
+        check(lib.raft_smooth2_loss_f32(_dev.ptr(image1), _dev.ptr(stacked), stride, n, B, H, W, gamma, smooth2_weight, edge_weight, eps,
+                                        upstream, _dev.ptr(buf[at_loss:]), _dev.ptr(buf[at_second:]),
+                                        _dev.ptr(d_preds) if want_grad else None, 1, _dev.ptr(ws), _dev.stream_ptr()),
+              'smooth2_loss')
     return out, d_preds
 
 
@@ -301,7 +320,7 @@ class PhotometricSequenceLoss:
 
     def terms(self, y_true, y_pred):
         """``{'loss', 'photometric', 'smoothness'}``, with ``census_weight > 0`` also ``'census'``: the loss, and the terms of the
-        LAST prediction (0-d device scalars)."""
+        LAST prediction (0-d device scalars).  (The subclasses add ``'ssim'`` and ``'smoothness2'``.)"""
         return _photometric_terms(_photometric_launch(y_true, y_pred, **self._params())[0])
 
     def __call__(self, y_true, y_pred):
@@ -328,6 +347,31 @@ class SSIMSequenceLoss(PhotometricSequenceLoss):
 
     def _params(self):
         return dict(super()._params(), ssim_weight=self.ssim_weight)
+
+
+class Smooth2SequenceLoss(SSIMSequenceLoss):
+    """``SSIMSequenceLoss`` with the edge-aware SECOND-order smoothness, the regulariser UFlow, ARFlow and
+    SMURF name: ``smooth2_weight > 0`` adds ``smooth2_weight * sm2_i`` to every prediction's term, ``sm2_i`` the Charbonnier penalty
+    of the second differences of prediction i along x and y.  It leaves an affine flow -- a zoom, a rotation, a receding ground
+    plane -- alone, where the first-order term pulls it towards a constant.  Its edge weight is the central difference of frame 1
+    over two pixels under the SAME ``edge_weight`` as the first-order term, and its penalty has the same ``eps``: a choice, not a
+    tuned value.  ``smooth_weight=0`` with ``smooth2_weight > 0`` is the second-order term alone (UFlow's KITTI setting).
+    ``smooth2_weight`` is the last keyword and has no tuned default (0 = the term is off: no launch, and the loss is the parent's bit
+    for bit); the parents keep their signatures, as ``SSIMSequenceLoss`` kept its parent's.  Nothing is claimed about accuracy on
+    real footage: nothing here was trained on any."""
+
+    def __init__(self, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, census_weight=0.0, ssim_weight=0.0, smooth2_weight=0.0):
+        super().__init__(gamma, smooth_weight, edge_weight, eps, census_weight, ssim_weight)
+        self.smooth2_weight = _smooth2_weight(smooth2_weight)
+
+    def _params(self):
+        return dict(super()._params(), smooth2_weight=self.smooth2_weight)
+
+
+def smooth2_sequence_loss(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, census_weight=0.0, ssim_weight=0.0,
+                          smooth2_weight=0.0):
+    """``Smooth2SequenceLoss(gamma, smooth_weight, edge_weight, eps, census_weight, ssim_weight, smooth2_weight)(y_true, y_pred)``."""
+    return Smooth2SequenceLoss(gamma, smooth_weight, edge_weight, eps, census_weight, ssim_weight, smooth2_weight)(y_true, y_pred)
 
 
 def photometric_sequence_loss(y_true, y_pred, gamma=0.8, smooth_weight=0.1, edge_weight=10.0, eps=0.01, census_weight=0.0):

@@ -697,7 +697,8 @@ class RAFT:
         ``end_point_error``; ``loss=losses.PhotometricSequenceLoss(...)`` makes ``train_step`` take unlabelled pairs
         ``(image1, image2)`` or ``(image1, image2, mask)`` and report ``loss`` / ``photometric`` / ``smoothness`` (DESIGN.md
         section 17; ``test_step`` still wants ground truth), and ``census`` when the loss has ``census_weight > 0`` (section 18);
-        ``losses.SSIMSequenceLoss(..., ssim_weight > 0)`` adds ``ssim`` (section 19).  ``trainable``: which weights ``train_step`` updates -- ``'all'``
+        ``losses.SSIMSequenceLoss(..., ssim_weight > 0)`` adds ``ssim`` (section 19), and
+        ``losses.Smooth2SequenceLoss(..., smooth2_weight > 0)`` ``smoothness2`` directly behind ``smoothness`` (section 24).  ``trainable``: which weights ``train_step`` updates -- ``'all'``
         (the reference's behaviour: encoders, norms and update block) or ``'update_block'`` (encoders frozen, run by the
         inference kernels).
 
@@ -786,7 +787,8 @@ class RAFT:
         """What ``train_step`` reports under a PhotometricSequenceLoss (``occluded``: in bidirectional mode; ``selfsup`` and
         ``selfsup_used``: with ``selfsup_crop``)."""
         on = [k for k in ('census', 'ssim') if getattr(self.loss, k + '_weight', 0.0) > 0]
-        return (('loss', 'photometric', *on, 'smoothness') + (('occluded',) if getattr(self, 'bidirectional', False) else ())
+        second = ('smoothness2',) if getattr(self.loss, 'smooth2_weight', 0.0) > 0 else ()
+        return (('loss', 'photometric', *on, 'smoothness', *second) + (('occluded',) if getattr(self, 'bidirectional', False) else ())
                 + (('selfsup', 'selfsup_used') if getattr(self, 'selfsup_crop', None) is not None else ()))
 
     BN_MOMENTUM = 0.99      # Keras BatchNormalization default (extractor.py:10 passes none)
