@@ -177,6 +177,7 @@ def cond(pred, true_fn, false_fn):
 def clip_by_global_norm(t_list, clip_norm):
     norm = _torch.sqrt(sum((g.double() ** 2).sum() for g in t_list)).to(float32)
     scale = clip_norm / _torch.maximum(norm, _torch.as_tensor(float(clip_norm)))
+    scale = scale + (norm - norm)       # TF (clip_ops.py): a non-finite global norm sets every entry to NaN
     return [g * scale for g in t_list], norm
 
 

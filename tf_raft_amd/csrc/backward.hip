@@ -742,7 +742,10 @@ extern "C" int raft_upsample_convex_backward_f32(const float *flow, const float 
 //                        accumulate = 1 adds to *out (the global norm runs over all gradient tensors)
 //   raft_adamw_step_f32  tensorflow-addons 0.11.1 DecoupledWeightDecayExtension + Keras Adam (TF 2.3), one tensor:
 //                          var -= weight_decay * var                  (decoupled, NOT scaled by the learning rate)
-//                          g = grad * grad_scale                      (grad_scale = clip_norm / max(global_norm, clip_norm))
+//                          g = grad * grad_scale                      (grad_scale = clip_norm / max(global_norm, clip_norm);
+//                                                                      NaN for a non-finite global_norm, as TF documents: "if
+//                                                                      global_norm == infinity then the entries in t_list are
+//                                                                      all set to NaN" -- var, m and v all become NaN)
 //                          m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2
 //                          var -= lr_t * m / (sqrt(v) + eps),  lr_t = lr sqrt(1 - b2^t) / (1 - b1^t) computed by the caller
 // ------------------------------------------------------------------------------------------------
@@ -776,6 +779,7 @@ __global__ void __launch_bounds__(256) adamw_kernel(float *__restrict__ var, con
     if (gnorm_sq) {   // tf.clip_by_global_norm: g * clip_norm / max(global_norm, clip_norm)
         const float gn = (float)sqrt(gnorm_sq[0]);
         scale = clip_norm / fmaxf(gn, clip_norm);
+        scale += gn - gn;   // TF's `scale + (use_norm - use_norm)`: inf or NaN norm -> NaN (fmaxf alone drops a NaN, inf gives 0)
     }
     const float g = grad[i] * scale;
     float w = var[i];
@@ -823,7 +827,11 @@ __global__ void __launch_bounds__(256) adamw_multi_kernel(MultiTensorArgs a, flo
     const float *grad = a.g[t];
     const int64_t n = a.n[t];
     float scale = 1.0f;
-    if (gnorm_sq) scale = clip_norm / fmaxf((float)sqrt(gnorm_sq[0]), clip_norm);
+    if (gnorm_sq) {
+        const float gn = (float)sqrt(gnorm_sq[0]);
+        scale = clip_norm / fmaxf(gn, clip_norm);
+        scale += gn - gn;   // non-finite norm -> NaN, as in adamw_kernel
+    }
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const float g = grad[i] * scale;   // the arithmetic of adamw_kernel, statement for statement
         float w = var[i];
@@ -1088,14 +1096,17 @@ extern "C" int raft_prepare_state_backward_f32(const float *net0, const float *i
 // (per sample and channel over H x W) and Keras BatchNormalization with batch statistics (per channel over B x H x W),
 // both eps = 1e-3 and biased variance.  x is viewed as (G groups, P pixels, C channels): G = B, P = H*W for instance
 // norm; G = 1, P = B*H*W for batch norm.
-//   stats     mean[g][c], rstd[g][c] = 1 / sqrt(var + eps)            (float64 partial sums over pixel slices, ordered)
+//   stats     mean[g][c], rstd[g][c] = 1 / sqrt(var + eps)            (float64 partial sums over pixel slices, ordered; the sums
+//             run over x - x0 with x0 = the group's first pixel of the channel, so E[x^2] - mean^2 does not cancel for a channel
+//             with a large mean over a small spread, and a constant channel has var = 0 and mean = x0 exactly)
 //   apply     y = (x - mean) * rstd * gamma + beta   [+ relu]
 //   backward  dx = gamma rstd (dy - mean_P(dy) - xhat mean_P(dy xhat)),  dgamma[c] = sum dy xhat,  dbeta[c] = sum dy
 // ------------------------------------------------------------------------------------------------
 namespace {
 constexpr int NORM_SLICES = 256;   // workgroups per group: batch norm has ONE group over B*H*W pixels
 
-// part[(g * NORM_SLICES + s) * C + c] = {sum a, sum b} over the slice's pixels; mode 0: (x, x^2); mode 1: (dy, dy * xhat)
+// part[(g * NORM_SLICES + s) * C + c] = {sum a, sum b} over the slice's pixels; mode 0: (x - x0, (x - x0)^2); mode 1: (dy, dy * xhat)
+// with the product in float64 (float32 products would leave 3 roundings per term in sums that mostly cancel)
 __global__ void __launch_bounds__(256) norm_partial_kernel(const float *__restrict__ x, const float *__restrict__ dy, const float *__restrict__ mean,
                                                            const float *__restrict__ rstd, int64_t P, int C, int mode,
                                                            double2 *__restrict__ part) {
@@ -1107,17 +1118,18 @@ __global__ void __launch_bounds__(256) norm_partial_kernel(const float *__restri
         const int c = c0 + cl;
         double a = 0.0, b = 0.0;
         if (c < C) {
-            const float mu = mode ? mean[(int64_t)g * C + c] : 0.f, rs = mode ? rstd[(int64_t)g * C + c] : 0.f;
+            const double mu = mode ? (double)mean[(int64_t)g * C + c] : (double)x[(int64_t)g * P * C + c];   // mode 0: the shift x0
+            const double rs = mode ? (double)rstd[(int64_t)g * C + c] : 0.0;
             for (int64_t p = lo + pr; p < hi; p += 4) {
                 const int64_t i = ((int64_t)g * P + p) * C + c;
                 if (mode == 0) {
-                    const double v = (double)x[i];
+                    const double v = (double)x[i] - mu;
                     a += v;
                     b += v * v;
                 } else {
-                    const float d = dy[i];
-                    a += (double)d;
-                    b += (double)(d * ((x[i] - mu) * rs));
+                    const double d = (double)dy[i];
+                    a += d;
+                    b += d * (((double)x[i] - mu) * rs);
                 }
             }
         }
@@ -1131,7 +1143,8 @@ __global__ void __launch_bounds__(256) norm_partial_kernel(const float *__restri
     }
 }
 
-__global__ void __launch_bounds__(256) norm_stats_final_kernel(const double2 *__restrict__ part, int G, int C, double inv_count, float eps,
+__global__ void __launch_bounds__(256) norm_stats_final_kernel(const double2 *__restrict__ part, const float *__restrict__ x, int64_t P,
+                                                               int G, int C, double inv_count, float eps,
                                                                float *__restrict__ mean, float *__restrict__ rstd, float *__restrict__ var_out) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= G * C) return;
@@ -1143,10 +1156,10 @@ __global__ void __launch_bounds__(256) norm_stats_final_kernel(const double2 *__
         a += t.x;
         b += t.y;
     }
-    const double mu = a * inv_count;
+    const double mu = a * inv_count;   // of x - x0
     double var = b * inv_count - mu * mu;
     if (var < 0.0) var = 0.0;
-    mean[i] = (float)mu;
+    mean[i] = (float)((double)x[(int64_t)g * P * C + c] + mu);
     rstd[i] = (float)(1.0 / sqrt(var + (double)eps));
     if (var_out) var_out[i] = (float)var;
 }
@@ -1224,7 +1237,7 @@ extern "C" int raft_norm_forward_f32(const float *x, int G, int64_t P, int C, co
     hipStream_t s = (hipStream_t)stream;
     norm_partial_kernel<<<G * NORM_SLICES, 256, 0, s>>>(x, nullptr, nullptr, nullptr, P, C, 0, (double2 *)workspace);
     RAFT_TRY(raft_launch_status());
-    norm_stats_final_kernel<<<raft_ceil_div((int64_t)G * C, 256), 256, 0, s>>>((const double2 *)workspace, G, C, 1.0 / (double)P, eps, mean, rstd, var);
+    norm_stats_final_kernel<<<raft_ceil_div((int64_t)G * C, 256), 256, 0, s>>>((const double2 *)workspace, x, P, G, C, 1.0 / (double)P, eps, mean, rstd, var);
     RAFT_TRY(raft_launch_status());
     const int64_t total = (int64_t)G * P * C;
     norm_apply_kernel<<<raft_ceil_div(total, 256), 256, 0, s>>>(x, mean, rstd, gamma, beta, P, C, relu, total, y);

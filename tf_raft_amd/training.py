@@ -82,7 +82,9 @@ class AdamW:
     def apply_gradients(self, grads, variables, clip_norm=None):
         """``variables`` / ``grads``: dicts name -> fp32 device tensor (variables are updated in place).  ``clip_norm``:
         ``tf.clip_by_global_norm`` (reference model.py:134) folded into the update kernel.  All tensors go through
-        ``raft_adamw_step_multi_f32``: one launch per 64 tensors."""
+        ``raft_adamw_step_multi_f32``: one launch per 64 tensors.  A non-finite global norm (one ``inf`` or ``nan`` in any
+        gradient) follows TensorFlow's documented rule: every entry of every clipped gradient is NaN, so every variable and
+        both slots of it are NaN after the step -- the step never continues silently on weight decay or unclipped gradients."""
         lib = _dev.lib()
         t = self.iterations + 1
         lr = self._lr()
