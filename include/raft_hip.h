@@ -344,6 +344,43 @@ int raft_flow_range_occlusion_f32(const float *flow_a, const float *flow_b, uint
 int raft_flow_range_visibility_f32(const float *flows, const uint8_t *mask, uint8_t *visible, float *occluded_fraction, int N, int H,
                                    int W, float threshold, int apply, void *workspace, double *records, void *stream);
 
+/* The forward splat of FRAMES along a flow, and the frame in between two frames: the accumulator above
+ * carried over to colour.  Frames are (N, H, W, C) with C in 1 .. 4, uint8 or float32 on 0 .. 255; flows (N, H, W, 2) float32.
+ * The source pixel at integer (x, y) of slice n with vector (u, v) and time t lands on sx = float(x) + t * u, sy = float(y) + t * v
+ * (one float32 multiplication, then one float32 addition, never fused).  It contributes iff -1 < sx < float(W) and
+ * -1 < sy < float(H) (a NaN, an infinity or 1e30 fails) and, with a non-NULL uint8 mask (N, H, W), mask[n, y, x] != 0.  The
+ * corners and their integer weights w are the range map's.  Every destination pixel holds C + 1 uint64 sums: W += w and
+ * S_c += w * q_c, with q_c the byte of a uint8 frame or (int)rintf(fminf(fmaxf(value, 0), 255) * 256) of a float32 one (a NaN
+ * gives 0).  Integer sums: every entry repeats bit for bit, whatever the order of the adds.
+ *   raft_splat_frames_*: dst[n, y, x, c] = float(double(S_c) / double(W)) (times 1 / 256 for float32 frames, before the cast), 0
+ *     where W == 0; weight (N, H, W), if not NULL, = float(double(W) * 2^-24): at t = 1 the flow's range map.  t must be finite.
+ *   raft_interpolate_frames_*: image1 is splatted to t along flow_forward (slices 0 .. N - 1 of the sums) and image2 to
+ *     s = 1.0f - t along flow_backward (slices N .. 2N - 1) by ONE scatter launch; then per pixel, in float64 and never fused,
+ *     td = t, a = (1 - td) * W1, b = td * W2, den = a + b and
+ *         den > 0:   out_c = ((1 - td) * S1_c + td * S2_c) / den
+ *         otherwise: out_c = (1 - td) * q1_c + td * q2_c on the pixel's own two quantised values, a HOLE: holes[n, y, x] = 1
+ *     (holes: uint8 (N, H, W), 0 elsewhere; may be NULL).  Float32 frames are multiplied by 1 / 256 at the end; a float32 dst
+ *     is the cast of out_c, a uint8 dst is (uint8)fmin(rint(out_c), 255).  0 <= t <= 1; mask1 / mask2 may each be NULL.
+ * `workspace` holds the sums: raft_frame_splat_workspace_bytes(slices, H, W, C) = slices * H * W * (C + 1) * 8 bytes, 8-byte
+ * aligned, zeroed by the entry itself, with slices = N for a splat and 2N for an interpolation (0: the sizes are refused).
+ * Errors, in this order: RAFT_E_NULL for a NULL required pointer; RAFT_E_SHAPE for a non-positive size, C outside 1 .. 4,
+ * H * W above 2^24, slices * H * W * 4 of 2^31 or more, a t that is not finite (splat) or outside [0, 1] or NaN (interpolate);
+ * RAFT_E_ALIGN for a flow or a workspace that is not 8-byte aligned.  All checks precede the first launch. */
+int64_t raft_frame_splat_workspace_bytes(int slices, int H, int W, int C);
+int raft_splat_frames_f32(const float *src, const float *flow, const uint8_t *mask, float t, float *dst, float *weight, int N, int H,
+                          int W, int C, void *workspace, void *stream);
+int raft_splat_frames_u8_f32(const uint8_t *src, const float *flow, const uint8_t *mask, float t, float *dst, float *weight, int N, int H,
+                             int W, int C, void *workspace, void *stream);
+int raft_interpolate_frames_f32(const float *image1, const float *image2, const float *flow_forward, const float *flow_backward,
+                                const uint8_t *mask1, const uint8_t *mask2, float t, float *dst, uint8_t *holes, int N, int H, int W, int C,
+                                void *workspace, void *stream);
+int raft_interpolate_frames_u8_f32(const uint8_t *image1, const uint8_t *image2, const float *flow_forward, const float *flow_backward,
+                                   const uint8_t *mask1, const uint8_t *mask2, float t, float *dst, uint8_t *holes, int N, int H, int W,
+                                   int C, void *workspace, void *stream);
+int raft_interpolate_frames_u8(const uint8_t *image1, const uint8_t *image2, const float *flow_forward, const float *flow_backward,
+                               const uint8_t *mask1, const uint8_t *mask2, float t, uint8_t *dst, uint8_t *holes, int N, int H, int W,
+                               int C, void *workspace, void *stream);
+
 /* ------------------------------------------------------------------ training augmentation */
 
 /* FlowAugmentor (reference tf_raft/datasets/augmentor.py:9-129, used at dataset.py:87-91) composed into one gather (the sparse

@@ -30,12 +30,11 @@
 
 #include "flow_sample.h"      // flow_taps: the in-frame test of a pixel's own vector
 #include "loss_common.h"      // the deterministic reduction of raft_flow_range_visibility_f32's count
+#include "splat_geometry.h"   // splat_taps: the in-range test and the four integer weights, shared with frame_splat.hip
 
 namespace {
 
 constexpr int kSplatThreads = 256;
-constexpr int kRangeShift = 12;                              // a bilinear weight per axis in 1 / 4096
-constexpr int kRangeOne = 1 << kRangeShift;
 constexpr int64_t kRangeMaxPixels = (int64_t)1 << 28;        // double(acc) * 2^-24 stays exact: acc <= H * W * 2^24 <= 2^52
 constexpr int kRangeColumns = 64;                            // the records are summed as rows of 64, as flow_check.hip's are
 
@@ -71,18 +70,15 @@ __global__ void __launch_bounds__(kSplatThreads) range_scatter_kernel(const floa
                 if (x >= W || y >= H) continue;
                 const float2 f = src[y * W + x];
                 const float sx = (float)x + f.x, sy = (float)y + f.y;
-                if (!(sx > -1.f && sx < fW && sy > -1.f && sy < fH)) continue;      // (a NaN fails)
-                const float fx = floorf(sx), fy = floorf(sy);
-                const int x0 = (int)fx, y0 = (int)fy;                               // -1 .. W - 1, -1 .. H - 1
-                const int qa = (int)rintf((sx - fx) * (float)kRangeOne), qb = (int)rintf((sy - fy) * (float)kRangeOne);
-                const unsigned wx[2] = {(unsigned)(kRangeOne - qa), (unsigned)qa}, wy[2] = {(unsigned)(kRangeOne - qb), (unsigned)qb};
+                const SplatTaps g = splat_taps(sx, sy, fW, fH);                     // the in-range test and the weights (splat_geometry.h)
+                if (!g.in) continue;
 #pragma unroll
                 for (int dy = 0; dy < 2; ++dy) {
-                    const int cy = y0 + dy;
+                    const int cy = g.y0 + dy;
 #pragma unroll
                     for (int dx = 0; dx < 2; ++dx) {
-                        const int cx = x0 + dx;
-                        const unsigned w = wx[dx] * wy[dy];                         // <= 2^24
+                        const int cx = g.x0 + dx;
+                        const unsigned w = g.wx[dx] * g.wy[dy];                     // <= 2^24
                         if (w == 0u || cx < 0 || cx >= W || cy < 0 || cy >= H) continue;
                         const int lx = cx - ox, ly = cy - oy;
                         if ((unsigned)lx < (unsigned)kWinW && (unsigned)ly < (unsigned)kWinH)

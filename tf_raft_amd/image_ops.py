@@ -36,6 +36,10 @@ training step: the 2N flows of the doubled batch in, the 
 vector splatted forward with integer bilinear weights, a pixel that receives too little is occluded (``raft_flow_range_*``,
 tf_raft_amd/csrc/flow_splat.hip); ``range_visibility_launch`` is its in-step form.
 
+``splat`` / ``interpolate`` carry FRAMES forward along a flow: the range map's integer accumulator with
+``C + 1`` sums per pixel, for uint8 frames and float32 frames on 0 .. 255, and the frame at a time ``t`` between two frames from
+both flows of a bidirectional prediction (``raft_splat_frames_*`` / ``raft_interpolate_frames_*``, tf_raft_amd/csrc/frame_splat.hip).
+
 ``forward_interpolate`` projects a low-resolution flow forward along itself: the start of the next pair's
 recurrence in a video stream (``raft_forward_interpolate_f32``, tf_raft_amd/csrc/flow_init.hip; ``tf_raft_amd.video``).
 
@@ -898,6 +902,229 @@ def range_occlusion(flow_forward, flow_backward, threshold=RANGE_THRESHOLD):
     b = _flow_like(flow_backward, t.shape[:-1], 'range_occlusion')
     occ_f, occ_b = range_occlusion_launch(f4, b.reshape(f4.shape), threshold)
     return _dev.wrap(occ_f.view(t.shape[:-1])), _dev.wrap(occ_b.view(t.shape[:-1]))
+
+
+# ------------------------------------------------------------------------------------------ forward splat of frames, the frame in between
+FRAME_SPLAT_MAX_PIXELS = 1 << 24      # csrc/frame_splat.hip kFrameMaxPixels: every uint64 sum stays below 2^64
+FRAME_SPLAT_MAX_CHANNELS = 4
+
+
+def check_splat_time(t, unit=False):
+    """A splat's time as a float: a number (no bool) whose float32 value is finite (``unit``: lies in ``[0, 1]``)."""
+    if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, float, np.integer, np.floating)):
+        raise ValueError(f't must be a number, got {t!r}')
+    try:
+        with np.errstate(over='ignore'):
+            v = float(np.float32(t))
+    except OverflowError:
+        v = float('inf')
+    if not np.isfinite(v) or (unit and not 0.0 <= v <= 1.0):
+        raise ValueError(f't must {"lie in [0, 1]" if unit else "be finite"} as a float32, got {t!r}')
+    return v
+
+
+def _check_frame_sizes(slices, H, W, C, what):
+    if not 1 <= C <= FRAME_SPLAT_MAX_CHANNELS:
+        raise ValueError(f'{what} takes frames of 1 to {FRAME_SPLAT_MAX_CHANNELS} channels, got {C}')
+    if H * W > FRAME_SPLAT_MAX_PIXELS or slices * H * W * FRAME_SPLAT_MAX_CHANNELS >= 1 << 31:
+        raise ValueError(f'{what} takes frames of up to 2^24 pixels and fewer than 2^29 pixels in all, got {slices} x {H} x {W}: too large')
+
+
+def _shape_and_type(x, what):
+    """Shape and torch type of a NumPy / torch argument as ``_on_device`` will deliver it, read without touching a device."""
+    if isinstance(x, torch.Tensor):
+        return tuple(x.shape), (torch.float32 if x.dtype == torch.float64 else x.dtype)
+    a = x if isinstance(x, np.ndarray) else np.asarray(x)
+    kinds = {np.dtype(np.uint8): torch.uint8, np.dtype(np.bool_): torch.bool, np.dtype(np.float32): torch.float32,
+             np.dtype(np.float64): torch.float32}
+    if a.dtype not in kinds:
+        raise TypeError(f'{what}: unsupported type {a.dtype}')
+    return tuple(a.shape), kinds[a.dtype]
+
+
+def _check_frames_flow_mask(frames, flow, mask, what):
+    """``(N, H, W, C)`` uint8 / float32 frames, their flow ``(N, H, W, 2)`` and an optional uint8 mask ``(N, H, W)``: plain
+    contiguous tensors of one device."""
+    if frames.dim() != 4:
+        raise ValueError(f'{what}: expected frames (N, H, W, C), got {tuple(frames.shape)}')
+    if frames.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f'{what} takes uint8 or float32 frames, got {frames.dtype}')
+    N, H, W, Cn = frames.shape
+    if tuple(flow.shape) != (N, H, W, 2) or flow.device != frames.device:
+        raise ValueError(f'frames {tuple(frames.shape)} on {frames.device} need a flow {(N, H, W, 2)}, got {tuple(flow.shape)} on {flow.device}')
+    _check_flow(flow, what)
+    if not frames.is_contiguous():
+        raise ValueError(f'{what}: the frames must be contiguous, got strides {tuple(frames.stride())} for {tuple(frames.shape)}')
+    if mask is not None:
+        _check_out(mask, (N, H, W), torch.uint8, frames.device)
+
+
+def _frame_workspace(device, slices, H, W, C):
+    """The uint64 sums of ``slices`` frames of ``C`` channels in the stream's grow-only workspace."""
+    from . import losses
+    nbytes = int(_dev.lib().raft_frame_splat_workspace_bytes(int(slices), int(H), int(W), int(C)))
+    if nbytes <= 0:
+        raise ValueError(f'a frame splat takes frames of up to 2^24 pixels and 1 to 4 channels, got {slices} x {H} x {W} x {C}: too large')
+    return losses._workspace(device, nbytes)
+
+
+def frame_splat_launch(frames: torch.Tensor, flow: torch.Tensor, t: float = 1.0, mask=None, want_weight: bool = False, out=None):
+    """The launches themselves (``raft_splat_frames_*``): contiguous device frames ``(N, H, W, C)`` of
+    uint8 / float32, their contiguous float32 flow ``(N, H, W, 2)`` and an optional contiguous uint8 ``mask`` ``(N, H, W)`` ->
+    ``(splatted, weight)`` on the CURRENT stream (plain tensors): float32 ``(N, H, W, C)`` (``out`` when given) and float32
+    ``(N, H, W)`` (None without ``want_weight``)."""
+    t = check_splat_time(t)
+    _check_frames_flow_mask(frames, flow, mask, 'splat')
+    N, H, W, Cn = frames.shape
+    _check_frame_sizes(N, H, W, Cn, 'splat')
+    fn, src = _source_entry(frames, 'splat_frames')
+    out = _check_out(out, (N, H, W, Cn), torch.float32, frames.device)
+    weight = torch.empty((N, H, W), device=frames.device, dtype=torch.float32) if want_weight else None
+    with torch.cuda.device(frames.device):
+        ws = _frame_workspace(frames.device, N, H, W, Cn)
+        check(fn(_dev.ptr(src), _dev.ptr(flow), _dev.ptr(mask) if mask is not None else None, t, _dev.ptr(out),
+                 _dev.ptr(weight) if weight is not None else None, N, H, W, Cn, _dev.ptr(ws), _dev.stream_ptr()), 'splat_frames')
+    return out, weight
+
+
+def _interpolate_entry(in_dtype, dtype):
+    """The entry's name and the result's type for frames of ``in_dtype`` and the result type asked for (None: float32)."""
+    if in_dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f'interpolate takes uint8 or float32 frames, got {in_dtype}')
+    if dtype in (None, torch.float32):
+        return ('raft_interpolate_frames_f32' if in_dtype == torch.float32 else 'raft_interpolate_frames_u8_f32'), torch.float32
+    if dtype == torch.uint8 and in_dtype == torch.uint8:
+        return 'raft_interpolate_frames_u8', torch.uint8
+    raise TypeError(f'interpolate returns float32, or uint8 for uint8 frames, got {in_dtype} -> {dtype}')
+
+
+def interpolate_launch(image1: torch.Tensor, image2: torch.Tensor, flow_forward: torch.Tensor, flow_backward: torch.Tensor,
+                       t: float = 0.5, mask1=None, mask2=None, want_holes: bool = False, dtype=None, out=None, holes=None):
+    """The launches themselves (``raft_interpolate_frames_*``): two contiguous device frame batches
+    ``(N, H, W, C)`` of one type (uint8 / float32), the contiguous float32 flows ``(N, H, W, 2)`` from frame 1 to frame 2 and
+    back, optional contiguous uint8 masks ``(N, H, W)`` (non-zero = this pixel is splatted) -> ``(frame, holes)`` on the CURRENT
+    stream (plain tensors): the frame at time ``t`` in ``[0, 1]``, ``(N, H, W, C)`` of ``dtype`` (float32, or uint8 for uint8
+    frames; written into ``out`` when given), and the uint8 map ``(N, H, W)`` of the pixels nothing landed on (None without
+    ``want_holes``; ``holes``: a tensor to write it into)."""
+    t = check_splat_time(t, unit=True)
+    _check_frames_flow_mask(image1, flow_forward, mask1, 'interpolate')
+    _check_frames_flow_mask(image2, flow_backward, mask2, 'interpolate')
+    if image1.shape != image2.shape or image1.dtype != image2.dtype or image1.device != image2.device:
+        raise ValueError(f'expected two frame batches of one shape, type and device, got {tuple(image1.shape)} {image1.dtype} on '
+                         f'{image1.device} / {tuple(image2.shape)} {image2.dtype} on {image2.device}')
+    name, out_dtype = _interpolate_entry(image1.dtype, dtype)
+    N, H, W, Cn = image1.shape
+    _check_frame_sizes(2 * N, H, W, Cn, 'interpolate')
+    out = _check_out(out, (N, H, W, Cn), out_dtype, image1.device)
+    holes = _check_out(holes, (N, H, W), torch.uint8, image1.device, alloc=bool(want_holes))
+    with torch.cuda.device(image1.device):
+        ws = _frame_workspace(image1.device, 2 * N, H, W, Cn)
+        check(getattr(_dev.lib(), name)(_dev.ptr(image1), _dev.ptr(image2), _dev.ptr(flow_forward), _dev.ptr(flow_backward),
+                                        _dev.ptr(mask1) if mask1 is not None else None, _dev.ptr(mask2) if mask2 is not None else None,
+                                        t, _dev.ptr(out), _dev.ptr(holes) if holes is not None else None, N, H, W, Cn, _dev.ptr(ws),
+                                        _dev.stream_ptr()), 'interpolate_frames')
+    return out, holes
+
+
+def _frames_ahead(x, what):
+    """Shape and type of a frames argument ``(H, W, C)`` / ``(N, H, W, C)``, checked before anything reaches a device."""
+    shape, dtype = _shape_and_type(x, what)
+    if len(shape) not in (3, 4):
+        raise ValueError(f'{what} expects (H, W, C) or (N, H, W, C), got {shape}')
+    if 0 in shape:
+        raise ValueError(f'empty input {shape}')
+    if dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f'{what} takes uint8 or float32 frames, got {dtype}')
+    return shape, dtype
+
+
+def _flow_ahead(flow, lead_shape, what):
+    shape, dtype = _shape_and_type(flow, what)
+    if shape != tuple(lead_shape) + (2,):
+        raise ValueError(f'{what} expects a flow {tuple(lead_shape) + (2,)}, got {shape}')
+    if dtype != torch.float32:
+        raise TypeError(f'a flow is float32, got {dtype}')
+
+
+def _mask_ahead(mask, lead_shape, what):
+    if mask is None:
+        return
+    shape, dtype = _shape_and_type(mask, what)
+    if shape != tuple(lead_shape):
+        raise ValueError(f'{what} expects a mask {tuple(lead_shape)}, got {shape}')
+    if dtype not in (torch.uint8, torch.bool):
+        raise TypeError(f'a mask is uint8 or bool, got {dtype}')
+
+
+def _mask_on_device(mask, shape3):
+    return None if mask is None else _on_device(mask).view(torch.uint8).reshape(shape3)
+
+
+def splat(frames, flow, t=1.0, mask=None, return_weight=False):
+    """Forward splat: ``(H, W, C)`` or ``(N, H, W, C)`` frames (NumPy or torch, host or device, uint8, or
+    float32 on 0 .. 255; float64 narrows; 1 to 4 channels) carried along ``flow`` (same leading shape, 2 channels, float32) to
+    time ``t`` -> a contiguous float32 device tensor of the frames' shape: every pixel travels to ``(x + t * u, y + t * v)`` and
+    hands its value to the four pixels around that point with bilinear weights; the result is the weighted mean of what landed,
+    0 where nothing did.  ``return_weight=True`` also returns how much landed, float32 ``(..., H, W)``: at ``t = 1`` the flow's
+    ``range_map``.  ``mask`` (uint8 / bool, the frames' leading shape): only pixels where it is non-zero travel.  Weights are
+    quantised to 1 / 4096 per axis, float32 values to 1 / 256 (and clamped to 0 .. 255), and everything is summed as integers:
+    the result does not depend on the order of the adds and repeats bit for bit.  A vector that ends outside ``(-1, W) x (-1, H)``
+    or is not finite contributes nothing."""
+    t = check_splat_time(t)
+    shape, _ = _frames_ahead(frames, 'splat')
+    _flow_ahead(flow, shape[:-1], 'splat')
+    _mask_ahead(mask, shape[:-1], 'splat')
+    shape4 = ((1,) + shape) if len(shape) == 3 else shape
+    _check_frame_sizes(shape4[0], shape4[1], shape4[2], shape4[3], 'splat')
+    x = _on_device(frames).reshape(shape4)
+    f = _on_device(flow).reshape(shape4[:3] + (2,))
+    out, weight = frame_splat_launch(x, f, t, _mask_on_device(mask, shape4[:3]), return_weight)
+    out = _dev.wrap(out.view(shape))
+    return (out, _dev.wrap(weight.view(shape[:-1]))) if return_weight else out
+
+
+def _times(t):
+    """``t`` of ``interpolate``: ``(list of checked floats, whether a sequence was given)``."""
+    if isinstance(t, (list, tuple, np.ndarray)) and np.ndim(t) == 1:
+        if len(t) == 0:
+            raise ValueError('t must not be empty')
+        return [check_splat_time(v, unit=True) for v in (t.tolist() if isinstance(t, np.ndarray) else t)], True
+    return [check_splat_time(t, unit=True)], False
+
+
+def interpolate(image1, image2, flow_forward, flow_backward, t=0.5, mask1=None, mask2=None, return_holes=False, dtype=None):
+    """The frame at time ``t`` between two frames: ``(H, W, C)`` or ``(N, H, W, C)`` frames of one type
+    (NumPy or torch, host or device, uint8, or float32 on 0 .. 255; 1 to 4 channels), the flow from frame 1 to frame 2 and the flow
+    back (float32, the frames' leading shape) -> a contiguous device tensor of the frames' shape, float32 or -- ``dtype=
+    torch.uint8``, for uint8 frames only -- uint8.  Frame 1 is splatted forward to ``t`` along ``flow_forward`` and frame 2 to
+    ``1 - t`` along ``flow_backward`` (``splat``), and every pixel is the mean of what landed on it, frame 1's share weighted by
+    ``1 - t`` and frame 2's by ``t``.  A pixel nothing landed on is a hole: it takes the cross-fade ``(1 - t) * image1 + t *
+    image2`` of its own two values; ``return_holes=True`` also returns their uint8 map ``(..., H, W)``.  ``mask1`` / ``mask2``
+    (uint8 / bool): only pixels where the mask is non-zero are splatted, e.g. ``occluded == 0`` of a bidirectional prediction.
+    ``t`` in ``[0, 1]`` may be a sequence: the result then has a leading axis of that length (one pair of launches per time).
+    Integer sums: the result repeats bit for bit."""
+    times, many = _times(t)
+    shape, in_dtype = _frames_ahead(image1, 'interpolate')
+    shape2, in_dtype2 = _frames_ahead(image2, 'interpolate')
+    if shape2 != shape or in_dtype2 != in_dtype:
+        raise ValueError(f'expected two frames of one shape and type, got {shape} {in_dtype} / {shape2} {in_dtype2}')
+    _, out_dtype = _interpolate_entry(in_dtype, dtype)
+    _flow_ahead(flow_forward, shape[:-1], 'interpolate')
+    _flow_ahead(flow_backward, shape[:-1], 'interpolate')
+    _mask_ahead(mask1, shape[:-1], 'interpolate')
+    _mask_ahead(mask2, shape[:-1], 'interpolate')
+    shape4 = ((1,) + shape) if len(shape) == 3 else shape
+    _check_frame_sizes(2 * shape4[0], shape4[1], shape4[2], shape4[3], 'interpolate')
+    i1, i2 = _on_device(image1).reshape(shape4), _on_device(image2).reshape(shape4)
+    ff, fb = _on_device(flow_forward).reshape(shape4[:3] + (2,)), _on_device(flow_backward).reshape(shape4[:3] + (2,))
+    m1, m2 = _mask_on_device(mask1, shape4[:3]), _mask_on_device(mask2, shape4[:3])
+    out = torch.empty((len(times),) + shape4, device=i1.device, dtype=out_dtype)
+    holes = torch.empty((len(times),) + shape4[:3], device=i1.device, dtype=torch.uint8) if return_holes else None
+    for k, tk in enumerate(times):
+        interpolate_launch(i1, i2, ff, fb, tk, m1, m2, return_holes, out_dtype, out[k], holes[k] if return_holes else None)
+    lead = (len(times),) if many else ()
+    res = _dev.wrap(out.view(lead + shape))
+    return (res, _dev.wrap(holes.view(lead + shape[:-1]))) if return_holes else res
 
 
 # ------------------------------------------------------------------------------------------ forward projection of a flow

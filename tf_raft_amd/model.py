@@ -612,6 +612,75 @@ class RAFT:
             raise ValueError('predict_bidirectional() received no batches')
         return BidirectionalFlow(*(np.concatenate(acc, axis=0) for acc in parts))
 
+    def interpolate_step(self, data, t=0.5, skip_occluded=False, **occlusion):
+        """The frame at time ``t`` between ``data = (image1, image2)``: one ``predict_step_bidirectional``
+        pass (``**occlusion``: its ``alpha``, ``beta``, ``occlusion_test``, ``range_threshold``), then ``image_ops.interpolate_launch``
+        on the RETURNED flows and the caller's own frames, at the frames' own size -- so it works with every ``target_size`` /
+        ``fit``.  Returns a device tensor ``(N, H, W, 3)``, uint8 for uint8 frames and float32 otherwise; ``t`` in ``[0, 1]`` may be
+        a sequence, the result is then ``(T, N, H, W, 3)`` from ONE forward pass.  ``skip_occluded=True`` splats only the pixels
+        the occlusion test trusts (``occluded_* == 0`` as ``mask1`` / ``mask2``); the default splats every pixel, which is a
+        choice, not a tuned value: random weights and no footage say nothing about which looks better."""
+        times, many = image_ops._times(t)
+        unknown = set(occlusion) - {'alpha', 'beta', 'occlusion_test', 'range_threshold'}
+        if unknown:
+            raise TypeError(f'interpolate_step() got unexpected keyword arguments {sorted(unknown)}')
+        image1, image2, *_ = data
+        shape, in_dtype = image_ops._frames_ahead(image1, 'interpolate_step')
+        shape2, in_dtype2 = image_ops._frames_ahead(image2, 'interpolate_step')
+        if len(shape) != 4 or shape2 != shape or in_dtype2 != in_dtype:
+            raise ValueError(f'expected two frame batches (N, H, W, 3) of one type, got {shape} {in_dtype} / {shape2} {in_dtype2}')
+        image_ops._check_frame_sizes(2 * shape[0], shape[1], shape[2], shape[3], 'interpolate_step')
+        i1, i2 = image_ops._on_device(image1), image_ops._on_device(image2)
+        res = self.predict_step_bidirectional((i1, i2), **occlusion)
+        fwd, bwd = res.forward.as_subclass(torch.Tensor), res.backward.as_subclass(torch.Tensor)
+        m1 = m2 = None
+        if skip_occluded:
+            m1 = (res.occluded_forward.as_subclass(torch.Tensor) == 0).view(torch.uint8)
+            m2 = (res.occluded_backward.as_subclass(torch.Tensor) == 0).view(torch.uint8)
+        out = torch.empty((len(times),) + tuple(i1.shape), device=i1.device, dtype=in_dtype)
+        for k, tk in enumerate(times):
+            image_ops.interpolate_launch(i1, i2, fwd, bwd, tk, m1, m2, dtype=in_dtype, out=out[k])
+        return _dev.wrap(out if many else out[0])
+
+    def predict_interpolated(self, x, t=0.5, batch_size=None, steps=None, skip_occluded=False, **occlusion):
+        """``interpolate_step`` over all pairs of ``x`` (as for ``predict_bidirectional()``) as one host array ``(N, H, W, 3)``, or
+        ``(T, N, H, W, 3)`` for a sequence of ``t``; uint8 for uint8 frames.  Host batches are uploaded one batch ahead of the
+        compute stream (``tf_raft_amd.prefetch``); every batch's frames are copied back synchronously."""
+        from .prefetch import prefetch_to_device
+        _, many = image_ops._times(t)
+        dev = _dev.require_gpu()
+        batches, _ = self._pair_batches(x, batch_size, steps)
+        parts = []
+        for image1, image2 in prefetch_to_device(batches, buffer_size=1, device=dev):
+            parts.append(self.interpolate_step((image1, image2), t, skip_occluded, **occlusion).as_subclass(torch.Tensor).cpu().numpy())
+        if not parts:
+            raise ValueError('predict_interpolated() received no batches')
+        return np.concatenate(parts, axis=1 if many else 0)
+
+    def interpolate_video(self, frames, factor=2, batch_size=None):
+        """One video ``(T, H, W, 3)``, host or device, at ``factor`` times its frame rate: a host array ``((T - 1) * factor + 1, H,
+        W, 3)`` of the frames' type (uint8, else float32) with the original frames verbatim at every ``factor``-th index and
+        ``factor - 1`` frames synthesised between neighbours at ``t = k / factor`` (``interpolate_step``, ``batch_size``
+        consecutive pairs per call, default 4)."""
+        shape = tuple(frames.shape) if hasattr(frames, 'shape') else np.shape(frames)
+        if len(shape) != 4 or shape[-1] != 3:
+            raise ValueError(f'frames must be one video (T, H, W, 3), got {shape}')
+        if shape[0] < 2:
+            raise ValueError(f'a video needs at least two frames, got T = {shape[0]}')
+        if isinstance(factor, (bool, np.bool_)) or not isinstance(factor, (int, np.integer)) or factor < 1:
+            raise ValueError(f'factor must be an integer >= 1, got {factor!r}')
+        factor = int(factor)
+        host = frames.detach().cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
+        if host.dtype != np.uint8:
+            host = host.astype(np.float32, copy=False)
+        out = np.empty(((shape[0] - 1) * factor + 1,) + shape[1:], host.dtype)
+        out[::factor] = host
+        if factor > 1:
+            mid = self.predict_interpolated([host[:-1], host[1:]], [k / factor for k in range(1, factor)], batch_size or 4)
+            for k in range(1, factor):
+                out[k::factor] = mid[k - 1]
+        return out
+
     def video(self, warm_start=False):
         """A stream of consecutive frames (``tf_raft_amd.video.FlowVideo``): ``push(frames)`` returns the flow from the previous
         frames to these, with the feature encoder run once per frame; ``warm_start=True`` starts every pair's recurrence from the
