@@ -381,6 +381,29 @@ int raft_interpolate_frames_u8(const uint8_t *image1, const uint8_t *image2, con
                                const uint8_t *mask1, const uint8_t *mask2, float t, uint8_t *dst, uint8_t *holes, int N, int H, int W,
                                int C, void *workspace, void *stream);
 
+/* Following points through a video: the flows of S consecutive frame pairs of N videos chained at
+ * sub-pixel positions by ONE launch.  pos_in (N, P, 2) floats, (x, y) in pixels of the frames; lost_in uint8 (N, P) or NULL (all
+ * 0); flow_forward (S, N, H, W, 2), the flows frame t0 + s -> t0 + s + 1; flow_backward the same shape for t0 + s + 1 -> t0 + s,
+ * or NULL (no consistency test); pos_out (S, N, P, 2) and lost_out uint8 (S, N, P): the state after every step; start int32
+ * (N, P) or NULL: a point with start > t0 + s is copied through step s untouched (a query point given at a later frame).
+ * Codes in lost: 0 = tracked, 1 = left the frame, 2 = failed the consistency test; any nonzero code is sticky, the point keeps
+ * the position it was last tracked at and its code, bit for bit.  One step of a tracked point at (x, y), with the sample of the
+ * warp entries above (in frame iff 0 <= sx <= W - 1 and 0 <= sy <= H - 1, a NaN fails; bilinear, every operation rounded on its
+ * own):
+ *     (x, y) out of frame: code 1.  f = flow_forward[s, n] sampled at (x, y); qx = x + f.x, qy = y + f.y, ONE float32 addition
+ *     each; (qx, qy) out of frame: code 1.  With a flow_backward, b = flow_backward[s, n] sampled at (qx, qy), and
+ *     !(|f + b|^2 <= alpha * (|f|^2 + |b|^2) + beta), raft_flow_consistency_f32's comparison in its operation order (one device
+ *     function serves both): code 2.  Otherwise the point moves to (qx, qy).
+ * One thread per point and no atomics: a thread reads its own point first and touches no other, so pos_out + (S - 1) * N * P * 2
+ * == pos_in and lost_out + (S - 1) * N * P == lost_in are allowed (the in-place streaming step with S = 1); no other overlap is.
+ * Errors, in this order: RAFT_E_NULL for a NULL pos_in, flow_forward, pos_out or lost_out; RAFT_E_SHAPE for a non-positive size,
+ * a negative t0, S * N * H * W * 2 or S * N * P * 2 of 2^31 elements or more, a negative or non-finite alpha or beta (checked
+ * with and without a flow_backward); RAFT_E_ALIGN for a pos_in, pos_out or flow that is not 8-byte aligned (read and written as
+ * float2).  All checks precede the launch. */
+int raft_track_points_f32(const float *pos_in, const uint8_t *lost_in, const int32_t *start, int t0, const float *flow_forward,
+                          const float *flow_backward, float *pos_out, uint8_t *lost_out, int S, int N, int64_t P, int H, int W,
+                          float alpha, float beta, void *stream);
+
 /* ------------------------------------------------------------------ training augmentation */
 
 /* FlowAugmentor (reference tf_raft/datasets/augmentor.py:9-129, used at dataset.py:87-91) composed into one gather (the sparse

@@ -70,30 +70,15 @@ __global__ void __launch_bounds__(kFlowCheckThreads) warp_kernel(const S *__rest
     }
 }
 
-struct alignas(8) FlowPair {
-    float2 lo, hi;               // two neighbouring vectors of a row, read as one 16-byte load
-};
-
 // One pixel of the test: the image's own flow vector f at (x, y) against `other` (the other direction's flow of the same image).
-// PAIR: the two taps of a row are neighbours in memory and come as ONE 16-byte load from the first of them (from the one before
-// where the first is the row's last pixel, whose right neighbour is itself); needs W >= 2.
+// PAIR: the two taps of a row come as ONE 16-byte load (sample_flow, flow_sample.h); needs W >= 2.  The comparison itself is
+// flows_disagree, which flow_track.hip applies to a tracked point.
 template <bool PAIR>
 __device__ __forceinline__ uint32_t occluded_at(const float2 *__restrict__ other, float2 f, int x, int y, int H, int W, float alpha,
                                                  float beta) {
     const Taps t = flow_taps(x, y, f, H, W);
-    float2 g00, g01, g10, g11;
-    if (PAIR) {
-        const int col = t.o01 - t.o00;               // 1, or 0 where x0 is the row's last pixel
-        const FlowPair r0 = *(const FlowPair *)(other + t.o00 + col - 1), r1 = *(const FlowPair *)(other + t.o10 + col - 1);
-        g00 = col ? r0.lo : r0.hi, g01 = r0.hi, g10 = col ? r1.lo : r1.hi, g11 = r1.hi;
-    } else {
-        g00 = other[t.o00], g01 = other[t.o01], g10 = other[t.o10], g11 = other[t.o11];
-    }
-    const float sx = bilinear(t, g00.x, g01.x, g10.x, g11.x), sy = bilinear(t, g00.y, g01.y, g10.y, g11.y);
-    const float dx = f.x + sx, dy = f.y + sy;
-    const float lhs = dx * dx + dy * dy;
-    const float rhs = alpha * ((f.x * f.x + f.y * f.y) + (sx * sx + sy * sy)) + beta;
-    return (t.in && lhs <= rhs) ? 0u : 1u;           // (a NaN anywhere: occluded)
+    const float2 s = sample_flow<PAIR>(other, t);
+    return (t.in && !flows_disagree(f, s, alpha, beta)) ? 0u : 1u;      // (a NaN anywhere: occluded)
 }
 
 template <bool PAIR>

@@ -82,9 +82,7 @@ __global__ void __launch_bounds__(kTileW *kTileH) view_frames_kernel(const float
     }
 }
 
-struct alignas(8) FlowPair {
-    float2 lo, hi;               // two neighbouring vectors of a row, read as one 16-byte load
-};
+// (FlowPair, two neighbouring vectors of a row read as one 16-byte load: flow_sample.h)
 struct MaskPair {
     uint8_t lo, hi;              // their trust bytes, read as one 2-byte load
 };

@@ -40,6 +40,11 @@ tf_raft_amd/csrc/flow_splat.hip); ``range_visibility_launch`` is its in-step for
 ``C + 1`` sums per pixel, for uint8 frames and float32 frames on 0 .. 255, and the frame at a time ``t`` between two frames from
 both flows of a bidirectional prediction (``raft_splat_frames_*`` / ``raft_interpolate_frames_*``, tf_raft_amd/csrc/frame_splat.hip).
 
+``track`` follows points through the flows of consecutive frame pairs: the forward flow sampled at the
+point, the point moved, the backward flow sampled there and tested against it, all steps of all points in one launch
+(``raft_track_points_f32``, tf_raft_amd/csrc/flow_track.hip); ``point_grid`` makes the points of a dense long-range flow and
+``tf_raft_amd.video.FlowTracker`` is the tracker above the model.
+
 ``forward_interpolate`` projects a low-resolution flow forward along itself: the start of the next pair's
 recurrence in a video stream (``raft_forward_interpolate_f32``, tf_raft_amd/csrc/flow_init.hip; ``tf_raft_amd.video``).
 
@@ -1125,6 +1130,152 @@ def interpolate(image1, image2, flow_forward, flow_backward, t=0.5, mask1=None, 
     lead = (len(times),) if many else ()
     res = _dev.wrap(out.view(lead + shape))
     return (res, _dev.wrap(holes.view(lead + shape[:-1]))) if return_holes else res
+
+
+# ------------------------------------------------------------------------------------------ points followed through a video
+def point_grid(H, W, stride=1, N=1):
+    """Every ``stride``-th pixel of an ``H x W`` frame as points: a host array ``(N, P, 2)`` float32 of ``(x, y)``, rows first
+    (``P = ceil(H / stride) * ceil(W / stride)``), the same for each of the ``N`` videos.  With ``stride=1`` it is the start of
+    a dense long-range flow: ``positions - point_grid(H, W)`` after ``track`` is that flow, ``lost`` its occlusion flag."""
+    for name, v in (('H', H), ('W', W), ('stride', stride), ('N', N)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f'{name} must be an integer >= 1, got {v!r}')
+    ys, xs = np.arange(0, int(H), int(stride), dtype=np.float32), np.arange(0, int(W), int(stride), dtype=np.float32)
+    grid = np.stack(np.broadcast_arrays(xs[None, :], ys[:, None]), axis=-1).reshape(1, -1, 2)
+    return np.ascontiguousarray(np.broadcast_to(grid, (int(N),) + grid.shape[1:]))
+
+
+def check_track_time(t0, steps=0):
+    """``t0`` of a track as an int: an integer (no bool) >= 0 with ``t0 + steps`` below 2^31."""
+    if isinstance(t0, (bool, np.bool_)) or not isinstance(t0, (int, np.integer)) or t0 < 0 or int(t0) + int(steps) >= 1 << 31:
+        raise ValueError(f't0 must be an integer >= 0 (with t0 + S below 2^31), got {t0!r}')
+    return int(t0)
+
+
+def _points_ahead(points, lost, start, what, lead=2):
+    """Shapes and types of ``points`` ``(N, P, 2)`` float32 (``lead=1``: ``(P, 2)``), ``lost`` (uint8 / bool, the points' leading
+    shape) and ``start`` (integers >= 0 below 2^31, the same shape), checked before anything reaches a device.  Returns the
+    points' leading shape."""
+    shape, dtype = _shape_and_type(points, what)
+    if len(shape) != lead + 1 or shape[-1] != 2:
+        raise ValueError(f'{what} expects points {"(N, P, 2)" if lead == 2 else "(P, 2)"}, got {shape}')
+    if 0 in shape:
+        raise ValueError(f'empty input {shape}')
+    if dtype != torch.float32:
+        raise TypeError(f'points are float32, got {dtype}')
+    if lost is not None:
+        lshape, ldtype = _shape_and_type(lost, what)
+        if lshape != shape[:-1]:
+            raise ValueError(f'{what} expects lost {shape[:-1]}, got {lshape}')
+        if ldtype not in (torch.uint8, torch.bool):
+            raise TypeError(f'lost is uint8 or bool, got {ldtype}')
+    if start is not None:
+        if isinstance(start, torch.Tensor):
+            sshape, integral = tuple(start.shape), start.dtype in (torch.int32, torch.int64)
+            host = start if start.device.type == 'cpu' else None
+        else:
+            host = np.asarray(start)
+            sshape, integral = host.shape, host.dtype.kind in 'iu'
+        if not integral:
+            raise TypeError(f'start holds integers (frame indices), got {start.dtype if hasattr(start, "dtype") else type(start)}')
+        if tuple(sshape) != shape[:-1]:
+            raise ValueError(f'{what} expects start {shape[:-1]}, got {tuple(sshape)}')
+        if host is not None and (int(host.min()) < 0 or int(host.max()) >= 1 << 31):
+            raise ValueError('start holds frame indices >= 0 (below 2^31)')
+    return shape[:-1]
+
+
+def _start_on_device(start, shape):
+    if start is None:
+        return None
+    t = start.detach() if isinstance(start, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(start).astype(np.int32)))
+    return t.to(device=_dev.require_gpu(), dtype=torch.int32).reshape(shape).contiguous()
+
+
+def _check_track_sizes(S, N, P, H, W):
+    if S * N * H * W * 2 >= 1 << 31 or S * N * P * 2 >= 1 << 31:
+        raise ValueError(f'a track takes fewer than 2^31 elements of flow and of positions, got (S, N, H, W) = {(S, N, H, W)} and '
+                         f'P = {P}: too large')
+
+
+def track_launch(points: torch.Tensor, forward: torch.Tensor, backward=None, lost=None, start=None, t0: int = 0,
+                 alpha: float = CONSISTENCY_ALPHA, beta: float = CONSISTENCY_BETA, out=None):
+    """The launch itself (``raft_track_points_f32``): contiguous float32 device points ``(N, P, 2)`` as
+    ``(x, y)`` in pixels, the contiguous float32 flows ``forward`` ``(S, N, H, W, 2)`` of the pairs ``t0 + s -> t0 + s + 1`` and
+    ``backward`` (the same shape, the other direction; None: only the frame borders are tested), optional contiguous ``lost``
+    (uint8 ``(N, P)``, nonzero = already lost) and ``start`` (int32 ``(N, P)``: a point is copied through until its frame) ->
+    ``(positions (S, N, P, 2) float32, lost (S, N, P) uint8)``, the state after every step, by ONE launch on the CURRENT stream
+    (plain tensors).  ``out``: a pair of tensors to write them into; with ``S = 1`` it may be ``(points.view(1, N, P, 2),
+    lost.view(1, N, P))`` -- the in-place step of a stream."""
+    alpha, beta = check_consistency_args(alpha, beta)
+    if points.dim() != 3 or points.shape[-1] != 2 or points.dtype != torch.float32 or not points.is_contiguous() or 0 in points.shape:
+        raise ValueError(f'expected contiguous float32 points (N, P, 2), got {tuple(points.shape)} {points.dtype}')
+    N, P, _ = points.shape
+    if forward.dim() != 5 or forward.shape[1] != N or forward.shape[-1] != 2 or forward.device != points.device or 0 in forward.shape:
+        raise ValueError(f'points {tuple(points.shape)} on {points.device} need flows (S, {N}, H, W, 2), got {tuple(forward.shape)} on '
+                         f'{forward.device}')
+    _check_flow(forward, 'track')
+    S, _, H, W, _ = forward.shape
+    if backward is not None:
+        if backward.shape != forward.shape or backward.device != forward.device:
+            raise ValueError(f'expected a backward flow {tuple(forward.shape)} on {forward.device}, got {tuple(backward.shape)} on '
+                             f'{backward.device}')
+        _check_flow(backward, 'track')
+    t0 = check_track_time(t0, S)
+    _check_track_sizes(S, N, P, H, W)
+    if points.data_ptr() % 8:
+        raise ValueError('track reads whole points: they must be 8-byte aligned')
+    if lost is not None:
+        lost = _check_out(lost, (N, P), torch.uint8, points.device)
+    if start is not None:
+        start = _check_out(start, (N, P), torch.int32, points.device)
+    if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+        raise ValueError('out must be a pair (positions (S, N, P, 2), lost (S, N, P))')
+    pos_out = _check_out(None if out is None else out[0], (S, N, P, 2), torch.float32, points.device)
+    lost_out = _check_out(None if out is None else out[1], (S, N, P), torch.uint8, points.device)
+    if pos_out.data_ptr() % 8:
+        raise ValueError('track writes whole points: the positions must be 8-byte aligned')
+    with torch.cuda.device(points.device):
+        check(_dev.lib().raft_track_points_f32(_dev.ptr(points), _dev.ptr(lost) if lost is not None else None,
+                                               _dev.ptr(start) if start is not None else None, t0, _dev.ptr(forward),
+                                               _dev.ptr(backward) if backward is not None else None, _dev.ptr(pos_out),
+                                               _dev.ptr(lost_out), S, N, P, H, W, alpha, beta, _dev.stream_ptr()), 'track_points')
+    return pos_out, lost_out
+
+
+def track(points, forward, backward=None, lost=None, start=None, t0=0, alpha=CONSISTENCY_ALPHA, beta=CONSISTENCY_BETA):
+    """Points followed along flows: ``points`` ``(N, P, 2)`` float32 as ``(x, y)`` in pixels (NumPy or
+    torch, host or device; float64 narrows), ``forward`` the flows ``(S, N, H, W, 2)`` of ``S`` consecutive frame pairs of ``N``
+    videos, or ``(N, H, W, 2)`` for one step, and ``backward`` the flows of the same pairs in the other direction ->
+    ``(positions, lost)``, device tensors ``(S, N, P, 2)`` float32 and ``(S, N, P)`` uint8: where every point is after every
+    step (without the step axis for a 4-D ``forward``).  A step samples the forward flow bilinearly at the point, moves the point
+    by it, samples the backward flow there and applies ``flow_consistency``'s test with ``alpha`` / ``beta`` (Meister et al.
+    2018, whose values the defaults are).  ``lost``: 0 = tracked, 1 = the point or its new position lies outside ``[0, W - 1] x
+    [0, H - 1]`` (or is NaN), 2 = the two flows disagree (an occlusion); a lost point stays lost and keeps the position it was
+    last tracked at.  ``backward=None``: only the frame borders are tested.  ``lost`` (uint8 / bool ``(N, P)``): the codes to
+    begin with; ``start`` (integers ``(N, P)``) with ``t0``, the frame index of the first pair's first frame: a point waits,
+    untouched, until the step that begins at its frame.  ONE launch on the current stream, whatever ``S`` is; the result equals
+    its float32 NumPy restatement bit for bit."""
+    alpha, beta = check_consistency_args(alpha, beta)
+    lead = _points_ahead(points, lost, start, 'track')
+    N, P = lead
+    fshape, fdtype = _shape_and_type(forward, 'track')
+    if len(fshape) not in (4, 5) or fshape[-1] != 2 or fshape[-4] != N or 0 in fshape:
+        raise ValueError(f'track expects flows (S, N, H, W, 2) or (N, H, W, 2) with N = {N}, got {fshape}')
+    if fdtype != torch.float32:
+        raise TypeError(f'a flow is float32, got {fdtype}')
+    if backward is not None:
+        _flow_ahead(backward, fshape[:-1], 'track')
+    shape5 = ((1,) + fshape) if len(fshape) == 4 else fshape
+    t0 = check_track_time(t0, shape5[0])
+    _check_track_sizes(shape5[0], N, P, shape5[2], shape5[3])
+    p = _on_device(points)
+    f = _on_device(forward).reshape(shape5)
+    b = None if backward is None else _on_device(backward).reshape(shape5)
+    pos, codes = track_launch(p, f, b, _mask_on_device(lost, lead), _start_on_device(start, lead), t0, alpha, beta)
+    if len(fshape) == 4:
+        pos, codes = pos[0], codes[0]
+    return _dev.wrap(pos), _dev.wrap(codes)
 
 
 # ------------------------------------------------------------------------------------------ forward projection of a flow

@@ -694,6 +694,23 @@ class RAFT:
         from .video import predict_video
         return predict_video(self, frames, warm_start, batch_size, steps)
 
+    def tracker(self, points, start=None, consistency=True, warm_start=False, alpha=image_ops.CONSISTENCY_ALPHA,
+                beta=image_ops.CONSISTENCY_BETA):
+        """Points followed through a stream of frames (``tf_raft_amd.video.FlowTracker``): ``points``
+        ``(N, P, 2)`` float32 as ``(x, y)`` in pixels of the frames; ``push(frames)`` returns ``(positions (N, P, 2), lost (N, P))``
+        in the pushed frames (None after the first push).  ``consistency=True`` tests every step against the backward flow of a
+        bidirectional pass; ``consistency=False`` rides on ``video(warm_start)`` and tests only the frame borders.  ``alpha`` /
+        ``beta`` are UnFlow's values, not tuned ones."""
+        from .video import FlowTracker
+        return FlowTracker(self, points, start, consistency, warm_start, alpha, beta)
+
+    def track_video(self, frames, points, start=None, consistency=True, batch_size=4, alpha=image_ops.CONSISTENCY_ALPHA,
+                    beta=image_ops.CONSISTENCY_BETA):
+        """``points`` ``(P, 2)`` followed through one video ``(T, H, W, 3)`` as host arrays ``(positions (T, P, 2), lost (T, P))``,
+        row 0 the points themselves (``tf_raft_amd.video.track_video``)."""
+        from .video import track_video
+        return track_video(self, frames, points, start, consistency, batch_size, alpha, beta)
+
     def predict(self, x, batch_size=None, steps=None, output='flow', clip_flow=None, convert_to_bgr=False, rad_max=None, **kwargs):
         """``keras.Model.predict`` over ``predict_step`` (reference model.py:160-166): the final flow of every image
         pair as one host array ``(N, H, W, 2)``.

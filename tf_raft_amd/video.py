@@ -9,6 +9,10 @@ projection (``image_ops.forward_interpolate``, the authors' video protocol) inst
 A call is the final-prediction forward pass of ``predict_step`` on the serial schedule on the caller's stream; the stream object
 is the ``video`` argument of ``RAFT._run``, which asks it for the two feature maps and the initial flow and leaves everything from
 the correlation volume on as it is.
+
+``FlowTracker`` (``model.tracker(points)``) and ``track_video`` follow points through footage: they chain the
+flows the predictor returns with ``image_ops.track_launch``, one launch per call whatever the number of pairs, and with
+``consistency=True`` (the default) test every step against the backward flow of ``predict_step_bidirectional``.
 """
 from __future__ import annotations
 
@@ -136,3 +140,120 @@ def predict_video(model, frames, warm_start=False, batch_size=None, steps=None):
     if not flows:
         raise ValueError('predict_video() ran no pair')
     return np.concatenate(flows, axis=0)
+
+
+class FlowTracker:
+    """``model.tracker(points, start=None, consistency=True, warm_start=False, alpha=..., beta=...)``: ``points`` ``(N, P, 2)``
+    float32 are ``(x, y)`` in pixels of the frames' own size, ``P`` query points in each of N videos.  ``push(frames)`` takes one
+    frame ``(N, H, W, 3)`` of each video and returns ``(positions (N, P, 2) float32, lost (N, P) uint8)`` as device tensors: where
+    every point is in THESE frames (None after the first push, whose frames the points are given in unless ``start`` says
+    otherwise).  ``lost``: 0 = tracked, 1 = left the frame, 2 = failed the forward-backward test; a lost point stays lost at the
+    position it was last tracked at (``image_ops.track``).  ``start`` (integers ``(N, P)``): the index of the pushed frame a
+    point is given in; it waits there, untouched, until that frame has been pushed.
+
+    ``consistency=True`` keeps the previous frames and runs ``predict_step_bidirectional((previous, frames))`` per push, so a
+    frame is encoded twice over its life; ``consistency=False`` rides on ``FlowVideo(model, warm_start)`` (every frame encoded
+    once) and tests only the frame borders.  It chains the flows the predictor RETURNS, at the frames' own size, so it works
+    with every ``target_size`` / ``fit``.  ``reset()`` goes back to the given points and forgets the stream."""
+
+    def __init__(self, model, points, start=None, consistency=True, warm_start=False, alpha=image_ops.CONSISTENCY_ALPHA,
+                 beta=image_ops.CONSISTENCY_BETA):
+        self.alpha, self.beta = image_ops.check_consistency_args(alpha, beta)
+        self.consistency = bool(consistency)
+        if self.consistency and warm_start:
+            raise ValueError('warm_start belongs to the one-directional stream: pass consistency=False with it')
+        self._lead = image_ops._points_ahead(points, None, start, 'tracker')
+        self.model = model
+        self._video = None if self.consistency else FlowVideo(model, warm_start)
+        self._given, self._given_start = points, start
+        self._points = self._start = None         # on the device from the first push on
+        self.reset()
+
+    def reset(self):
+        self._signature = None
+        self._previous = None                    # consistency: the last frames, as they came
+        self._pos = self._lost = None
+        self._t = 0                              # frames pushed so far
+        if self._video is not None:
+            self._video.reset()
+
+    def push(self, frames):
+        shape = tuple(frames.shape) if hasattr(frames, 'shape') else np.shape(frames)
+        dtype = frames.dtype if hasattr(frames, 'dtype') else np.asarray(frames).dtype
+        if len(shape) != 4 or shape[-1] != 3 or 0 in shape or shape[0] != self._lead[0]:
+            raise ValueError(f'frames must be (N, H, W, 3) with N = {self._lead[0]}, one frame per video of the points, got {shape}')
+        signature = shape[:3] + (str(dtype).replace('torch.', ''),)
+        if self._signature is not None and signature != self._signature:
+            raise ValueError(f'this tracker holds frames (N, H, W, type) = {self._signature}, got {signature}: reset() it first')
+        if self._points is None:
+            self._points = image_ops._on_device(self._given)
+            self._start = image_ops._start_on_device(self._given_start, self._lead)
+        forward = backward = None
+        if self.consistency:
+            frames = image_ops._on_device(frames)
+            if self._previous is not None:
+                res = self.model.predict_step_bidirectional((self._previous, frames), self.alpha, self.beta)
+                forward, backward = res.forward.as_subclass(torch.Tensor), res.backward.as_subclass(torch.Tensor)
+            self._previous = frames
+        else:
+            flow = self._video.push(frames)
+            forward = None if flow is None else flow.as_subclass(torch.Tensor)
+        self._signature = signature
+        self._t += 1
+        if forward is None:
+            return None
+        pos, lost = image_ops.track_launch(self._points if self._pos is None else self._pos, forward[None],
+                                           None if backward is None else backward[None], self._lost, self._start, self._t - 2,
+                                           self.alpha, self.beta)
+        self._pos, self._lost = pos[0], lost[0]
+        return _dev.wrap(self._pos), _dev.wrap(self._lost)
+
+
+def track_video(model, frames, points, start=None, consistency=True, batch_size=4, alpha=image_ops.CONSISTENCY_ALPHA,
+                beta=image_ops.CONSISTENCY_BETA):
+    """``RAFT.track_video``: ``points`` ``(P, 2)`` float32, ``(x, y)`` in pixels, followed through ONE video ``(T, H, W, 3)``,
+    host or device -> host arrays ``(positions (T, P, 2) float32, lost (T, P) uint8)``: row ``t`` says where every point is in
+    frame ``t`` (row 0: the points themselves; a point with ``start[p] = k`` holds its given position in rows ``0 .. k``).
+    ``batch_size`` consecutive pairs run per call (``predict_step_bidirectional``; with ``consistency=False`` a ``FlowVideo``
+    call, every frame encoded once, only the frame borders tested) and ONE ``image_ops.track_launch`` chains the call's pairs,
+    positions and codes carried from call to call.  Host frames are uploaded one chunk ahead of the compute stream."""
+    from .prefetch import prefetch_to_device
+    alpha, beta = image_ops.check_consistency_args(alpha, beta)
+    shape = tuple(frames.shape) if hasattr(frames, 'shape') else np.shape(frames)
+    if len(shape) != 4 or shape[-1] != 3:
+        raise ValueError(f'frames must be one video (T, H, W, 3), got {shape}')
+    T = shape[0]
+    if T < 2:
+        raise ValueError(f'a video needs at least two frames, got T = {T}')
+    (P,) = image_ops._points_ahead(points, None, start, 'track_video', lead=1)
+    if isinstance(batch_size, (bool, np.bool_)) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
+        raise ValueError(f'batch_size must be an integer >= 1, got {batch_size!r}')
+    bs = int(batch_size)
+    dev = _dev.require_gpu()
+    first = image_ops._on_device(points).reshape(1, P, 2)
+    begin = image_ops._start_on_device(start, (1, P))
+    pos = torch.empty((T, 1, P, 2), device=dev, dtype=torch.float32)
+    lost = torch.zeros((T, 1, P), device=dev, dtype=torch.uint8)
+    pos[0] = first
+    video = None if consistency else FlowVideo(model, False)
+    # a chunk holds the new frames of a call; the call's first frame is the one before them
+    chunks = ((frames[a:b],) for a, b in [(0, 1)] + [(s, min(s + bs, T)) for s in range(1, T, bs)])
+    previous, t = None, 0                        # the last frame of the chunk before, and its index
+    for (chunk,) in prefetch_to_device(chunks, buffer_size=1, device=dev):
+        k = chunk.shape[0]
+        if video is not None:
+            forward, backward = video._step(chunk, k), None
+        elif previous is None:
+            forward = backward = None
+        else:
+            both = torch.cat([previous, chunk], dim=0)
+            res = model.predict_step_bidirectional((both[:-1], both[1:]), alpha, beta)
+            forward, backward = res.forward, res.backward
+        previous = chunk[-1:]
+        if forward is None:
+            continue
+        forward = forward.as_subclass(torch.Tensor)[:, None]
+        backward = None if backward is None else backward.as_subclass(torch.Tensor)[:, None]
+        image_ops.track_launch(pos[t], forward, backward, lost[t], begin, t, alpha, beta, out=(pos[t + 1:t + 1 + k], lost[t + 1:t + 1 + k]))
+        t += k
+    return pos[:, 0].cpu().numpy(), lost[:, 0].cpu().numpy()
