@@ -404,6 +404,44 @@ int raft_track_points_f32(const float *pos_in, const uint8_t *lost_in, const int
                           const float *flow_backward, float *pos_out, uint8_t *lost_out, int S, int N, int64_t P, int H, int W,
                           float alpha, float beta, void *stream);
 
+/* The camera's motion from a flow (csrc/flow_motion.hip has the definition in the operation order of the kernels; DESIGN.md
+ * section 27).  raft_flow_fit_motion_f32 fits, per slice of flow (N, H, W, 2), the displacement field d(X, Y) = L (X, Y) + t in
+ * the centred coordinates X = x - (W - 1) / 2, Y = y - (H - 1) / 2 to the USED vectors by iteratively reweighted least squares:
+ * a pixel is used iff both components of its vector are finite and mask == NULL, or mask_invert == 0 and its byte of mask (uint8
+ * (N, H, W)) is nonzero, or mask_invert == 1 and the byte is zero (an occluded_* mask goes in as it is).  model: 0 translation,
+ * 1 similarity (rotation, uniform zoom, shift), 2 affine.  Solve 1 weights every used pixel 1; solve k > 1 weights it
+ * 1 / (1 + r2 / scale^2), r2 its squared residual under the float64 estimate of solve k - 1 (Cauchy; evaluated with one division
+ * as s2 / (s2 + r2), s2 = (double)scale * (double)scale); iterations in 1 .. 32, scale in pixels, positive and finite.  All arithmetic behind the load is float64, never fused; sums are per-thread float64, reduced
+ * through records that belong to one slice each and added in a fixed order: the same input gives the same bits, and a slice's
+ * result does not depend on the other slices.
+ *   motion (N, 2, 3): the map p2 = M (x, y, 1) from frame 1 to frame 2 in plain pixel coordinates, M[:, :2] = I + L,
+ *     M[:, 2] = t - L c with c the frame centre, formed in float64, each entry rounded once; zero flow gives the identity exactly.
+ *   stats (N, 4): used / (H W); the inlier share Sw / used and the weighted RMS residual sqrt(Sw_r2 / Sw), both with the Cauchy
+ *     weights under the FINAL estimate; the status.  The first three are 0 where no pixel is used.
+ *   status: 0 the model asked for was fitted; 1 its normal equations had no rank (affine: D <= 1e-12 max(cxx, cyy)^2; similarity:
+ *     cxx + cyy <= 0; or a NaN), L = 0 and t = the weighted mean vector; 2 nothing to fit (!(Sw > 0)), L = 0 and t = 0.  0 and 1
+ *     refer to the last solve; 2 stays once it is met.
+ * workspace: raft_flow_motion_workspace_doubles(N, H, W) doubles (0: the sizes are refused), 8-byte aligned; it need not be
+ * cleared.  2 * iterations + 2 launches on `stream`, no atomics, no memset, no host synchronisation.
+ * Errors, in this order: RAFT_E_NULL for a NULL flow, motion, stats or workspace; RAFT_E_SHAPE for a non-positive size,
+ * N * H * W * 2 of 2^31 or more, N above 65535, a model outside 0 .. 2, iterations outside 1 .. 32, a mask_invert other than 0 or
+ * 1, a scale that is not positive and finite; RAFT_E_ALIGN for a flow or a workspace that is not 8-byte aligned.  All checks
+ * precede the first launch.
+ *
+ * raft_flow_residual_f32: residual[n, y, x] = flow[n, y, x] - g with g = (((double)m00 * x + (double)m01 * y) + (double)m02) - x
+ * (likewise for the second component with row 1 and y), evaluated in float64, never fused, each component rounded to float32
+ * once; moving (uint8 (N, H, W)) = 1 iff !(rx^2 + ry^2 <= threshold^2) on the float64 residual, so a vector that is not finite
+ * is marked.  residual or moving may be NULL, not both.  One launch, every output element written once.  Errors: RAFT_E_NULL
+ * (flow, motion, or both outputs NULL); RAFT_E_SHAPE (a non-positive size, N * H * W * 2 of 2^31 or more, a threshold that is
+ * negative or not finite, checked with and without `moving`); RAFT_E_ALIGN (a flow or a residual that is not 8-byte aligned).
+ * raft_motion_flow_f32: flow[n, y, x] = g, the dense flow of the motions, each component rounded once; the same errors. */
+int64_t raft_flow_motion_workspace_doubles(int N, int H, int W);
+int raft_flow_fit_motion_f32(const float *flow, const uint8_t *mask, int mask_invert, float *motion, float *stats,
+                             int N, int H, int W, int model, int iterations, float scale, double *workspace, void *stream);
+int raft_flow_residual_f32(const float *flow, const float *motion, float *residual, uint8_t *moving,
+                           int N, int H, int W, float threshold, void *stream);
+int raft_motion_flow_f32(const float *motion, float *flow, int N, int H, int W, void *stream);
+
 /* ------------------------------------------------------------------ training augmentation */
 
 /* FlowAugmentor (reference tf_raft/datasets/augmentor.py:9-129, used at dataset.py:87-91) composed into one gather (the sparse

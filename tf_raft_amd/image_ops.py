@@ -45,6 +45,12 @@ point, the point moved, the backward flow sampled there and tested against it, a
 (``raft_track_points_f32``, tf_raft_amd/csrc/flow_track.hip); ``point_grid`` makes the points of a dense long-range flow and
 ``tf_raft_amd.video.FlowTracker`` is the tracker above the model.
 
+``fit_motion`` says what the camera did between two frames: one 2 x 3 matrix per slice -- a translation, a
+similarity or an affine map -- fitted to the vectors of a flow by iteratively reweighted least squares, float64 sums in a fixed order
+(``raft_flow_fit_motion_f32``, tf_raft_amd/csrc/flow_motion.hip); ``residual_flow`` is the flow with that motion taken away and the
+mask of what moves on its own, ``motion_flow`` the dense flow of a motion, and ``MotionViews`` hands corrections to ``view_frames``
+(``tf_raft_amd.video.stabilize_video``).
+
 ``forward_interpolate`` projects a low-resolution flow forward along itself: the start of the next pair's
 recurrence in a video stream (``raft_forward_interpolate_f32``, tf_raft_amd/csrc/flow_init.hip; ``tf_raft_amd.video``).
 
@@ -1276,6 +1282,224 @@ def track(points, forward, backward=None, lost=None, start=None, t0=0, alpha=CON
     if len(fshape) == 4:
         pos, codes = pos[0], codes[0]
     return _dev.wrap(pos), _dev.wrap(codes)
+
+
+# ------------------------------------------------------------------------------------------ the camera's motion
+MOTION_MODELS = ('translation', 'similarity', 'affine')      # the C entry's model 0, 1, 2
+MOTION_ITERATIONS, MOTION_SCALE = 5, 1.0                     # choices, not tuned values
+MOTION_MAX_ITERATIONS = 32                                   # include/raft_hip.h raft_flow_fit_motion_f32
+MOTION_MAX_SLICES = 65535                                    # csrc/flow_motion.hip kMotionMaxSlices
+
+
+def _float32_value(v, name):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f'{name} must be a number, got {v!r}')
+    try:
+        with np.errstate(over='ignore'):
+            return float(np.float32(v))
+    except OverflowError:
+        return float('inf')
+
+
+def check_motion_args(model='affine', iterations=MOTION_ITERATIONS, scale=MOTION_SCALE):
+    """``(model index, iterations, scale)`` of a motion fit: ``model`` one of ``MOTION_MODELS``, ``iterations`` an integer (no
+    bool) in 1 .. 32, ``scale`` a number whose float32 value is positive and finite (pixels)."""
+    if not isinstance(model, str) or model not in MOTION_MODELS:
+        raise ValueError(f"model must be 'translation', 'similarity' or 'affine', got {model!r}")
+    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) or not 1 <= iterations <= MOTION_MAX_ITERATIONS:
+        raise ValueError(f'iterations must be an integer in 1 .. {MOTION_MAX_ITERATIONS}, got {iterations!r}')
+    s = _float32_value(scale, 'scale')
+    if not (s > 0.0 and np.isfinite(s)):
+        raise ValueError(f'scale must be positive and finite as a float32, got {scale!r}')
+    return MOTION_MODELS.index(model), int(iterations), s
+
+
+def check_motion_threshold(threshold):
+    """``threshold`` of ``residual_flow`` as a float, or None: a number (no bool) whose float32 value is finite and >= 0."""
+    if threshold is None:
+        return None
+    t = _float32_value(threshold, 'threshold')
+    if not (t >= 0.0 and np.isfinite(t)):
+        raise ValueError(f'threshold must be finite and >= 0 as a float32, got {threshold!r}')
+    return t
+
+
+def _check_motion_sizes(N, H, W, fit, what):
+    if N * H * W * 2 >= 1 << 31 or (fit and N > MOTION_MAX_SLICES):
+        raise ValueError(f'{what} takes flows of fewer than 2^31 floats{" in at most 65535 slices" if fit else ""}, got {N} x {H} x {W}: '
+                         'too large')
+
+
+def _check_motion(motion, N, device, what):
+    if (not isinstance(motion, torch.Tensor) or tuple(motion.shape) != (N, 2, 3) or motion.dtype != torch.float32 or motion.device != device
+            or not motion.is_contiguous()):
+        raise ValueError(f'{what}: motion must be a contiguous float32 tensor {(N, 2, 3)} on {device}')
+    return motion if type(motion) is torch.Tensor else motion.as_subclass(torch.Tensor)
+
+
+def fit_motion_launch(flow: torch.Tensor, mask=None, invert: bool = False, model: str = 'affine', iterations: int = MOTION_ITERATIONS,
+                      scale: float = MOTION_SCALE):
+    """The launches themselves (``raft_flow_fit_motion_f32``): a contiguous float32 device flow ``(N, H, W, 2)``
+    and an optional contiguous uint8 ``mask`` ``(N, H, W)`` -- a pixel is used where it is nonzero, with ``invert=True`` where it
+    is zero -> ``(motion (N, 2, 3), stats (N, 4))`` float32 on the CURRENT stream (plain tensors), ``2 * iterations + 2``
+    launches enqueued by one call, nothing synchronised."""
+    from . import losses
+    model, iterations, scale = check_motion_args(model, iterations, scale)
+    if flow.dim() != 4 or flow.shape[-1] != 2 or 0 in flow.shape:
+        raise ValueError(f'expected a flow (N, H, W, 2), got {tuple(flow.shape)}')
+    _check_flow(flow, 'fit_motion')
+    N, H, W, _ = flow.shape
+    _check_motion_sizes(N, H, W, True, 'fit_motion')
+    if mask is not None:
+        mask = _check_out(mask, (N, H, W), torch.uint8, flow.device)
+    motion = torch.empty((N, 2, 3), device=flow.device, dtype=torch.float32)
+    stats = torch.empty((N, 4), device=flow.device, dtype=torch.float32)
+    lib = _dev.lib()
+    with torch.cuda.device(flow.device):
+        ws = losses._workspace(flow.device, 8 * int(lib.raft_flow_motion_workspace_doubles(N, H, W)))
+        check(lib.raft_flow_fit_motion_f32(_dev.ptr(flow), _dev.ptr(mask) if mask is not None else None, int(bool(invert)), _dev.ptr(motion),
+                                           _dev.ptr(stats), N, H, W, model, iterations, scale, _dev.ptr(ws), _dev.stream_ptr()),
+              'fit_motion')
+    return motion, stats
+
+
+def residual_flow_launch(flow: torch.Tensor, motion: torch.Tensor, threshold=None, want_residual: bool = True):
+    """The launch itself (``raft_flow_residual_f32``): a contiguous float32 device flow ``(N, H, W, 2)`` and the motions ``(N, 2, 3)``
+    -> ``(residual (N, H, W, 2) float32, moving (N, H, W) uint8)`` on the CURRENT stream (plain tensors): the flow minus the
+    motion's own, and 1 where what is left is longer than ``threshold`` (``moving`` is None without a threshold, ``residual`` with
+    ``want_residual=False``)."""
+    threshold = check_motion_threshold(threshold)
+    if flow.dim() != 4 or flow.shape[-1] != 2 or 0 in flow.shape:
+        raise ValueError(f'expected a flow (N, H, W, 2), got {tuple(flow.shape)}')
+    _check_flow(flow, 'residual_flow')
+    N, H, W, _ = flow.shape
+    _check_motion_sizes(N, H, W, False, 'residual_flow')
+    motion = _check_motion(motion, N, flow.device, 'residual_flow')
+    if threshold is None and not want_residual:
+        raise ValueError('residual_flow: nothing to compute without a threshold and without the residual')
+    residual = torch.empty((N, H, W, 2), device=flow.device, dtype=torch.float32) if want_residual else None
+    moving = torch.empty((N, H, W), device=flow.device, dtype=torch.uint8) if threshold is not None else None
+    with torch.cuda.device(flow.device):
+        check(_dev.lib().raft_flow_residual_f32(_dev.ptr(flow), _dev.ptr(motion), _dev.ptr(residual) if residual is not None else None,
+                                                _dev.ptr(moving) if moving is not None else None, N, H, W,
+                                                0.0 if threshold is None else threshold, _dev.stream_ptr()), 'residual_flow')
+    return residual, moving
+
+
+def motion_flow_launch(motion: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """The launch itself (``raft_motion_flow_f32``): contiguous float32 device motions ``(N, 2, 3)`` -> their dense flows
+    ``(N, H, W, 2)`` float32 on the CURRENT stream (a plain tensor)."""
+    H, W = _view_size((H, W))
+    if not isinstance(motion, torch.Tensor) or motion.dim() != 3 or 0 in motion.shape:
+        raise ValueError(f'expected motions (N, 2, 3), got {tuple(getattr(motion, "shape", ()))}')
+    N = motion.shape[0]
+    motion = _check_motion(motion, N, motion.device, 'motion_flow')
+    _check_motion_sizes(N, H, W, False, 'motion_flow')
+    flow = torch.empty((N, H, W, 2), device=motion.device, dtype=torch.float32)
+    with torch.cuda.device(motion.device):
+        check(_dev.lib().raft_motion_flow_f32(_dev.ptr(motion), _dev.ptr(flow), N, H, W, _dev.stream_ptr()), 'motion_flow')
+    return flow
+
+
+def _flow_lead(flow, what):
+    """Shape of a flow argument ``(..., H, W, 2)`` with its leading axes folded: ``(shape, (N, H, W))``, checked ahead."""
+    shape, dtype = _shape_and_type(flow, what)
+    if len(shape) < 3 or shape[-1] != 2:
+        raise ValueError(f'{what} expects a flow (..., H, W, 2), got {shape}')
+    if 0 in shape:
+        raise ValueError(f'empty input {shape}')
+    if dtype != torch.float32:
+        raise TypeError(f'a flow is float32, got {dtype}')
+    return shape, (int(np.prod(shape[:-3], dtype=np.int64)),) + shape[-3:-1]
+
+
+def _motion_ahead(motion, lead, what):
+    shape, dtype = _shape_and_type(motion, what)
+    if shape != tuple(lead) + (2, 3):
+        raise ValueError(f'{what} expects motions {tuple(lead) + (2, 3)}, got {shape}')
+    if dtype != torch.float32:
+        raise TypeError(f'a motion is float32, got {dtype}')
+
+
+def fit_motion(flow, mask=None, occluded=None, model='affine', iterations=MOTION_ITERATIONS, scale=MOTION_SCALE, return_stats=False):
+    """What the camera did between two frames, from their flow: a float32 flow ``(..., H, W, 2)`` (NumPy or
+    torch, host or device; float64 narrows) -> the motions ``(..., 2, 3)`` as a float32 device tensor, one per leading index: the
+    map ``p2 = M (x, y, 1)`` from frame 1 to frame 2 in pixel coordinates whose own flow fits the given one best.  ``model``:
+    ``'translation'``, ``'similarity'`` (rotation, uniform zoom, shift) or ``'affine'``.  ``mask`` (uint8 / bool ``(..., H, W)``):
+    only pixels where it is nonzero are fitted; ``occluded``: the same with the other polarity, so the ``occluded_*`` masks of a
+    bidirectional prediction go in as they are (one of the two at most).  Vectors that are not finite are left out.
+
+    Iteratively reweighted least squares: the first of ``iterations`` solves is plain least squares, every later one weights a
+    pixel ``1 / (1 + r^2 / scale^2)`` with ``r`` its residual under the solve before (Cauchy), so whatever moves on its own loses
+    its say.  ``iterations=5`` and ``scale=1.0`` pixel are choices, not tuned values.  ``return_stats=True`` also returns
+    ``(..., 4)`` float32: the share of used pixels, the inlier share (mean weight), the weighted RMS residual in pixels, and the
+    status (0 fitted, 1 the vectors do not determine the model: translation only, 2 no pixel to fit: identity).  Float64 sums in a
+    fixed order: the result repeats bit for bit and a slice does not depend on the rest of the batch."""
+    check_motion_args(model, iterations, scale)
+    shape, (N, H, W) = _flow_lead(flow, 'fit_motion')
+    if mask is not None and occluded is not None:
+        raise ValueError('fit_motion takes mask or occluded, not both')
+    chosen = mask if mask is not None else occluded
+    _mask_ahead(chosen, shape[:-1], 'fit_motion')
+    _check_motion_sizes(N, H, W, True, 'fit_motion')
+    f = _on_device(flow).reshape(N, H, W, 2)
+    motion, stats = fit_motion_launch(f, _mask_on_device(chosen, (N, H, W)), occluded is not None, model, iterations, scale)
+    motion = _dev.wrap(motion.view(shape[:-3] + (2, 3)))
+    return (motion, _dev.wrap(stats.view(shape[:-3] + (4,)))) if return_stats else motion
+
+
+def residual_flow(flow, motion, threshold=None):
+    """The flow with the camera's motion taken away: a float32 flow ``(..., H, W, 2)`` and motions ``(..., 2, 3)`` (NumPy or torch,
+    host or device) -> ``flow - motion_flow(motion, H, W)`` as a float32 device tensor of the flow's shape, formed in float64 and
+    rounded once.  With a ``threshold`` (pixels, finite and >= 0) it returns ``(residual, moving)``, ``moving`` the uint8 mask
+    ``(..., H, W)`` of the pixels whose residual is longer than the threshold or not finite: what moves on its own.  One launch."""
+    threshold = check_motion_threshold(threshold)
+    shape, (N, H, W) = _flow_lead(flow, 'residual_flow')
+    _motion_ahead(motion, shape[:-3], 'residual_flow')
+    _check_motion_sizes(N, H, W, False, 'residual_flow')
+    f = _on_device(flow).reshape(N, H, W, 2)
+    residual, moving = residual_flow_launch(f, _on_device(motion).reshape(N, 2, 3), threshold)
+    residual = _dev.wrap(residual.view(shape))
+    return residual if threshold is None else (residual, _dev.wrap(moving.view(shape[:-1])))
+
+
+def motion_flow(motion, H, W):
+    """The dense flow of motions ``(..., 2, 3)`` float32 (NumPy or torch, host or device) on an ``H x W`` frame: a float32 device
+    tensor ``(..., H, W, 2)`` with ``M (x, y, 1) - (x, y)`` at pixel ``(y, x)``, formed in float64 and rounded once.  One launch."""
+    H, W = _view_size((H, W))
+    shape, dtype = _shape_and_type(motion, 'motion_flow')
+    if len(shape) < 2 or shape[-2:] != (2, 3) or 0 in shape:
+        raise ValueError(f'motion_flow expects motions (..., 2, 3), got {shape}')
+    if dtype != torch.float32:
+        raise TypeError(f'a motion is float32, got {dtype}')
+    N = int(np.prod(shape[:-2], dtype=np.int64))
+    _check_motion_sizes(N, H, W, False, 'motion_flow')
+    return _dev.wrap(motion_flow_launch(_on_device(motion).reshape(N, 2, 3), H, W).view(shape[:-2] + (H, W, 2)))
+
+
+class MotionViews:
+    """Motions ``(N, 2, 3)`` (host, float64) as the views of ``view_host_records``: slice ``n`` is resampled at ``p = M q + o`` with
+    ``M = motions[n, :, :2]`` and ``o = motions[n, :, 2]``, each number rounded to float32 once; no colour change."""
+
+    def __init__(self, motions):
+        m = np.asarray(motions, dtype=np.float64)
+        if m.ndim != 3 or m.shape[1:] != (2, 3) or m.shape[0] < 1:
+            raise ValueError(f'expected motions (N, 2, 3), got {m.shape}')
+        self.motions = m
+
+    def __len__(self):
+        return self.motions.shape[0]
+
+    def records(self, doubled=False):
+        recs = (_ffi.ViewParams * (len(self) * (2 if doubled else 1)))()
+        for b, r in enumerate(recs):
+            m = self.motions[b % len(self)]
+            # (a map without an inverse gets one that is not finite: view_host_records refuses the record)
+            inv = np.linalg.inv(m[:, :2]) if np.isfinite(m).all() and np.linalg.det(m[:, :2]) != 0 else np.full((2, 2), np.nan)
+            with np.errstate(over='ignore'):
+                r.m[:], r.o[:], r.inv[:] = (a.astype(np.float32).tolist() for a in (m[:, :2].reshape(4), m[:, 2], inv.reshape(4)))
+            r.gain[:], r.bias[:], r.colour = [1.0] * 3, [0.0] * 3, 0
+        return recs
 
 
 # ------------------------------------------------------------------------------------------ forward projection of a flow

@@ -76,6 +76,18 @@ class BidirectionalFlow(NamedTuple):
     occluded_backward: object
 
 
+class CameraMotion(NamedTuple):
+    """What ``camera_motion_step`` returns: the motions ``(N, 2, 3)`` float32 (frame 1 to frame 2 in pixels) with their statistics
+    ``(N, 4)``, the forward flow with the motion's own taken away ``(N, H, W, 2)``, the uint8 mask ``(N, H, W)`` of what moves on its
+    own, and the forward flow and occlusion mask they were computed from."""
+    motion: object
+    stats: object
+    residual: object
+    moving: object
+    forward: object
+    occluded_forward: object
+
+
 def _hinted(hint):
     return _ffi.thread_concurrency(hint) if hint is not None else contextlib.nullcontext()
 
@@ -710,6 +722,37 @@ class RAFT:
         row 0 the points themselves (``tf_raft_amd.video.track_video``)."""
         from .video import track_video
         return track_video(self, frames, points, start, consistency, batch_size, alpha, beta)
+
+    def camera_motion_step(self, data, model='affine', occlusion_test='consistency', iterations=image_ops.MOTION_ITERATIONS,
+                           scale=image_ops.MOTION_SCALE, threshold=1.0, **occlusion):
+        """What the camera did between ``data = (image1, image2)`` and what moves on its own:
+        ``CameraMotion(motion, stats, residual, moving, forward, occluded_forward)`` of device tensors.  One
+        ``predict_step_bidirectional`` pass (``occlusion_test`` and ``**occlusion``: its ``alpha``, ``beta``, ``range_threshold``);
+        the RETURNED forward flow, at the frames' own size whatever ``target_size`` / ``fit`` is, is fitted with the pixels of
+        ``occluded_forward`` left out (``image_ops.fit_motion_launch``: ``model``, ``iterations``, ``scale``) -> ``motion`` ``(N, 2, 3)``
+        and ``stats`` ``(N, 4)``; ``residual`` ``(N, H, W, 2)`` is the flow minus the motion's own and ``moving`` ``(N, H, W)`` uint8
+        marks where it is longer than ``threshold`` pixels (``image_ops.residual_flow_launch``).  ``iterations``, ``scale`` and
+        ``threshold`` are choices, not tuned values."""
+        image_ops.check_motion_args(model, iterations, scale)
+        threshold = image_ops.check_motion_threshold(threshold)
+        if threshold is None:
+            raise ValueError('threshold must be a number, got None')
+        unknown = set(occlusion) - {'alpha', 'beta', 'range_threshold'}
+        if unknown:
+            raise TypeError(f'camera_motion_step() got unexpected keyword arguments {sorted(unknown)}')
+        res = self.predict_step_bidirectional(data, occlusion_test=occlusion_test, **occlusion)
+        forward, occluded = res.forward.as_subclass(torch.Tensor), res.occluded_forward.as_subclass(torch.Tensor)
+        motion, stats = image_ops.fit_motion_launch(forward, occluded, True, model, iterations, scale)
+        residual, moving = image_ops.residual_flow_launch(forward, motion, threshold)
+        return CameraMotion(_dev.wrap(motion), _dev.wrap(stats), _dev.wrap(residual), _dev.wrap(moving), res.forward, res.occluded_forward)
+
+    def stabilize_video(self, frames, model='similarity', radius=15, iterations=image_ops.MOTION_ITERATIONS, scale=image_ops.MOTION_SCALE,
+                        batch_size=4, occlusion_test='consistency', return_motion=False):
+        """One video ``(T, H, W, 3)`` steadied: the camera's motion fitted pair by pair on the device, its path smoothed on the host
+        and every frame resampled under its correction (``tf_raft_amd.video.stabilize_video``); a host array of the frames' shape
+        and type."""
+        from .video import stabilize_video
+        return stabilize_video(self, frames, model, radius, iterations, scale, batch_size, occlusion_test, return_motion)
 
     def predict(self, x, batch_size=None, steps=None, output='flow', clip_flow=None, convert_to_bgr=False, rad_max=None, **kwargs):
         """``keras.Model.predict`` over ``predict_step`` (reference model.py:160-166): the final flow of every image

@@ -13,6 +13,10 @@ the correlation volume on as it is.
 ``FlowTracker`` (``model.tracker(points)``) and ``track_video`` follow points through footage: they chain the
 flows the predictor returns with ``image_ops.track_launch``, one launch per call whatever the number of pairs, and with
 ``consistency=True`` (the default) test every step against the backward flow of ``predict_step_bidirectional``.
+
+``smooth_trajectory`` and ``stabilize_video`` steady footage: the camera's motion of every pair is fitted on the
+device (``image_ops.fit_motion_launch``), the path of the camera is smoothed on the host, and every frame is resampled under its
+correction (``image_ops.view_frames_launch``).  There is no streaming form: the smoother needs the frames to come.
 """
 from __future__ import annotations
 
@@ -207,6 +211,110 @@ class FlowTracker:
                                            self.alpha, self.beta)
         self._pos, self._lost = pos[0], lost[0]
         return _dev.wrap(self._pos), _dev.wrap(self._lost)
+
+
+def _as_3x3(m):
+    g = np.zeros(m.shape[:-2] + (3, 3), np.float64)
+    g[..., :2, :] = m
+    g[..., 2, 2] = 1.0
+    return g
+
+
+def smooth_trajectory(motions, radius=15, sigma=None):
+    """The corrections that steady a camera path (host only, float64 NumPy): ``motions`` ``(T - 1, 2, 3)`` are
+    the maps of consecutive frame pairs, frame ``t`` to frame ``t + 1`` in pixels (``image_ops.fit_motion``) -> ``(T, 2, 3)``, one
+    correction per frame.  With the path ``G_0 = I``, ``G_t = M_{t-1} G_{t-1}`` (3 x 3 products: where a pixel of frame 0 is in
+    frame ``t``), the steadied path ``S_t`` is the mean of ``G_s`` over ``|s - t| <= radius`` with the weights ``exp(-(s - t)^2 /
+    (2 sigma^2))``, renormalised where the window leaves the video (``sigma`` defaults to ``radius / 2``), and correction ``t`` is
+    ``G_t S_t^-1``: the map from a pixel of the steadied frame to the position in frame ``t`` that it shows, the ``p = M q + o`` of
+    ``image_ops.view_frames``.  The mean is taken entry by entry, which is a choice (it is exact for translations and a first-order
+    one for rotations and zooms that vary little within a window), not a derived optimum.  Where ``S_t`` equals ``G_t`` entry for
+    entry -- always with ``radius=0`` -- the correction is the identity exactly."""
+    m = np.asarray(motions, dtype=np.float64)
+    if m.ndim != 3 or m.shape[1:] != (2, 3):
+        raise ValueError(f'motions must be (T - 1, 2, 3), got {m.shape}')
+    if not np.isfinite(m).all():
+        raise ValueError('motions must be finite')
+    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) or radius < 0:
+        raise ValueError(f'radius must be an integer >= 0, got {radius!r}')
+    radius = int(radius)
+    if sigma is None:
+        sigma = radius / 2.0
+    elif isinstance(sigma, (bool, np.bool_)) or not isinstance(sigma, (int, float, np.integer, np.floating)) or not (
+            float(sigma) > 0.0 and np.isfinite(float(sigma))):
+        raise ValueError(f'sigma must be positive and finite, got {sigma!r}')
+    sigma = float(sigma)
+    T = m.shape[0] + 1
+    step = _as_3x3(m)
+    path = np.empty((T, 3, 3), np.float64)
+    path[0] = np.eye(3)
+    for t in range(1, T):
+        path[t] = step[t - 1] @ path[t - 1]
+    out = np.empty((T, 2, 3), np.float64)
+    for t in range(T):
+        lo, hi = max(t - radius, 0), min(t + radius, T - 1)
+        k = np.arange(lo, hi + 1, dtype=np.float64) - t
+        w = np.exp(-(k * k) / (2.0 * sigma * sigma)) if radius > 0 else np.ones(1)
+        # (the mean as G_t plus the mean deviation from it: a path that stands still is its own mean to the last bit)
+        steady = path[t] + np.tensordot(w, path[lo:hi + 1] - path[t], axes=1) / w.sum()
+        if np.array_equal(steady, path[t]):
+            out[t] = np.eye(3)[:2]
+        else:
+            out[t] = (path[t] @ np.linalg.inv(steady))[:2]
+    return out
+
+
+def stabilize_video(model, frames, motion_model='similarity', radius=15, iterations=image_ops.MOTION_ITERATIONS,
+                    scale=image_ops.MOTION_SCALE, batch_size=4, occlusion_test='consistency', return_motion=False):
+    """``RAFT.stabilize_video``: ONE video ``(T, H, W, 3)``, host or device, uint8 or float32 on 0 .. 255 -> the steadied video as a
+    host array of the same shape and type (and with ``return_motion=True`` the fitted motions ``(T - 1, 2, 3)`` float32 and the
+    corrections ``(T, 2, 3)`` float64).  ``batch_size`` consecutive pairs run per call (``predict_step_bidirectional`` with
+    ``occlusion_test``), each forward flow is fitted on the device with its ``occluded_forward`` mask left out
+    (``image_ops.fit_motion_launch``: ``motion_model``, ``iterations``, ``scale``), the motions come to the host in ONE copy,
+    ``smooth_trajectory(motions, radius)`` steadies the path there, and every frame is resampled bilinearly under its correction
+    (``image_ops.view_frames_launch``), pixels from outside the frame 0.  uint8 frames are rounded (half to even) and clipped back
+    to uint8.  The frames stay on the device between the two passes.  Nothing is claimed about how the result looks."""
+    from .prefetch import prefetch_to_device
+    image_ops.check_motion_args(motion_model, iterations, scale)
+    occlusion_test = image_ops.check_occlusion_test(occlusion_test)
+    shape, dtype = image_ops._frames_ahead(frames, 'stabilize_video')
+    if len(shape) != 4 or shape[-1] != 3:
+        raise ValueError(f'frames must be one video (T, H, W, 3), got {shape}')
+    T, H, W, _ = shape
+    if T < 2:
+        raise ValueError(f'a video needs at least two frames, got T = {T}')
+    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) or radius < 0:
+        raise ValueError(f'radius must be an integer >= 0, got {radius!r}')
+    if isinstance(batch_size, (bool, np.bool_)) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
+        raise ValueError(f'batch_size must be an integer >= 1, got {batch_size!r}')
+    bs = int(batch_size)
+    dev = _dev.require_gpu()
+    motions = torch.empty((T - 1, 2, 3), device=dev, dtype=torch.float32)
+    chunks = ((frames[a:b],) for a, b in [(0, 1)] + [(s, min(s + bs, T)) for s in range(1, T, bs)])
+    kept, t = [], 0
+    for (chunk,) in prefetch_to_device(chunks, buffer_size=1, device=dev):
+        chunk = image_ops._on_device(chunk)
+        if kept:
+            both = torch.cat([kept[-1][-1:], chunk], dim=0)
+            res = model.predict_step_bidirectional((both[:-1], both[1:]), occlusion_test=occlusion_test)
+            fit, _ = image_ops.fit_motion_launch(res.forward.as_subclass(torch.Tensor), res.occluded_forward.as_subclass(torch.Tensor),
+                                                 True, motion_model, iterations, scale)
+            motions[t:t + chunk.shape[0]] = fit
+            t += chunk.shape[0]
+        kept.append(chunk)
+    host_motions = motions.cpu().numpy()                        # the one download
+    corrections = smooth_trajectory(host_motions, radius)
+    out = np.empty(shape, np.uint8 if dtype == torch.uint8 else np.float32)
+    t = 0
+    for chunk in kept:
+        k = chunk.shape[0]
+        records = image_ops.view_records(image_ops.MotionViews(corrections[t:t + k]), k, dev)
+        seen = image_ops.view_frames_launch(chunk.to(torch.float32), records, (H, W))
+        if dtype == torch.uint8:
+            seen = seen.round_().clamp_(0, 255).to(torch.uint8)
+        out[t:t + k] = seen.cpu().numpy()
+        t += k
+    return (out, host_motions, corrections) if return_motion else out
 
 
 def track_video(model, frames, points, start=None, consistency=True, batch_size=4, alpha=image_ops.CONSISTENCY_ALPHA,
