@@ -442,6 +442,50 @@ int raft_flow_residual_f32(const float *flow, const float *motion, float *residu
                            int N, int H, int W, float threshold, void *stream);
 int raft_motion_flow_f32(const float *motion, float *flow, int N, int H, int W, void *stream);
 
+/* Motion-compensated temporal filtering: a centre frame fused with K neighbours that are aligned onto it
+ * along flows and averaged robustly, in ONE launch.  center (N, H, W, C), uint8 or float32 on 0 .. 255, C in 1 .. 4.  Neighbour k,
+ * k = 0 .. K - 1 with K in 1 .. 16, is the (N, H, W, C) block of the centre's type at neighbours + index[k] * N * H * W * C
+ * elements; index is a HOST array of K entries >= 0, read at call time and passed by value with the launch (NULL: 0 .. K - 1); an
+ * entry may repeat, so a window frames[t - r : t + r + 1] of a device video serves as it lies, with no copies.  vectors
+ * (K, N, H, W, 2) float32: with absolute == 0 the flow centre -> neighbour k, the sample position of the pixel at integer (x, y)
+ * being sx = float(x) + u, sy = float(y) + v as for raft_warp_f32; with absolute == 1 the sample position (sx, sy) itself, so
+ * raft_track_points_f32's positions go in as they are.  skip: NULL, or uint8 (K, N, H, W), nonzero = neighbour k is not used at this
+ * pixel (an occluded_* mask or raft_track_points_f32's lost codes go in unchanged).  sigma (on the 0 .. 255 scale) and
+ * center_weight are positive and finite, and s2 = sigma * sigma is positive and finite as a float32; patch_radius r in 0 .. 3.
+ * Per pixel p = (x, y) of slice n and neighbour k, in float32, every product, sum and quotient rounded on its own, never fused:
+ *     vis_k(p) = the sample position is IN FRAME (0 <= sx <= W - 1 and 0 <= sy <= H - 1, a NaN fails) && (skip == NULL ||
+ *                skip[k, n, p] == 0)
+ *     c_k[ch]  = neighbour k's channel ch sampled there by the bilinear rule of raft_warp_f32 (uint8 taps converted to float
+ *                first; out of frame the taps are those of position (0, 0), the value is never weighted)
+ *     q_k(p)   = sum over ch = 0 .. C - 1, in this order, of d * d with d = center[ch] - c_k[ch];  0.f where !vis_k(p)
+ *     D, cnt   = the sum of q_k(p') and the count of p' over the window p' = (x + dx, y + dy), dy = -r .. r outer, dx = -r .. r
+ *                inner, over the p' that are in the frame and have vis_k(p')  (q_k is +0 or larger: the kernel adds 0.f for the
+ *                others, which changes no bit)
+ *     m        = D / (float)(cnt * C)
+ *     w_k(p)   = vis_k(p) ? s2 / (s2 + m) : 0.f                                   (Cauchy, one division, as raft_flow_fit_motion_f32)
+ *   num[ch] = center_weight * center[ch], den = center_weight;  for k = 0 .. K - 1 in this order: num[ch] = num[ch] + w_k * c_k[ch],
+ *   den = den + w_k;  then dst[n, y, x, ch] = num[ch] / den and weight[n, y, x] = den.
+ * dst (N, H, W, C): float32 (_f32: float32 frames; _u8_f32: uint8 frames) or uint8 (_u8: uint8 frames, rintf -- half to even --
+ * then clamped to 0 .. 255); weight: NULL, or float32 (N, H, W).  A pixel with no visible neighbour gets (center_weight *
+ * center) / center_weight and the weight center_weight.  No transcendental function appears, so the result equals its float32
+ * NumPy restatement bit for bit and repeats bit for bit.  One launch on `stream`: no workspace, no atomics, no memset, every
+ * output element written exactly once; a workgroup stages (q_k, vis_k) of its 32 x 8 tile and a ring of r pixels in LDS once per
+ * neighbour.  dst and weight may overlap no input and not each other (windows read the neighbours' pixels).
+ * Errors, in this order: RAFT_E_NULL for a NULL center, neighbours, vectors or dst; RAFT_E_SHAPE for K outside 1 .. 16, a
+ * non-positive size, C outside 1 .. 4, patch_radius outside 0 .. 3, absolute other than 0 or 1, N * H * W above 2^26, a sigma,
+ * sigma * sigma or center_weight that is not positive and finite, a negative index (or one beyond 2^60 elements); RAFT_E_ALIGN for
+ * vectors that are not 8-byte aligned or float32 frames, dst or weight that are not 4-byte aligned (uint8 frames may lie at any
+ * address); RAFT_E_SHAPE for an output that overlaps an input or the other output.  All checks precede the launch. */
+int raft_fuse_frames_f32(const float *center, const float *neighbours, const int64_t *index, const float *vectors, const uint8_t *skip,
+                         int absolute, float sigma, float center_weight, int patch_radius, float *dst, float *weight, int K, int N,
+                         int H, int W, int C, void *stream);
+int raft_fuse_frames_u8_f32(const uint8_t *center, const uint8_t *neighbours, const int64_t *index, const float *vectors,
+                            const uint8_t *skip, int absolute, float sigma, float center_weight, int patch_radius, float *dst,
+                            float *weight, int K, int N, int H, int W, int C, void *stream);
+int raft_fuse_frames_u8(const uint8_t *center, const uint8_t *neighbours, const int64_t *index, const float *vectors,
+                        const uint8_t *skip, int absolute, float sigma, float center_weight, int patch_radius, uint8_t *dst,
+                        float *weight, int K, int N, int H, int W, int C, void *stream);
+
 /* ------------------------------------------------------------------ training augmentation */
 
 /* FlowAugmentor (reference tf_raft/datasets/augmentor.py:9-129, used at dataset.py:87-91) composed into one gather (the sparse

@@ -176,7 +176,19 @@ def side_stream(device, role: str) -> 'torch.cuda.Stream':
     key = (device.index if device.index is not None else torch.cuda.current_device(), role)
     s = _SIDE_STREAMS.get(key)
     if s is None:
-        s = _SIDE_STREAMS[key] = torch.cuda.Stream(device=device)
+        # torch hands out the 32 streams of its pool round robin, so a stream made now can BE one made 32 k creations ago by
+        # anyone in the process (every prefetch_to_device call makes one).  Two roles on one stream would hand the three-stream
+        # loops the same stream twice, which they refuse: draw again until the stream is none a role of this device holds.
+        # Compared by torch's stream id, not by the raw handle: reading the handles here cost bench.py 9 % (345 against 380
+        # pairs/s in one job, docs/NOTEBOOK.md section 40.6) -- presumably because a pool stream's HIP stream is created when its
+        # handle is first asked for, and HIP maps streams onto hardware queues in creation order.
+        taken = {t.stream_id for (d, _), t in _SIDE_STREAMS.items() if d == key[0]}
+        s = torch.cuda.Stream(device=device)
+        for _ in range(64):
+            if s.stream_id not in taken:
+                break
+            s = torch.cuda.Stream(device=device)
+        _SIDE_STREAMS[key] = s
     return s
 
 

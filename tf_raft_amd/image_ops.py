@@ -51,6 +51,11 @@ similarity or an affine map -- fitted to the vectors of a flow by iteratively re
 mask of what moves on its own, ``motion_flow`` the dense flow of a motion, and ``MotionViews`` hands corrections to ``view_frames``
 (``tf_raft_amd.video.stabilize_video``).
 
+``fuse_frames`` is motion-compensated temporal filtering: K neighbours aligned onto a centre frame along
+their flows (or at ``track``'s positions) and averaged under a patch-based Cauchy weight, occluded and out-of-frame pixels left
+out, in ONE launch that repeats bit for bit (``raft_fuse_frames_*``, tf_raft_amd/csrc/frame_fuse.hip); ``RAFT.fuse_step`` and
+``tf_raft_amd.video.denoise_video`` are burst fusion and video denoising above the model.
+
 ``forward_interpolate`` projects a low-resolution flow forward along itself: the start of the next pair's
 recurrence in a video stream (``raft_forward_interpolate_f32``, tf_raft_amd/csrc/flow_init.hip; ``tf_raft_amd.video``).
 
@@ -67,6 +72,7 @@ on another stream reads).  Making the object makes -- the first time: uploads --
 from __future__ import annotations
 
 import collections
+import ctypes
 
 import numpy as np
 import torch
@@ -1282,6 +1288,161 @@ def track(points, forward, backward=None, lost=None, start=None, t0=0, alpha=CON
     if len(fshape) == 4:
         pos, codes = pos[0], codes[0]
     return _dev.wrap(pos), _dev.wrap(codes)
+
+
+# ------------------------------------------------------------------------------------------ temporal fusion
+FUSE_SIGMA, FUSE_PATCH_RADIUS, FUSE_CENTER_WEIGHT = 10.0, 1, 1.0      # choices, not tuned values
+FUSE_MAX_NEIGHBOURS, FUSE_MAX_PATCH_RADIUS, FUSE_MAX_CHANNELS = 16, 3, 4      # csrc/frame_fuse.hip
+FUSE_MAX_PIXELS = 1 << 26                                             # N * H * W of one call
+
+
+def check_fuse_args(sigma=FUSE_SIGMA, patch_radius=FUSE_PATCH_RADIUS, center_weight=FUSE_CENTER_WEIGHT):
+    """``(sigma, patch_radius, center_weight)`` of a fusion as two floats around an int: numbers (no bool) whose float32 values
+    are positive and finite (``sigma * sigma`` too, in float32), and an integer radius in 0 .. 3."""
+    vals = []
+    for name, v in (('sigma', sigma), ('center_weight', center_weight)):
+        f = _float32_value(v, name)
+        if not (np.isfinite(f) and f > 0.0):
+            raise ValueError(f'{name} must be positive and finite as a float32, got {v!r}')
+        vals.append(f)
+    with np.errstate(over='ignore', under='ignore'):
+        s2 = float(np.float32(vals[0]) * np.float32(vals[0]))
+    if not (np.isfinite(s2) and s2 > 0.0):
+        raise ValueError(f'sigma * sigma must be positive and finite as a float32, got sigma = {sigma!r}')
+    if isinstance(patch_radius, (bool, np.bool_)) or not isinstance(patch_radius, (int, np.integer)) or \
+            not 0 <= patch_radius <= FUSE_MAX_PATCH_RADIUS:
+        raise ValueError(f'patch_radius must be an integer in 0 .. {FUSE_MAX_PATCH_RADIUS}, got {patch_radius!r}')
+    return vals[0], int(patch_radius), vals[1]
+
+
+def _check_fuse_sizes(K, N, H, W, C, what):
+    if not 1 <= K <= FUSE_MAX_NEIGHBOURS:
+        raise ValueError(f'{what} takes 1 to {FUSE_MAX_NEIGHBOURS} neighbours, got {K}')
+    if not 1 <= C <= FUSE_MAX_CHANNELS:
+        raise ValueError(f'{what} takes frames of 1 to {FUSE_MAX_CHANNELS} channels, got {C}')
+    if N * H * W > FUSE_MAX_PIXELS:
+        raise ValueError(f'{what} takes up to 2^26 pixels in a frame batch, got {N} x {H} x {W}: too large')
+
+
+def _fuse_entry(in_dtype, dtype):
+    """The entry's name and the result's type for frames of ``in_dtype`` and the result type asked for (None: the frames')."""
+    if in_dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f'fuse_frames takes uint8 or float32 frames, got {in_dtype}')
+    if dtype is None:
+        dtype = in_dtype
+    if dtype == torch.float32:
+        return ('raft_fuse_frames_f32' if in_dtype == torch.float32 else 'raft_fuse_frames_u8_f32'), torch.float32
+    if dtype == torch.uint8 and in_dtype == torch.uint8:
+        return 'raft_fuse_frames_u8', torch.uint8
+    raise TypeError(f'fuse_frames returns float32, or uint8 for uint8 frames, got {in_dtype} -> {dtype}')
+
+
+def _check_fuse_index(index, M):
+    """``index`` of a fusion (None: every block of the stack in order) as a list of ints in ``0 .. M - 1``; repeats are allowed."""
+    if index is None:
+        return list(range(M))
+    if isinstance(index, (str, bytes)) or not hasattr(index, '__iter__'):
+        raise ValueError(f'index must be a sequence of integers, got {index!r}')
+    out = []
+    for i in (index.tolist() if isinstance(index, np.ndarray) else index):
+        if isinstance(i, (bool, np.bool_)) or not isinstance(i, (int, np.integer)) or not 0 <= i < M:
+            raise ValueError(f'index holds integers in 0 .. {M - 1} (blocks of the stack), got {i!r}')
+        out.append(int(i))
+    return out
+
+
+def fuse_frames_launch(center: torch.Tensor, stack: torch.Tensor, vectors: torch.Tensor, index=None, skip=None,
+                       absolute: bool = False, sigma: float = FUSE_SIGMA, patch_radius: int = FUSE_PATCH_RADIUS,
+                       center_weight: float = FUSE_CENTER_WEIGHT, want_weight: bool = False, dtype=None, out=None, weight=None):
+    """The launch itself (``raft_fuse_frames_*``): a contiguous device centre ``(N, H, W, C)`` of uint8 /
+    float32, a contiguous ``stack`` ``(M, N, H, W, C)`` of the same type on the same device and ``index``, a sequence of K block
+    numbers of the stack (None: all M in order; repeats allowed) -- so ``video.view(T, 1, H, W, C)`` with the indices of a
+    frame's neighbours fuses a window where it lies --, contiguous float32 ``vectors`` ``(K, N, H, W, 2)`` (flows centre ->
+    neighbour k, or with ``absolute`` the sample positions themselves, e.g. ``track_launch``'s) and an optional contiguous uint8
+    ``skip`` ``(K, N, H, W)`` (nonzero = not used) -> ``(fused, weight)`` by ONE launch on the CURRENT stream (plain tensors):
+    ``(N, H, W, C)`` of ``dtype`` (None: the frames' type; float32, or uint8 for uint8 frames; ``out`` when given) and float32
+    ``(N, H, W)`` (None without ``want_weight``; ``weight``: a tensor to write it into).  The outputs may overlap no input."""
+    sigma, patch_radius, center_weight = check_fuse_args(sigma, patch_radius, center_weight)
+    if center.dim() != 4 or 0 in center.shape or not center.is_contiguous():
+        raise ValueError(f'fuse_frames: expected a contiguous centre (N, H, W, C), got {tuple(center.shape)}')
+    name, out_dtype = _fuse_entry(center.dtype, dtype)
+    N, H, W, Cn = center.shape
+    if (stack.dim() != 5 or tuple(stack.shape[1:]) != (N, H, W, Cn) or stack.shape[0] < 1 or stack.dtype != center.dtype
+            or stack.device != center.device or not stack.is_contiguous()):
+        raise ValueError(f'a centre {tuple(center.shape)} {center.dtype} on {center.device} needs a contiguous stack (M, {N}, {H}, {W}, '
+                         f'{Cn}) of its type, got {tuple(stack.shape)} {stack.dtype} on {stack.device}')
+    index = _check_fuse_index(index, stack.shape[0])
+    K = len(index)
+    _check_fuse_sizes(K, N, H, W, Cn, 'fuse_frames')
+    if tuple(vectors.shape) != (K, N, H, W, 2) or vectors.device != center.device:
+        raise ValueError(f'{K} neighbours of {tuple(center.shape)} need vectors {(K, N, H, W, 2)}, got {tuple(vectors.shape)} on {vectors.device}')
+    _check_flow(vectors, 'fuse_frames')
+    if skip is not None:
+        skip = _check_out(skip, (K, N, H, W), torch.uint8, center.device)
+    out = _check_out(out, (N, H, W, Cn), out_dtype, center.device)
+    weight = _check_out(weight, (N, H, W), torch.float32, center.device, alloc=bool(want_weight))
+    with torch.cuda.device(center.device):
+        check(getattr(_dev.lib(), name)(_dev.ptr(center), _dev.ptr(stack), (ctypes.c_int64 * K)(*index), _dev.ptr(vectors),
+                                        _dev.ptr(skip) if skip is not None else None, 1 if absolute else 0, sigma, center_weight,
+                                        patch_radius, _dev.ptr(out), _dev.ptr(weight) if weight is not None else None, K, N, H, W, Cn,
+                                        _dev.stream_ptr()), 'fuse_frames')
+    return out, weight
+
+
+def _stacked(neighbours):
+    """A list / tuple of K frame batches as one array ``(K, ...)`` (anything else is returned as it is)."""
+    if isinstance(neighbours, (list, tuple)) and neighbours and all(hasattr(a, 'shape') for a in neighbours):
+        if all(isinstance(a, torch.Tensor) for a in neighbours):
+            return torch.stack(list(neighbours), dim=0)
+        return np.stack([a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a) for a in neighbours], axis=0)
+    return neighbours
+
+
+def _fuse_ahead(center, neighbours, vectors, skip, what):
+    """Shapes and types of a fusion's arrays, checked before anything reaches a device: ``(frame shape, frame type, K)``."""
+    shape, in_dtype = _frames_ahead(center, what)
+    nshape, ndtype = _shape_and_type(neighbours, what)
+    if len(nshape) != len(shape) + 1 or nshape[1:] != shape or ndtype != in_dtype:
+        raise ValueError(f'{what} expects neighbours (K,) + {shape} of the centre\'s type {in_dtype}, got {nshape} {ndtype}')
+    K = nshape[0]
+    shape4 = ((1,) + shape) if len(shape) == 3 else shape
+    _check_fuse_sizes(K, shape4[0], shape4[1], shape4[2], shape4[3], what)
+    _flow_ahead(vectors, (K,) + shape[:-1], what)
+    _mask_ahead(skip, (K,) + shape[:-1], what)
+    return shape, in_dtype, K
+
+
+def fuse_frames(center, neighbours, flows=None, positions=None, skip=None, sigma=FUSE_SIGMA, patch_radius=FUSE_PATCH_RADIUS,
+                center_weight=FUSE_CENTER_WEIGHT, return_weight=False, dtype=None):
+    """Motion-compensated temporal filtering: a centre frame ``(H, W, C)`` or ``(N, H, W, C)`` (NumPy or
+    torch, host or device, uint8, or float32 on 0 .. 255; float64 narrows; 1 to 4 channels) fused with ``neighbours`` ``(K, ...)``
+    of the same shape and type (an array, or a list of K frames; K in 1 .. 16) -> a contiguous device tensor of the centre's shape,
+    uint8 for uint8 frames unless ``dtype=torch.float32``, float32 otherwise.  Exactly one of ``flows`` (``(K, ..., H, W, 2)``
+    float32: the flow centre -> neighbour k, as ``predict_step_bidirectional`` gives it for the pair (centre, neighbour k)) and
+    ``positions`` (the same shape: where every pixel of the centre lies in neighbour k, as ``track`` gives it for
+    ``point_grid(H, W)``) says where to sample.  Every neighbour is sampled bilinearly there (``warp``'s rule) and averaged with
+    the centre under the weight ``sigma^2 / (sigma^2 + m)``, ``m`` the mean squared difference to the centre per channel over the
+    ``(2 * patch_radius + 1)^2`` window of pixels that see the neighbour; the centre weighs ``center_weight``.  A neighbour is not
+    used at a pixel whose sample leaves the frame, is NaN, or where ``skip`` (uint8 / bool ``(K, ..., H, W)``: an ``occluded_*``
+    mask, ``track``'s ``lost``) is nonzero.  ``return_weight=True`` also returns the sum of the weights, float32 ``(..., H, W)``
+    (``center_weight`` where nothing was used).  ``sigma`` is on the 0 .. 255 scale; it, ``patch_radius`` and ``center_weight``
+    are choices, not tuned values.  ONE launch; float32 in a fixed order without transcendental functions, so the result equals
+    its NumPy restatement and repeats bit for bit."""
+    check_fuse_args(sigma, patch_radius, center_weight)
+    if (flows is None) == (positions is None):
+        raise ValueError('fuse_frames takes exactly one of flows and positions')
+    neighbours = _stacked(neighbours)
+    vectors = flows if flows is not None else positions
+    shape, in_dtype, K = _fuse_ahead(center, neighbours, vectors, skip, 'fuse_frames')
+    _fuse_entry(in_dtype, dtype)
+    shape4 = ((1,) + shape) if len(shape) == 3 else shape
+    c = _on_device(center).reshape(shape4)
+    stack = _on_device(neighbours).reshape((K,) + shape4)
+    v = _on_device(vectors).reshape((K,) + shape4[:3] + (2,))
+    s = _mask_on_device(skip, (K,) + shape4[:3])
+    out, weight = fuse_frames_launch(c, stack, v, None, s, positions is not None, sigma, patch_radius, center_weight, return_weight, dtype)
+    out = _dev.wrap(out.view(shape))
+    return (out, _dev.wrap(weight.view(shape[:-1]))) if return_weight else out
 
 
 # ------------------------------------------------------------------------------------------ the camera's motion (DESIGN.md section 27)

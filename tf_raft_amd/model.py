@@ -754,6 +754,46 @@ class RAFT:
         from .video import stabilize_video
         return stabilize_video(self, frames, model, radius, iterations, scale, batch_size, occlusion_test, return_motion)
 
+    def fuse_step(self, data, sigma=image_ops.FUSE_SIGMA, patch_radius=image_ops.FUSE_PATCH_RADIUS,
+                  center_weight=image_ops.FUSE_CENTER_WEIGHT, occlusion_test='consistency', **occlusion):
+        """Burst fusion: ``data = (center, neighbours)`` with ``center`` ``(N, H, W, 3)`` and ``neighbours``
+        ``(K, N, H, W, 3)`` of one type (uint8, or float32 on 0 .. 255; host or device; K in 1 .. 16) -> the centre fused with its
+        neighbours, a device tensor ``(N, H, W, 3)`` of the frames' type.  ONE ``predict_step_bidirectional`` call on the ``K * N``
+        pairs (centre, neighbour k) (``occlusion_test`` and ``**occlusion``: its ``alpha``, ``beta``, ``range_threshold``): its
+        ``forward`` is the flow centre -> neighbour k and its ``occluded_forward`` the ``skip`` of ONE
+        ``image_ops.fuse_frames_launch`` (``sigma``, ``patch_radius``, ``center_weight``) on the caller's own frames, at the frames'
+        own size -- so it works with every ``target_size`` / ``fit``.  The centre goes through the feature encoder K times (once per
+        pair; there is no forward path that shares it).  ``sigma``, ``patch_radius`` and ``center_weight`` are choices, not tuned
+        values: random weights and no footage say nothing about how the result looks."""
+        image_ops.check_fuse_args(sigma, patch_radius, center_weight)
+        image_ops.check_occlusion_test(occlusion_test)
+        unknown = set(occlusion) - {'alpha', 'beta', 'range_threshold'}
+        if unknown:
+            raise TypeError(f'fuse_step() got unexpected keyword arguments {sorted(unknown)}')
+        center, neighbours, *_ = data
+        neighbours = image_ops._stacked(neighbours)
+        shape, in_dtype = image_ops._frames_ahead(center, 'fuse_step')
+        nshape, ndtype = image_ops._shape_and_type(neighbours, 'fuse_step')
+        if len(shape) != 4 or shape[-1] != 3 or len(nshape) != 5 or nshape[1:] != shape or ndtype != in_dtype:
+            raise ValueError(f'expected a centre (N, H, W, 3) and neighbours (K, N, H, W, 3) of one type, got {shape} {in_dtype} / '
+                             f'{nshape} {ndtype}')
+        K, N, H, W, _ = nshape
+        image_ops._check_fuse_sizes(K, N, H, W, 3, 'fuse_step')
+        c, stack = image_ops._on_device(center), image_ops._on_device(neighbours)
+        first = c.unsqueeze(0).expand(K, N, H, W, 3).reshape(K * N, H, W, 3)
+        res = self.predict_step_bidirectional((first, stack.view(K * N, H, W, 3)), occlusion_test=occlusion_test, **occlusion)
+        flows = res.forward.as_subclass(torch.Tensor).contiguous().view(K, N, H, W, 2)
+        skip = res.occluded_forward.as_subclass(torch.Tensor).contiguous().view(K, N, H, W)
+        out, _ = image_ops.fuse_frames_launch(c, stack, flows, None, skip, False, sigma, patch_radius, center_weight)
+        return _dev.wrap(out)
+
+    def denoise_video(self, frames, radius=2, sigma=image_ops.FUSE_SIGMA, patch_radius=image_ops.FUSE_PATCH_RADIUS,
+                      center_weight=image_ops.FUSE_CENTER_WEIGHT, batch_size=4):
+        """One video ``(T, H, W, 3)`` filtered along its motion: every frame fused with up to ``radius`` frames on each side,
+        aligned by chained bidirectional flows (``tf_raft_amd.video.denoise_video``); a host array of the frames' shape and type."""
+        from .video import denoise_video
+        return denoise_video(self, frames, radius, sigma, patch_radius, center_weight, batch_size)
+
     def predict(self, x, batch_size=None, steps=None, output='flow', clip_flow=None, convert_to_bgr=False, rad_max=None, **kwargs):
         """``keras.Model.predict`` over ``predict_step`` (reference model.py:160-166): the final flow of every image
         pair as one host array ``(N, H, W, 2)``.
