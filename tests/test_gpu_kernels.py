@@ -746,6 +746,9 @@ def _update_inputs(rng, variant, B, h, w):
     return net, inp, corr, flow
 
 
+# Both shapes run the single-pair plan (direct, F(2x2) and F(2, 5) kernels).  The large-batch plans of launch_plan.h -- F(4x4, 3x3),
+# F(4, 5), the K-split / 64-channel workgroups -- meet the float64 oracle block by block in test_gpu_update_plans.py, with
+# bounds tied to the fp32 oracle's own error (update_plan_cases.py).
 @pytest.mark.parametrize('shape', [(2, 8, 12), (1, 56, 64)])
 def test_basic_update_block_matches_oracle(rng, shape):
     from oracle.layers import W, basic_update_block

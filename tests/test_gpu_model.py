@@ -353,8 +353,9 @@ def test_north_star_against_the_reference_source_output(case):
 
 def test_north_star_with_every_3x3_layer_on_winograd_f4x4(raft_opt):
     """The F(4x4,3x3) kernels are the default from 4 pairs on (checked per element by test_north_star_benchmarked_batches); here
-    the single-pair north-star case is run with ALL THREE 3x3 layers of the update block forced onto them (RAFT_CONV_WINO4 = 13:
-    at this size the K-split workgroups), free-running, 24 iterations, 1e-3 on every prediction."""
+    the single-pair north-star case is run with three of the FOUR 3x3 layers of the update block forced onto them (RAFT_CONV_WINO4
+    = 13: convc2, conv and fh1_mask0, at this size the K-split workgroups; convf2, bit 2, stays on the direct kernel -- it meets the
+    float64 oracle on F(4x4) in test_gpu_update_plans.py), free-running, 24 iterations, 1e-3 on every prediction."""
     import oracle
     import tf_raft_amd
     cond = _assert_oracle_is_well_conditioned('raft_448x512_seed0_it24_conditioned')
