@@ -386,7 +386,8 @@ int raft_interpolate_frames_u8(const uint8_t *image1, const uint8_t *image2, con
  * 0); flow_forward (S, N, H, W, 2), the flows frame t0 + s -> t0 + s + 1; flow_backward the same shape for t0 + s + 1 -> t0 + s,
  * or NULL (no consistency test); pos_out (S, N, P, 2) and lost_out uint8 (S, N, P): the state after every step; start int32
  * (N, P) or NULL: a point with start > t0 + s is copied through step s untouched (a query point given at a later frame).
- * Codes in lost: 0 = tracked, 1 = left the frame, 2 = failed the consistency test; any nonzero code is sticky, the point keeps
+ * Codes in lost: 0 = tracked, 1 = left the frame, 2 = failed the consistency test (3 = an empty slot comes in from
+ * raft_detect_points below and is never produced here); any nonzero code is sticky, the point keeps
  * the position it was last tracked at and its code, bit for bit.  One step of a tracked point at (x, y), with the sample of the
  * warp entries above (in frame iff 0 <= sx <= W - 1 and 0 <= sy <= H - 1, a NaN fails; bilinear, every operation rounded on its
  * own):
@@ -485,6 +486,77 @@ int raft_fuse_frames_u8_f32(const uint8_t *center, const uint8_t *neighbours, co
 int raft_fuse_frames_u8(const uint8_t *center, const uint8_t *neighbours, const int64_t *index, const float *vectors,
                         const uint8_t *skip, int absolute, float sigma, float center_weight, int patch_radius, uint8_t *dst,
                         float *weight, int K, int N, int H, int W, int C, void *stream);
+
+/* Corner detection and re-seeding for the point tracker (csrc/point_detect.hip): "good features to track"
+ * on the device.  frames (N, H, W, C), C in {1, 3}, uint8 or float32 on 0 .. 255 (float32 values are used as they are).
+ *
+ * The score, per pixel, all float32, every operation rounded on its own, never fused, in exactly this order:
+ *     g        = C == 1 ? the value : (0.299f * R + 0.587f * G) + 0.114f * B                    (uint8 converted to float first)
+ *     gx       = ((g[y-1][x+1] - g[y-1][x-1]) + 2.f * (g[y][x+1] - g[y][x-1])) + (g[y+1][x+1] - g[y+1][x-1])      (Sobel 3 x 3)
+ *     gy       = ((g[y+1][x-1] - g[y-1][x-1]) + 2.f * (g[y+1][x] - g[y-1][x])) + (g[y+1][x+1] - g[y-1][x+1])
+ *     a, b, c  = the sums of gx * gx, gx * gy, gy * gy over the (2 block_radius + 1)^2 window around the pixel: EACH WINDOW ROW
+ *                LEFT TO RIGHT first (r = p[-R]; r = r + p[-R + 1]; ...), THEN THE ROWS' SUMS TOP TO BOTTOM in the same manner
+ *     method 0 (min_eig, Shi-Tomasi):  d = a - c;  s = ((a + c) - sqrtf(d * d + 4.f * (b * b))) / 2.f      (sqrt correctly rounded)
+ *     method 1 (harris):               t = a + c;  s = (a * c - b * b) - harris_k * (t * t)
+ *     score    = s > 0 ? s : 0          (a NaN or a negative response is 0: every score is a non-negative float, and such floats
+ *                                        order like their bit patterns)
+ * A pixel closer than `border` to a frame edge (x < border or x >= W - border, likewise y) scores 0; border >= block_radius + 1, so
+ * no stencil of a scored pixel leaves the frame.  block_radius in 1 .. 3; harris_k finite and >= 0 (checked under both methods).
+ *   raft_corner_score_*: score (N, H, W); smax (N) or NULL: the per-image maximum of the score (an atomic maximum over the bits:
+ *     order-independent), zeroed by the entry itself.  One launch.
+ *
+ * raft_detect_points runs the score into its workspace and selects points from it (frames_u8: 1 = uint8 frames, 0 = float32):
+ *     thr[n]   = quality_level * smax[n], ONE float32 product; quality_level in [0, 1)
+ *     key(p)   = (uint64)score bits << 32 | (0xFFFFFFFF - raster index y * W + x): unique within an image; of two equal scores the
+ *                EARLIER pixel in raster order has the larger key
+ *     p is a LOCAL MAXIMUM iff its key is the largest in its (2 min_distance + 1)^2 window, clipped to the frame (min_distance in
+ *                1 .. RAFT_DETECT_MAX_MIN_DISTANCE).  Any two local maxima are more than min_distance apart in Chebyshev
+ *                distance, so an image holds at most ceil(H / (m + 1)) * ceil(W / (m + 1)) of them: the workspace's bound.
+ *     a local maximum is a CANDIDATE iff score > 0, score >= thr[n], mask == NULL or mask[n, y, x] != 0 (uint8 (N, H, W)), and it
+ *                is not within Chebyshev distance min_distance of a live point of `avoid`: avoid_points (N, avoid_P, 2) as (x, y)
+ *                with avoid_lost uint8 (N, avoid_P), code 0 = live (both NULL: none).  A live point (px, py) that is in frame
+ *                (0 <= px <= W - 1 and 0 <= py <= H - 1; a NaN is not) bars the integer pixels ceilf(px - (float)m) .. floorf(px +
+ *                (float)m) by the same in y; any other point bars nothing.  Mask and avoid apply AFTER the suppression: the
+ *                neighbours of a barred maximum do not move up.
+ *     the max_points (1 .. RAFT_DETECT_MAX_POINTS) candidates with the LARGEST KEYS per image, largest first, fill the slots:
+ *                points (N, K, 2) float32 (x, y), integer-valued; scores (N, K); count (N) int32 = the number of filled slots;
+ *                lost (N, K) uint8 or NULL: 0 for a filled slot, 3 for an empty one.  Empty slots hold (-1, -1) and score 0.
+ * Codes in `lost` across the tracker: 0 = tracked, 1 = left the frame, 2 = failed the consistency test (raft_track_points_f32),
+ * 3 = EMPTY: the slot never held a point.  raft_track_points_f32 keeps any nonzero code and its position bit for bit, so 3 rides
+ * through it untouched until raft_refill_points fills the slot.
+ * Candidates are gathered through an atomic slot counter, in an order that differs from run to run; keys are unique, so they are a
+ * set, and the sorted top-K of a set is the same bits every run.  workspace: raft_detect_points_workspace_bytes(N, H, W,
+ * min_distance) bytes (0: the sizes are refused), 8-byte aligned, need not be cleared.  Up to two memsets and four launches on
+ * `stream` (score; occupancy stamp, with avoid only; suppression + candidates; one workgroup per image selects and sorts).
+ * Errors, in this order: RAFT_E_NULL for a NULL frames, score / points, scores, count or workspace, or only one of the avoid pair;
+ * RAFT_E_SHAPE for a non-positive size, C outside {1, 3}, H * W >= 2^32, N * H * W >= 2^31, block_radius outside 1 .. 3, a method
+ * or frames_u8 other than 0 or 1, a harris_k that is negative or not finite, border < block_radius + 1, H or W <= 2 * border,
+ * max_points or min_distance out of range, a quality_level outside [0, 1) or NaN, N * avoid_P * 2 >= 2^31; RAFT_E_ALIGN for a
+ * workspace that is not 8-byte aligned or a float32 / int32 array that is not 4-byte aligned.  All checks precede the first launch.
+ *
+ * raft_refill_points puts new points into the lost slots of a tracker's state: pos_in (N, P, 2), lost_in uint8 (N, P), new_points
+ * (N, K, 2) strongest first with new_count (N) int32 (clamped to 0 .. K), the frame index t >= 0.  Per video, the slots with a
+ * nonzero code in ascending slot order take new points 0, 1, ... until either side runs out: the r-th such slot (r < new_count[n])
+ * gets pos_out = new_points[n, r], lost_out = 0, born = t, ids = next_id[n] + r; every other slot copies pos and lost through and
+ * leaves born and ids as they are; next_id[n] grows by the number of refilled slots.  born, ids (N, P) int32 and next_id (N) int32
+ * are updated in place.  One launch, one workgroup per video, an ordered prefix scan over the slots, no atomics; pos_out == pos_in
+ * and lost_out == lost_in are allowed (a thread reads its own slot before it writes it).  Ids never repeat within a video (up to
+ * 2^31 of them).  Errors: RAFT_E_NULL for any NULL pointer; RAFT_E_SHAPE for a non-positive N or P, K outside 1 ..
+ * RAFT_DETECT_MAX_POINTS, a negative t, N * P * 2 >= 2^31; RAFT_E_ALIGN for a float32 / int32 array that is not 4-byte aligned. */
+#define RAFT_DETECT_MAX_POINTS 4096
+#define RAFT_DETECT_MAX_MIN_DISTANCE 15
+int raft_corner_score_f32(const float *frames, float *score, float *smax, int N, int H, int W, int C, int block_radius, int method,
+                          float harris_k, int border, void *stream);
+int raft_corner_score_u8_f32(const uint8_t *frames, float *score, float *smax, int N, int H, int W, int C, int block_radius, int method,
+                             float harris_k, int border, void *stream);
+int64_t raft_detect_points_workspace_bytes(int N, int H, int W, int min_distance);
+int raft_detect_points(const void *frames, int frames_u8, const uint8_t *mask, const float *avoid_points, const uint8_t *avoid_lost,
+                       int64_t avoid_P, float *points, float *scores, int32_t *count, uint8_t *lost, int N, int H, int W, int C,
+                       int max_points, int min_distance, float quality_level, int block_radius, int method, float harris_k, int border,
+                       void *workspace, void *stream);
+int raft_refill_points(const float *pos_in, const uint8_t *lost_in, const float *new_points, const int32_t *new_count, int t,
+                       float *pos_out, uint8_t *lost_out, int32_t *born, int32_t *ids, int32_t *next_id, int N, int64_t P, int K,
+                       void *stream);
 
 /* ------------------------------------------------------------------ training augmentation */
 

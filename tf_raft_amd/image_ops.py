@@ -56,6 +56,12 @@ their flows (or at ``track``'s positions) and averaged under a patch-based Cauch
 out, in ONE launch that repeats bit for bit (``raft_fuse_frames_*``, tf_raft_amd/csrc/frame_fuse.hip); ``RAFT.fuse_step`` and
 ``tf_raft_amd.video.denoise_video`` are burst fusion and video denoising above the model.
 
+``detect_points`` finds the points worth following: a Shi-Tomasi / Harris corner score from Sobel
+derivatives (``corner_score``), non-maximum suppression over a ``(2 * min_distance + 1)^2`` window and the ``max_points`` strongest
+survivors per image, strongest first, all on the device and bit for bit the same every run (``raft_detect_points``,
+tf_raft_amd/csrc/point_detect.hip); ``refill_points_launch`` puts new points into the slots a tracker has lost
+(``raft_refill_points``).  ``tf_raft_amd.video.FlowTracker`` uses both: ``points=None`` and ``replenish=True``.
+
 ``forward_interpolate`` projects a low-resolution flow forward along itself: the start of the next pair's
 recurrence in a video stream (``raft_forward_interpolate_f32``, tf_raft_amd/csrc/flow_init.hip; ``tf_raft_amd.video``).
 
@@ -1288,6 +1294,272 @@ def track(points, forward, backward=None, lost=None, start=None, t0=0, alpha=CON
     if len(fshape) == 4:
         pos, codes = pos[0], codes[0]
     return _dev.wrap(pos), _dev.wrap(codes)
+
+
+# ------------------------------------------------------------------------------------------ corner detection
+DETECT_MAX_POINTS = _ffi._CONSTANTS['RAFT_DETECT_MAX_POINTS']
+DETECT_MAX_MIN_DISTANCE = _ffi._CONSTANTS['RAFT_DETECT_MAX_MIN_DISTANCE']
+DETECT_MAX_BLOCK_RADIUS = 3                                           # csrc/point_detect.hip kMaxBlockRadius
+# choices, not tuned values: OpenCV's qualityLevel convention and blockSize = 3, Harris' usual k
+DETECT_MIN_DISTANCE, DETECT_QUALITY_LEVEL, DETECT_BLOCK_RADIUS, DETECT_HARRIS_K, DETECT_BORDER = 7, 0.01, 1, 0.04, 8
+DETECT_METHODS = {'min_eig': 0, 'harris': 1}
+LOST_EMPTY = 3                                                        # the code of a slot that never held a point
+
+
+def _int_in(v, name, lo, hi):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+        raise ValueError(f'{name} must be an integer in {lo} .. {hi}, got {v!r}')
+    return int(v)
+
+
+def check_score_args(block_radius=DETECT_BLOCK_RADIUS, method='min_eig', harris_k=DETECT_HARRIS_K, border=DETECT_BORDER):
+    """The corner score's parameters as ``(block_radius, method code, harris_k, border)``: ``block_radius`` an integer in 1 .. 3,
+    ``method`` 'min_eig' or 'harris', ``harris_k`` a number (no bool) that is finite and >= 0 as a float32, ``border`` an integer
+    >= ``block_radius + 1``."""
+    r = _int_in(block_radius, 'block_radius', 1, DETECT_MAX_BLOCK_RADIUS)
+    if not isinstance(method, str) or method not in DETECT_METHODS:
+        raise ValueError(f'method must be one of {sorted(DETECT_METHODS)}, got {method!r}')
+    k = _float32_value(harris_k, 'harris_k')
+    if not (np.isfinite(k) and k >= 0):
+        raise ValueError(f'harris_k must be finite and >= 0 as a float32, got {harris_k!r}')
+    if isinstance(border, (bool, np.bool_)) or not isinstance(border, (int, np.integer)) or not r + 1 <= border <= 1 << 29:
+        raise ValueError(f'border must be an integer >= block_radius + 1 = {r + 1}, got {border!r}')
+    return r, DETECT_METHODS[method], k, int(border)
+
+
+def check_detect_args(max_points, min_distance=DETECT_MIN_DISTANCE, quality_level=DETECT_QUALITY_LEVEL):
+    """``(max_points, min_distance, quality_level)`` of a detection: integers in 1 .. 4096 and 1 .. 15, and a number (no bool)
+    whose float32 value lies in ``[0, 1)``."""
+    K = _int_in(max_points, 'max_points', 1, DETECT_MAX_POINTS)
+    m = _int_in(min_distance, 'min_distance', 1, DETECT_MAX_MIN_DISTANCE)
+    q = _float32_value(quality_level, 'quality_level')
+    if not 0.0 <= q < 1.0:
+        raise ValueError(f'quality_level must lie in [0, 1) as a float32, got {quality_level!r}')
+    return K, m, q
+
+
+DETECT_OPTIONS = ('min_distance', 'quality_level', 'block_radius', 'method', 'harris_k', 'border', 'mask')
+
+
+def check_detect_options(detect, max_points=1):
+    """``detect=dict(...)`` of the tracker: a dict (None: empty) of ``DETECT_OPTIONS`` whose values pass the checks of
+    ``detect_points``; returns a copy."""
+    if detect is None:
+        return {}
+    if not isinstance(detect, dict) or not set(detect) <= set(DETECT_OPTIONS):
+        raise ValueError(f'detect must be a dict of {", ".join(DETECT_OPTIONS)}, got {detect!r}')
+    detect = dict(detect)
+    check_detect_args(max_points, detect.get('min_distance', DETECT_MIN_DISTANCE), detect.get('quality_level', DETECT_QUALITY_LEVEL))
+    check_score_args(detect.get('block_radius', DETECT_BLOCK_RADIUS), detect.get('method', 'min_eig'),
+                     detect.get('harris_k', DETECT_HARRIS_K), detect.get('border', DETECT_BORDER))
+    if detect.get('mask') is not None:
+        shape, dtype = _shape_and_type(detect['mask'], 'detect')
+        if len(shape) != 3 or dtype not in (torch.uint8, torch.bool):
+            raise ValueError(f'the mask of detect is uint8 or bool (N, H, W), got {shape} {dtype}')
+    return detect
+
+
+def _check_detect_sizes(N, H, W, C, border, what):
+    if C not in (1, 3):
+        raise ValueError(f'{what} takes frames of 1 or 3 channels, got {C}')
+    if H <= 2 * border or W <= 2 * border:
+        raise ValueError(f'{what}: H and W must be greater than 2 * border = {2 * border}, got {H} x {W}')
+    if H * W >= 1 << 32 or N * H * W >= 1 << 31:
+        raise ValueError(f'{what} takes fewer than 2^31 pixels in all, got {N} x {H} x {W}: too large')
+
+
+def _check_detect_frames(frames, what):
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 4 or 0 in frames.shape or not frames.is_contiguous():
+        raise ValueError(f'{what}: expected contiguous frames (N, H, W, C), got '
+                         f'{tuple(frames.shape) if hasattr(frames, "shape") else type(frames)}')
+    if frames.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f'{what} takes uint8 or float32 frames, got {frames.dtype}')
+
+
+def corner_score_launch(frames: torch.Tensor, block_radius: int = DETECT_BLOCK_RADIUS, method: str = 'min_eig',
+                        harris_k: float = DETECT_HARRIS_K, border: int = DETECT_BORDER, want_max: bool = False, out=None):
+    """The launch itself (``raft_corner_score_*``): contiguous device frames ``(N, H, W, C)``, uint8 or
+    float32, ``C`` 1 or 3 -> ``(score (N, H, W) float32, smax (N,) float32 or None)`` on the CURRENT stream (plain tensors)."""
+    r, code, k, border = check_score_args(block_radius, method, harris_k, border)
+    _check_detect_frames(frames, 'corner_score')
+    N, H, W, Cn = frames.shape
+    _check_detect_sizes(N, H, W, Cn, border, 'corner_score')
+    out = _check_out(out, (N, H, W), torch.float32, frames.device)
+    smax = torch.empty((N,), device=frames.device, dtype=torch.float32) if want_max else None
+    fn, src = _source_entry(frames, 'corner_score')
+    with torch.cuda.device(frames.device):
+        check(fn(_dev.ptr(src), _dev.ptr(out), _dev.ptr(smax) if smax is not None else None, N, H, W, Cn, r, code, k, border,
+                 _dev.stream_ptr()), 'corner_score')
+    return out, smax
+
+
+def corner_score(frames, block_radius=DETECT_BLOCK_RADIUS, method='min_eig', harris_k=DETECT_HARRIS_K, border=DETECT_BORDER,
+                 return_max=False):
+    """The corner score of every pixel: ``(H, W, C)`` or ``(N, H, W, C)`` frames (NumPy or torch, host or
+    device, uint8, or float32 on 0 .. 255; float64 narrows; 1 or 3 channels) -> a float32 device tensor of the frames' leading
+    shape.  ``method='min_eig'`` is the smaller eigenvalue of the structure tensor (Shi-Tomasi), ``'harris'`` ``det - harris_k *
+    trace^2``, of Sobel derivatives summed over a ``(2 * block_radius + 1)^2`` window; negative responses and NaNs are 0, and so
+    are the pixels closer than ``border`` to a frame edge.  ``return_max=True`` also returns the per-image maximum.  Every operation
+    is one float32 operation in a fixed order: the map equals its NumPy restatement bit for bit."""
+    r, _, k, border = check_score_args(block_radius, method, harris_k, border)
+    shape, _ = _frames_ahead(frames, 'corner_score')
+    shape4 = ((1,) + shape) if len(shape) == 3 else shape
+    _check_detect_sizes(shape4[0], shape4[1], shape4[2], shape4[3], border, 'corner_score')
+    score, smax = corner_score_launch(_on_device(frames).reshape(shape4), r, method, k, border, return_max)
+    score = _dev.wrap(score.view(shape[:-1]))
+    return (score, _dev.wrap(smax.view(shape[:-3]))) if return_max else score
+
+
+def detect_workspace_bytes(N, H, W, min_distance=DETECT_MIN_DISTANCE):
+    """``raft_detect_points_workspace_bytes``: the bytes a detection on ``(N, H, W)`` frames needs (host arithmetic only)."""
+    nbytes = int(_ffi.load_library().raft_detect_points_workspace_bytes(int(N), int(H), int(W), int(min_distance)))
+    if nbytes <= 0:
+        raise ValueError(f'a detection takes fewer than 2^31 pixels in all and min_distance in 1 .. {DETECT_MAX_MIN_DISTANCE}, got '
+                         f'{N} x {H} x {W}, min_distance = {min_distance}: too large')
+    return nbytes
+
+
+def _check_avoid(avoid, N, device=None):
+    """``avoid=(points (N, P, 2) float32, lost (N, P) uint8 / bool)`` by shape and type alone; returns P."""
+    if not isinstance(avoid, (tuple, list)) or len(avoid) != 2:
+        raise ValueError('avoid must be a pair (points (N, P, 2), lost (N, P))')
+    (N2, P) = _points_ahead(avoid[0], avoid[1], None, 'avoid')
+    if avoid[1] is None:
+        raise ValueError('avoid must be a pair (points (N, P, 2), lost (N, P))')
+    if N2 != N:
+        raise ValueError(f'avoid holds points of {N2} videos, the frames are {N}')
+    if N * P * 2 >= 1 << 31:
+        raise ValueError(f'avoid takes fewer than 2^30 points, got {N} x {P}: too large')
+    return P
+
+
+def detect_points_launch(frames: torch.Tensor, max_points: int, min_distance: int = DETECT_MIN_DISTANCE,
+                         quality_level: float = DETECT_QUALITY_LEVEL, block_radius: int = DETECT_BLOCK_RADIUS, method: str = 'min_eig',
+                         harris_k: float = DETECT_HARRIS_K, border: int = DETECT_BORDER, mask=None, avoid=None, want_lost: bool = False,
+                         out=None, workspace=None):
+    """The launches themselves (``raft_detect_points``): contiguous device frames ``(N, H, W, C)``, uint8 or
+    float32, ``C`` 1 or 3; an optional contiguous uint8 ``mask`` ``(N, H, W)`` (nonzero = allowed); an optional pair ``avoid =
+    (points (N, P, 2) float32, lost (N, P) uint8)`` of contiguous device tensors -> ``(points (N, K, 2) float32, scores (N, K)
+    float32, count (N,) int32, lost (N, K) uint8 or None)`` on the CURRENT stream (plain tensors).  ``out``: a tuple of four tensors
+    to write them into (the last may be None without ``want_lost``); ``workspace``: a contiguous uint8 device tensor of at least
+    ``detect_workspace_bytes(N, H, W, min_distance)`` bytes, 8-byte aligned (None: the stream's grow-only workspace)."""
+    K, m, q = check_detect_args(max_points, min_distance, quality_level)
+    r, code, k, border = check_score_args(block_radius, method, harris_k, border)
+    _check_detect_frames(frames, 'detect_points')
+    N, H, W, Cn = frames.shape
+    _check_detect_sizes(N, H, W, Cn, border, 'detect_points')
+    dev = frames.device
+    if mask is not None:
+        mask = _check_out(mask, (N, H, W), torch.uint8, dev)
+    P = 0
+    if avoid is not None:
+        P = _check_avoid(avoid, N)
+        avoid = (_check_out(avoid[0], (N, P, 2), torch.float32, dev), _check_out(avoid[1], (N, P), torch.uint8, dev))
+    if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 4):
+        raise ValueError('out must be a tuple (points (N, K, 2), scores (N, K), count (N,), lost (N, K) or None)')
+    out = (None,) * 4 if out is None else out
+    points = _check_out(out[0], (N, K, 2), torch.float32, dev)
+    scores = _check_out(out[1], (N, K), torch.float32, dev)
+    count = _check_out(out[2], (N,), torch.int32, dev)
+    lost = _check_out(out[3], (N, K), torch.uint8, dev, alloc=bool(want_lost))
+    nbytes = detect_workspace_bytes(N, H, W, m)
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1
+                                  or workspace.numel() < nbytes or workspace.device != dev or not workspace.is_contiguous()
+                                  or workspace.data_ptr() % 8):
+        raise ValueError(f'workspace must be a contiguous uint8 tensor of at least {nbytes} bytes on {dev}, 8-byte aligned')
+    with torch.cuda.device(dev):
+        if workspace is None:
+            from . import losses
+            workspace = losses._workspace(dev, nbytes)
+        check(_dev.lib().raft_detect_points(_dev.ptr(frames), int(frames.dtype == torch.uint8), _dev.ptr(mask) if mask is not None else None,
+                                            _dev.ptr(avoid[0]) if avoid is not None else None,
+                                            _dev.ptr(avoid[1]) if avoid is not None else None, P, _dev.ptr(points), _dev.ptr(scores),
+                                            _dev.ptr(count), _dev.ptr(lost) if lost is not None else None, N, H, W, Cn, K, m, q, r, code,
+                                            k, border, _dev.ptr(workspace), _dev.stream_ptr()), 'detect_points')
+    return points, scores, count, lost
+
+
+def detect_points(frames, max_points, min_distance=DETECT_MIN_DISTANCE, quality_level=DETECT_QUALITY_LEVEL,
+                  block_radius=DETECT_BLOCK_RADIUS, method='min_eig', harris_k=DETECT_HARRIS_K, border=DETECT_BORDER, mask=None,
+                  avoid=None, return_lost=False):
+    """Good features to track: ``(N, H, W, C)`` frames (NumPy or torch, host or device, uint8, or float32 on
+    0 .. 255; 1 or 3 channels) -> ``(points (N, K, 2) float32, scores (N, K) float32, count (N,) int32)`` as device tensors, ``K =
+    max_points`` (1 .. 4096): per image the up to ``K`` strongest corners as ``(x, y)``, STRONGEST FIRST; the slots from
+    ``count[n]`` on hold ``(-1, -1)`` and score 0.  ``return_lost=True`` also returns ``lost (N, K)`` uint8, 0 for a filled slot
+    and 3 for an empty one: with ``points`` it is the state a tracker starts from (``track`` carries code 3 through untouched).
+
+    A pixel is taken iff its ``corner_score`` is the largest in its ``(2 * min_distance + 1)^2`` window (of equal scores the
+    earlier pixel in raster order wins), positive, and at least ``quality_level`` times the image's largest score; ``mask`` (uint8
+    / bool ``(N, H, W)``, nonzero = allowed) and ``avoid = (points (N, P, 2), lost (N, P))`` -- no new point within ``min_distance``
+    (Chebyshev) of a point whose code is 0 -- are applied after that suppression.  The window replaces OpenCV's greedy
+    minimum-distance rule: any two points are more than ``min_distance`` apart in both methods, but the sets differ.  The result
+    equals its NumPy restatement bit for bit and repeats bit for bit."""
+    K, m, q = check_detect_args(max_points, min_distance, quality_level)
+    r, _, k, border = check_score_args(block_radius, method, harris_k, border)
+    shape, _ = _frames_ahead(frames, 'detect_points')
+    if len(shape) != 4:
+        raise ValueError(f'detect_points expects frames (N, H, W, C), got {shape}')
+    _check_detect_sizes(shape[0], shape[1], shape[2], shape[3], border, 'detect_points')
+    _mask_ahead(mask, shape[:3], 'detect_points')
+    if avoid is not None:
+        _check_avoid(avoid, shape[0])
+    detect_workspace_bytes(shape[0], shape[1], shape[2], m)
+    x = _on_device(frames)
+    if avoid is not None:
+        avoid = (_on_device(avoid[0]), _on_device(avoid[1]).view(torch.uint8))
+    res = detect_points_launch(x, K, m, q, r, method, k, border, _mask_on_device(mask, shape[:3]), avoid, return_lost)
+    return tuple(_dev.wrap(t) for t in (res if return_lost else res[:3]))
+
+
+def refill_points_launch(pos: torch.Tensor, lost: torch.Tensor, new_points: torch.Tensor, new_count: torch.Tensor, t: int,
+                         born: torch.Tensor, ids: torch.Tensor, next_id: torch.Tensor, out=None):
+    """The launch itself (``raft_refill_points``): a tracker's state ``pos (N, P, 2)`` float32 and ``lost
+    (N, P)`` uint8, a detection's ``new_points (N, K, 2)`` float32 (strongest first) with ``new_count (N,)`` int32, and the frame
+    index ``t`` -> ``(positions, lost)`` (``out``: a pair to write them into; ``out=(pos, lost)`` refills in place).  Per video
+    the slots with a nonzero code take the new points in ascending slot order until either side runs out: such a slot gets the
+    new position, code 0, ``born = t`` and the next id of the video.  ``born``, ``ids`` ``(N, P)`` and ``next_id`` ``(N,)``
+    (int32) are updated in place.  One launch on the CURRENT stream; all tensors contiguous on one device."""
+    t = check_track_time(t)
+    if not isinstance(pos, torch.Tensor) or pos.dim() != 3 or pos.shape[-1] != 2 or pos.dtype != torch.float32 or not pos.is_contiguous() \
+            or 0 in pos.shape:
+        raise ValueError(f'expected contiguous float32 positions (N, P, 2), got '
+                         f'{(tuple(pos.shape), pos.dtype) if isinstance(pos, torch.Tensor) else type(pos)}')
+    N, P, _ = pos.shape
+    dev = pos.device
+    if N * P * 2 >= 1 << 31:
+        raise ValueError(f'a refill takes fewer than 2^30 points, got {N} x {P}: too large')
+    lost = _check_out(lost, (N, P), torch.uint8, dev)
+    if not isinstance(new_points, torch.Tensor) or new_points.dim() != 3 or new_points.shape[0] != N or new_points.shape[2] != 2 \
+            or not 1 <= new_points.shape[1] <= DETECT_MAX_POINTS:
+        raise ValueError(f'expected new points ({N}, K, 2) with K in 1 .. {DETECT_MAX_POINTS}, got '
+                         f'{tuple(new_points.shape) if isinstance(new_points, torch.Tensor) else type(new_points)}')
+    K = new_points.shape[1]
+    new_points = _check_out(new_points, (N, K, 2), torch.float32, dev)
+    new_count = _check_out(new_count, (N,), torch.int32, dev)
+    born = _check_out(born, (N, P), torch.int32, dev)
+    ids = _check_out(ids, (N, P), torch.int32, dev)
+    next_id = _check_out(next_id, (N,), torch.int32, dev)
+    if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+        raise ValueError('out must be a pair (positions (N, P, 2), lost (N, P))')
+    pos_out = _check_out(None if out is None else out[0], (N, P, 2), torch.float32, dev)
+    lost_out = _check_out(None if out is None else out[1], (N, P), torch.uint8, dev)
+    with torch.cuda.device(dev):
+        check(_dev.lib().raft_refill_points(_dev.ptr(pos), _dev.ptr(lost), _dev.ptr(new_points), _dev.ptr(new_count), t, _dev.ptr(pos_out),
+                                            _dev.ptr(lost_out), _dev.ptr(born), _dev.ptr(ids), _dev.ptr(next_id), N, P, K,
+                                            _dev.stream_ptr()), 'refill_points')
+    return pos_out, lost_out
+
+
+def tracker_ids(lost: torch.Tensor, start=None):
+    """What a replenishing tracker starts from for the state ``lost (N, P)``: ``(born, ids, next_id)`` int32 device tensors --
+    ``born`` the slot's ``start`` (or 0), ``ids`` ``0 .. P - 1``, both -1 for an empty slot (code 3); ``next_id`` ``P``."""
+    N, P = lost.shape
+    empty = lost == LOST_EMPTY
+    minus = torch.full((N, P), -1, device=lost.device, dtype=torch.int32)
+    born = torch.zeros((N, P), device=lost.device, dtype=torch.int32) if start is None else start.to(torch.int32)
+    ids = torch.arange(P, device=lost.device, dtype=torch.int32).expand(N, P)
+    return (torch.where(empty, minus, born).contiguous(), torch.where(empty, minus, ids).contiguous(),
+            torch.full((N,), P, device=lost.device, dtype=torch.int32))
 
 
 # ------------------------------------------------------------------------------------------ temporal fusion (DESIGN.md section 28)

@@ -707,21 +707,24 @@ class RAFT:
         return predict_video(self, frames, warm_start, batch_size, steps)
 
     def tracker(self, points, start=None, consistency=True, warm_start=False, alpha=image_ops.CONSISTENCY_ALPHA,
-                beta=image_ops.CONSISTENCY_BETA):
+                beta=image_ops.CONSISTENCY_BETA, max_points=None, replenish=False, detect=None):
         """Points followed through a stream of frames (``tf_raft_amd.video.FlowTracker``): ``points``
         ``(N, P, 2)`` float32 as ``(x, y)`` in pixels of the frames; ``push(frames)`` returns ``(positions (N, P, 2), lost (N, P))``
         in the pushed frames (None after the first push).  ``consistency=True`` tests every step against the backward flow of a
         bidirectional pass; ``consistency=False`` rides on ``video(warm_start)`` and tests only the frame borders.  ``alpha`` /
-        ``beta`` are UnFlow's values, not tuned ones."""
+        ``beta`` are UnFlow's values, not tuned ones.  ``points=None`` with ``max_points=K`` detects the points in the first
+        pushed frames (``image_ops.detect_points`` with the options of ``detect=dict(...)``, DESIGN.md section 29);
+        ``replenish=True`` refills lost slots from a detection on every pushed frame and gives the tracker ``.ids`` and ``.born``."""
         from .video import FlowTracker
-        return FlowTracker(self, points, start, consistency, warm_start, alpha, beta)
+        return FlowTracker(self, points, start, consistency, warm_start, alpha, beta, max_points, replenish, detect)
 
     def track_video(self, frames, points, start=None, consistency=True, batch_size=4, alpha=image_ops.CONSISTENCY_ALPHA,
-                    beta=image_ops.CONSISTENCY_BETA):
+                    beta=image_ops.CONSISTENCY_BETA, max_points=None, replenish=False, detect=None):
         """``points`` ``(P, 2)`` followed through one video ``(T, H, W, 3)`` as host arrays ``(positions (T, P, 2), lost (T, P))``,
-        row 0 the points themselves (``tf_raft_amd.video.track_video``)."""
+        row 0 the points themselves (``tf_raft_amd.video.track_video``).  ``points=None`` with ``max_points=K`` detects them in
+        frame 0; ``replenish=True`` refills lost slots at the chunk boundaries and also returns ``ids (T, P)``."""
         from .video import track_video
-        return track_video(self, frames, points, start, consistency, batch_size, alpha, beta)
+        return track_video(self, frames, points, start, consistency, batch_size, alpha, beta, max_points, replenish, detect)
 
     def camera_motion_step(self, data, model='affine', occlusion_test='consistency', iterations=image_ops.MOTION_ITERATIONS,
                            scale=image_ops.MOTION_SCALE, threshold=1.0, **occlusion):

@@ -150,6 +150,50 @@ def predict_video(model, frames, warm_start=False, batch_size=None, steps=None):
     return np.concatenate(flows, axis=0)
 
 
+def _detect_frames(t):
+    """Device frames as the detector takes them: uint8 and float32 as they are, any other type as float32."""
+    t = t.detach().as_subclass(torch.Tensor)
+    return (t if t.dtype in (torch.uint8, torch.float32) else t.to(torch.float32)).contiguous()
+
+
+def _check_seeding(points, start, max_points, replenish, detect, lead):
+    """The arguments ``points=None`` / ``max_points`` / ``replenish`` / ``detect`` of the tracker and of ``track_video``, checked
+    before anything reaches a device: ``(K of the detections or None, detect options without the mask, the mask)``."""
+    if not isinstance(replenish, (bool, np.bool_)):
+        raise ValueError(f'replenish must be True or False, got {replenish!r}')
+    if max_points is not None:
+        image_ops.check_detect_args(max_points)
+    if points is None:
+        if max_points is None:
+            raise ValueError('points=None asks the tracker to detect its points: pass max_points=K with it')
+        if start is not None:
+            raise ValueError('start belongs to given points: detected points begin at the first frame')
+        K = int(max_points)
+    else:
+        K = int(max_points) if max_points is not None else min(lead[-1], image_ops.DETECT_MAX_POINTS)
+    if points is not None and not replenish:
+        if detect is not None:
+            raise ValueError('detect belongs to points=None or replenish=True')
+        return None, {}, None
+    options = image_ops.check_detect_options(detect, K)
+    mask = options.pop('mask', None)
+    return K, options, mask
+
+
+def _check_detect_mask(mask, shape3):
+    """The detector's mask against frames of ``shape3 = (N, H, W)``, by shape alone (nothing reaches a device)."""
+    if mask is not None:
+        mshape, _ = image_ops._shape_and_type(mask, 'detect')
+        if tuple(mshape) != tuple(shape3):
+            raise ValueError(f'the mask of detect must be {tuple(shape3)} for these frames, got {tuple(mshape)}')
+
+
+def _detect_mask(mask, shape3):
+    """The detector's mask on the device; a wrong shape fails before any launch."""
+    _check_detect_mask(mask, shape3)
+    return image_ops._mask_on_device(mask, tuple(shape3))
+
+
 class FlowTracker:
     """``model.tracker(points, start=None, consistency=True, warm_start=False, alpha=..., beta=...)``: ``points`` ``(N, P, 2)``
     float32 are ``(x, y)`` in pixels of the frames' own size, ``P`` query points in each of N videos.  ``push(frames)`` takes one
@@ -162,15 +206,29 @@ class FlowTracker:
     ``consistency=True`` keeps the previous frames and runs ``predict_step_bidirectional((previous, frames))`` per push, so a
     frame is encoded twice over its life; ``consistency=False`` rides on ``FlowVideo(model, warm_start)`` (every frame encoded
     once) and tests only the frame borders.  It chains the flows the predictor RETURNS, at the frames' own size, so it works
-    with every ``target_size`` / ``fit``.  ``reset()`` goes back to the given points and forgets the stream."""
+    with every ``target_size`` / ``fit``.  ``reset()`` goes back to the given points and forgets the stream.
+
+    ``points=None`` with ``max_points=K``: the first pushed frames are run through
+    ``image_ops.detect_points`` with the options of ``detect=dict(min_distance, quality_level, block_radius, method, harris_k,
+    border, mask)``; ``P = K``, N is learned at that push, and the slots the detector could not fill carry the code 3 (empty) at
+    ``(-1, -1)``.  ``replenish=True``: after every push's track launch the pushed frames are run through the detector, with the
+    tracker's live points as ``avoid`` and the same ``min_distance``, and the new points fill the slots with a nonzero code in
+    ascending slot order, strongest point first (``image_ops.refill_points_launch``); the tracker then has ``.ids`` and ``.born``
+    ``(N, P)`` int32 device tensors: the identity of the point a slot holds (the given points are 0 .. P - 1, every refill takes
+    the next number of its video, an empty slot has -1) and the index of the pushed frame it came in at (``start`` or 0 for the
+    given points).  With given ``points`` ``P`` is theirs; ``max_points`` then only limits a push's detections (default
+    ``min(P, 4096)``).  Detection runs on the caller's frames at their own size and touches neither the predictor nor its
+    schedule."""
 
     def __init__(self, model, points, start=None, consistency=True, warm_start=False, alpha=image_ops.CONSISTENCY_ALPHA,
-                 beta=image_ops.CONSISTENCY_BETA):
+                 beta=image_ops.CONSISTENCY_BETA, max_points=None, replenish=False, detect=None):
         self.alpha, self.beta = image_ops.check_consistency_args(alpha, beta)
         self.consistency = bool(consistency)
         if self.consistency and warm_start:
             raise ValueError('warm_start belongs to the one-directional stream: pass consistency=False with it')
-        self._lead = image_ops._points_ahead(points, None, start, 'tracker')
+        self._lead = None if points is None else image_ops._points_ahead(points, None, start, 'tracker')
+        self._K, self._detect, self._mask = _check_seeding(points, start, max_points, replenish, detect, self._lead)
+        self.replenish = bool(replenish)
         self.model = model
         self._video = None if self.consistency else FlowVideo(model, warm_start)
         self._given, self._given_start = points, start
@@ -181,24 +239,42 @@ class FlowTracker:
         self._signature = None
         self._previous = None                    # consistency: the last frames, as they came
         self._pos = self._lost = None
+        self.ids = self.born = self._next_id = self._mask_dev = None
         self._t = 0                              # frames pushed so far
         if self._video is not None:
             self._video.reset()
 
+    def _seed(self, frames):
+        """The first push of a tracker that detects or replenishes: the state, and who is in it."""
+        if self._given is None:
+            self._pos, _, _, self._lost = image_ops.detect_points_launch(frames, self._K, mask=self._mask_dev, want_lost=True,
+                                                                         **self._detect)
+        if self.replenish:
+            if self._lost is None:
+                self._lost = torch.zeros(self._points.shape[:2], device=self._points.device, dtype=torch.uint8)
+            self.born, self.ids, self._next_id = image_ops.tracker_ids(self._lost, self._start)
+
     def push(self, frames):
         shape = tuple(frames.shape) if hasattr(frames, 'shape') else np.shape(frames)
         dtype = frames.dtype if hasattr(frames, 'dtype') else np.asarray(frames).dtype
-        if len(shape) != 4 or shape[-1] != 3 or 0 in shape or shape[0] != self._lead[0]:
+        if self._lead is None:
+            if len(shape) != 4 or shape[-1] != 3 or 0 in shape:
+                raise ValueError(f'frames must be (N, H, W, 3), one frame per video, got {shape}')
+        elif len(shape) != 4 or shape[-1] != 3 or 0 in shape or shape[0] != self._lead[0]:
             raise ValueError(f'frames must be (N, H, W, 3) with N = {self._lead[0]}, one frame per video of the points, got {shape}')
         signature = shape[:3] + (str(dtype).replace('torch.', ''),)
         if self._signature is not None and signature != self._signature:
             raise ValueError(f'this tracker holds frames (N, H, W, type) = {self._signature}, got {signature}: reset() it first')
-        if self._points is None:
+        seeding = self._K is not None
+        if seeding and self._signature is None:
+            self._mask_dev = _detect_mask(self._mask, shape[:3])
+        if self._points is None and self._given is not None:
             self._points = image_ops._on_device(self._given)
             self._start = image_ops._start_on_device(self._given_start, self._lead)
         forward = backward = None
-        if self.consistency:
+        if self.consistency or seeding:
             frames = image_ops._on_device(frames)
+        if self.consistency:
             if self._previous is not None:
                 res = self.model.predict_step_bidirectional((self._previous, frames), self.alpha, self.beta)
                 forward, backward = res.forward.as_subclass(torch.Tensor), res.backward.as_subclass(torch.Tensor)
@@ -206,14 +282,22 @@ class FlowTracker:
         else:
             flow = self._video.push(frames)
             forward = None if flow is None else flow.as_subclass(torch.Tensor)
+        first = self._signature is None
         self._signature = signature
         self._t += 1
+        if seeding and first:
+            self._seed(_detect_frames(frames))
         if forward is None:
             return None
         pos, lost = image_ops.track_launch(self._points if self._pos is None else self._pos, forward[None],
-                                           None if backward is None else backward[None], self._lost, self._start, self._t - 2,
-                                           self.alpha, self.beta)
+                                           None if backward is None else backward[None], self._lost,
+                                           self.born if self.replenish else self._start, self._t - 2, self.alpha, self.beta)
         self._pos, self._lost = pos[0], lost[0]
+        if self.replenish:
+            new, _, count, _ = image_ops.detect_points_launch(_detect_frames(frames), self._K, mask=self._mask_dev,
+                                                              avoid=(self._pos, self._lost), **self._detect)
+            image_ops.refill_points_launch(self._pos, self._lost, new, count, self._t - 1, self.born, self.ids, self._next_id,
+                                           out=(self._pos, self._lost))
         return _dev.wrap(self._pos), _dev.wrap(self._lost)
 
 
@@ -322,13 +406,20 @@ def stabilize_video(model, frames, motion_model='similarity', radius=15, iterati
 
 
 def track_video(model, frames, points, start=None, consistency=True, batch_size=4, alpha=image_ops.CONSISTENCY_ALPHA,
-                beta=image_ops.CONSISTENCY_BETA):
+                beta=image_ops.CONSISTENCY_BETA, max_points=None, replenish=False, detect=None):
     """``RAFT.track_video``: ``points`` ``(P, 2)`` float32, ``(x, y)`` in pixels, followed through ONE video ``(T, H, W, 3)``,
     host or device -> host arrays ``(positions (T, P, 2) float32, lost (T, P) uint8)``: row ``t`` says where every point is in
     frame ``t`` (row 0: the points themselves; a point with ``start[p] = k`` holds its given position in rows ``0 .. k``).
     ``batch_size`` consecutive pairs run per call (``predict_step_bidirectional``; with ``consistency=False`` a ``FlowVideo``
     call, every frame encoded once, only the frame borders tested) and ONE ``image_ops.track_launch`` chains the call's pairs,
-    positions and codes carried from call to call.  Host frames are uploaded one chunk ahead of the compute stream."""
+    positions and codes carried from call to call.  Host frames are uploaded one chunk ahead of the compute stream.
+
+    ``points=None`` with ``max_points=K``: frame 0 is run through ``image_ops.detect_points`` with the
+    options of ``detect=dict(...)`` (its ``mask`` is ``(1, H, W)``); ``P = K`` and the slots the detector could not fill hold the
+    code 3 and ``(-1, -1)`` in every row.  ``replenish=True`` also returns ``ids (T, P)`` int32, the identity of the point a slot
+    holds in every row (``FlowTracker``): lost slots are refilled from a detection on the LAST frame of every call, so a slot is
+    refilled only at a chunk boundary, every ``batch_size`` frames, and stays lost within a chunk -- one track launch still
+    chains a chunk."""
     from .prefetch import prefetch_to_device
     alpha, beta = image_ops.check_consistency_args(alpha, beta)
     shape = tuple(frames.shape) if hasattr(frames, 'shape') else np.shape(frames)
@@ -337,22 +428,35 @@ def track_video(model, frames, points, start=None, consistency=True, batch_size=
     T = shape[0]
     if T < 2:
         raise ValueError(f'a video needs at least two frames, got T = {T}')
-    (P,) = image_ops._points_ahead(points, None, start, 'track_video', lead=1)
+    lead = None if points is None else image_ops._points_ahead(points, None, start, 'track_video', lead=1)
+    K, options, mask = _check_seeding(points, start, max_points, replenish, detect, lead)
+    P = K if points is None else lead[0]
     if isinstance(batch_size, (bool, np.bool_)) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
         raise ValueError(f'batch_size must be an integer >= 1, got {batch_size!r}')
     bs = int(batch_size)
+    _check_detect_mask(mask, (1,) + shape[1:3])
     dev = _dev.require_gpu()
-    first = image_ops._on_device(points).reshape(1, P, 2)
+    mask = image_ops._mask_on_device(mask, (1,) + shape[1:3])
     begin = image_ops._start_on_device(start, (1, P))
     pos = torch.empty((T, 1, P, 2), device=dev, dtype=torch.float32)
     lost = torch.zeros((T, 1, P), device=dev, dtype=torch.uint8)
-    pos[0] = first
+    if points is not None:
+        pos[0] = image_ops._on_device(points).reshape(1, P, 2)
+    ids = ids_now = next_id = None
     video = None if consistency else FlowVideo(model, False)
     # a chunk holds the new frames of a call; the call's first frame is the one before them
     chunks = ((frames[a:b],) for a, b in [(0, 1)] + [(s, min(s + bs, T)) for s in range(1, T, bs)])
     previous, t = None, 0                        # the last frame of the chunk before, and its index
     for (chunk,) in prefetch_to_device(chunks, buffer_size=1, device=dev):
         k = chunk.shape[0]
+        if previous is None:                                                      # frame 0
+            if points is None:
+                image_ops.detect_points_launch(_detect_frames(chunk), K, mask=mask, want_lost=True, out=(pos[0], None, None, lost[0]),
+                                               **options)
+            if replenish:
+                begin, ids_now, next_id = image_ops.tracker_ids(lost[0], begin)
+                ids = torch.empty((T, 1, P), device=dev, dtype=torch.int32)
+                ids[0] = ids_now
         if video is not None:
             forward, backward = video._step(chunk, k), None
         elif previous is None:
@@ -368,6 +472,13 @@ def track_video(model, frames, points, start=None, consistency=True, batch_size=
         backward = None if backward is None else backward.as_subclass(torch.Tensor)[:, None]
         image_ops.track_launch(pos[t], forward, backward, lost[t], begin, t, alpha, beta, out=(pos[t + 1:t + 1 + k], lost[t + 1:t + 1 + k]))
         t += k
+        if replenish:
+            ids[t - k + 1:t] = ids_now                   # within the chunk nobody came in
+            new, _, count, _ = image_ops.detect_points_launch(_detect_frames(chunk[-1:]), K, mask=mask, avoid=(pos[t], lost[t]), **options)
+            image_ops.refill_points_launch(pos[t], lost[t], new, count, t, begin, ids_now, next_id, out=(pos[t], lost[t]))
+            ids[t] = ids_now
+    if replenish:
+        return pos[:, 0].cpu().numpy(), lost[:, 0].cpu().numpy(), ids[:, 0].cpu().numpy()
     return pos[:, 0].cpu().numpy(), lost[:, 0].cpu().numpy()
 
 
