@@ -558,6 +558,66 @@ int raft_refill_points(const float *pos_in, const uint8_t *lost_in, const float 
                        float *pos_out, uint8_t *lost_out, int32_t *born, int32_t *ids, int32_t *next_id, int N, int64_t P, int K,
                        void *stream);
 
+/* Connected components of a mask and their statistics (csrc/components.hip): which objects move, where they
+ * are, how large they are and how fast they go.  mask and exclude are uint8 (N, H, W); exclude may be NULL.
+ *     FOREGROUND   pixel (n, y, x) iff mask[n, y, x] != 0 and (exclude == NULL or exclude[n, y, x] == 0)
+ *     COMPONENTS   the classes of an image's foreground under `connectivity` 4 (W, E, N, S) or 8 (and the diagonals); nothing
+ *                  connects two images of a batch
+ *     ROOT INDEX   of a component: min(y * W + x) over its pixels
+ * Everything below is an integer -- a minimum of indices, integer sums, minima and maxima, taken with integer atomics -- up to ONE
+ * float64 division of two exact integers and one rounding to float32 per centroid and mean-flow component.  So every output is a
+ * function of the input alone, whatever order the merges and the atomics ran in, and repeats bit for bit.
+ *
+ * raft_label_components: labels (N, H, W) int32 = 0 for a background pixel, 1 + root index for a foreground pixel.
+ *     Three launches, no memset: a 32 x 16 tile labelled in LDS; the tiles' borders merged; every pixel sent to its root.
+ *
+ * raft_find_objects selects, per image, the components with area >= min_area (min_area >= 1) and orders them by
+ *     key      = (uint64)area << 32 | (0xFFFFFFFF - root index), LARGEST FIRST: larger objects first, of equal areas the one that
+ *                starts earlier in raster order (keys are unique within an image).
+ *     The first K = max_objects (1 .. RAFT_OBJECTS_MAX) of them fill the slots 0 .. K - 1:
+ *     count     (N) int32         the number of filled slots
+ *     area      (N, K) int32      pixels
+ *     boxes     (N, K, 4) int32   x0, y0, x1, y1, inclusive
+ *     centroid  (N, K, 2) float32 (float)((double)Sx / (double)area), likewise y, with Sx, Sy the exact integer sums of x and y
+ *     mean_flow (N, K, 2) float32 or NULL; written (and flow read) only when flow (float32 (N, H, W, 2)) and mean_flow are BOTH
+ *                                 non-NULL.  A pixel of the object contributes iff both components of its vector are finite and
+ *                                 at most 2^20 in magnitude: q = (int64)rintf(u * 256.f) (one float32 product, round to nearest
+ *                                 even) per component to an int64 sum S, and 1 to a counter cnt; the mean is (float)((double)S /
+ *                                 (256.0 * (double)cnt)), or 0 where cnt == 0.  The quantum of 1/256 px is the frame splat's; the
+ *                                 clamp keeps every sum below 2^63 (2^31 pixels * 2^28).
+ *     labels    (N, H, W) int32 or NULL: slot + 1 for the pixels of a selected component, 0 for background and for the pixels of
+ *                                 every other component.
+ *     An empty slot has area 0, box (0, 0, -1, -1), centroid (-1, -1) and mean flow 0.
+ *     One memset and seven launches: the three above (the third also counts areas, at the root's own pixel), the roots with area >=
+ *     min_area gathered as candidates through an atomic slot counter (one reservation per workgroup; their order differs from run
+ *     to run, they are a set, and the sorted top-K of a set is the same bits every run), one workgroup per image selects and
+ *     sorts, one pass over the pixels writes labels and accumulates boxes and sums into the K records, one thread per slot divides.
+ *
+ * raft_remove_small_components: out (N, H, W) uint8 = 1 where the pixel is foreground and its component has at least min_area
+ *     pixels, else 0.  out == mask IS allowed (the mask is read by the first launch only, out written by the last, which
+ *     reads neither); for the same reason out == exclude is safe too.  One memset and four launches.
+ *
+ * workspace: raft_components_workspace_bytes(N, H, W, connectivity, min_area) bytes (0: the sizes are refused), 8-byte aligned, need
+ * not be cleared: 12 bytes per pixel (parent, root, area), N counters, N * bound keys of 8 bytes and N * RAFT_OBJECTS_MAX * 8 records
+ * of 56 bytes, every part padded to 8 bytes.  bound is exact: an image holds at most ceil(H / 2) * ceil(W / 2) components under
+ * 8-connectivity (no two pixels of a 2 x 2 cell lie in different components), at most ceil(H W / 2) under 4-connectivity, and in
+ * either case at most floor(H W / min_area) of at least min_area pixels; bound is the smaller of the two that apply, so the
+ * candidate list cannot overflow.  raft_label_components uses the first 4 bytes per pixel only and takes the size of any min_area.
+ * No workgroup waits for another anywhere (no flag, no grid barrier, no cooperative launch); no entry synchronises or downloads.
+ * Errors, in this order: RAFT_E_NULL for a NULL mask, labels (raft_label_components), out, count, area, boxes, centroid or
+ * workspace; RAFT_E_SHAPE for a non-positive size, H * W > 2^31 - 2, N * H * W >= 2^31, a connectivity other than 4 or 8,
+ * min_area < 1, max_objects outside 1 .. RAFT_OBJECTS_MAX; RAFT_E_ALIGN for a workspace that is not 8-byte aligned or a float32 /
+ * int32 array that is not 4-byte aligned.  All checks precede the first launch. */
+#define RAFT_OBJECTS_MAX 1024
+int64_t raft_components_workspace_bytes(int N, int H, int W, int connectivity, int min_area);
+int raft_label_components(const uint8_t *mask, const uint8_t *exclude, int32_t *labels, int N, int H, int W, int connectivity,
+                          void *workspace, void *stream);
+int raft_find_objects(const uint8_t *mask, const uint8_t *exclude, const float *flow, int32_t *labels, int32_t *count, int32_t *area,
+                      int32_t *boxes, float *centroid, float *mean_flow, int N, int H, int W, int connectivity, int min_area,
+                      int max_objects, void *workspace, void *stream);
+int raft_remove_small_components(const uint8_t *mask, const uint8_t *exclude, uint8_t *out, int N, int H, int W, int connectivity,
+                                 int min_area, void *workspace, void *stream);
+
 /* ------------------------------------------------------------------ training augmentation */
 
 /* FlowAugmentor (reference tf_raft/datasets/augmentor.py:9-129, used at dataset.py:87-91) composed into one gather (the sparse

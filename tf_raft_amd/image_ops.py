@@ -62,6 +62,13 @@ survivors per image, strongest first, all on the device and bit for bit the same
 tf_raft_amd/csrc/point_detect.hip); ``refill_points_launch`` puts new points into the slots a tracker has lost
 (``raft_refill_points``).  ``tf_raft_amd.video.FlowTracker`` uses both: ``points=None`` and ``replenish=True``.
 
+``label_components`` / ``find_objects`` / ``remove_small_components`` turn a mask into a list: the connected
+components of a ``moving`` or an occlusion mask under 4- or 8-connectivity, labelled by their smallest raster index, and the
+``max_objects`` largest of at least ``min_area`` pixels with area, box, centroid and mean flow, largest first -- a union-find over
+tiles in which no workgroup waits for another, integer atomics throughout, so the result repeats bit for bit
+(``raft_label_components`` / ``raft_find_objects`` / ``raft_remove_small_components``, tf_raft_amd/csrc/components.hip);
+``RAFT.moving_objects_step`` is the list of what moves on its own above the model.
+
 ``forward_interpolate`` projects a low-resolution flow forward along itself: the start of the next pair's
 recurrence in a video stream (``raft_forward_interpolate_f32``, tf_raft_amd/csrc/flow_init.hip; ``tf_raft_amd.video``).
 
@@ -79,6 +86,7 @@ from __future__ import annotations
 
 import collections
 import ctypes
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -1560,6 +1568,194 @@ def tracker_ids(lost: torch.Tensor, start=None):
     ids = torch.arange(P, device=lost.device, dtype=torch.int32).expand(N, P)
     return (torch.where(empty, minus, born).contiguous(), torch.where(empty, minus, ids).contiguous(),
             torch.full((N,), P, device=lost.device, dtype=torch.int32))
+
+
+# ------------------------------------------------------------------------------------------ connected components
+OBJECTS_MAX = _ffi._CONSTANTS['RAFT_OBJECTS_MAX']
+OBJECTS_MIN_AREA, OBJECTS_CONNECTIVITY = 64, 8                        # choices, not tuned values
+OBJECTS_MAX_AREA = (1 << 31) - 2                                      # H * W of one image
+
+
+class Objects(NamedTuple):
+    """What ``find_objects`` returns: per image the up to ``K`` largest components, LARGEST FIRST -- ``labels`` ``(N, H, W)`` int32
+    (slot + 1, 0 elsewhere), ``count`` ``(N,)`` int32, ``area`` ``(N, K)`` int32, ``boxes`` ``(N, K, 4)`` int32 as inclusive
+    ``x0, y0, x1, y1``, ``centroid`` ``(N, K, 2)`` float32 as ``(x, y)`` and ``mean_flow`` ``(N, K, 2)`` float32.  Fields that
+    were not asked for are None."""
+    labels: object
+    count: object
+    area: object
+    boxes: object
+    centroid: object
+    mean_flow: object
+
+
+def check_objects_args(max_objects=1, min_area=OBJECTS_MIN_AREA, connectivity=OBJECTS_CONNECTIVITY):
+    """``(max_objects, min_area, connectivity)`` of a component search: integers (no bool) in 1 .. ``OBJECTS_MAX`` and 1 .. 2^31 - 2,
+    and 4 or 8."""
+    K = _int_in(max_objects, 'max_objects', 1, OBJECTS_MAX)
+    a = _int_in(min_area, 'min_area', 1, OBJECTS_MAX_AREA)
+    if isinstance(connectivity, (bool, np.bool_)) or not isinstance(connectivity, (int, np.integer)) or connectivity not in (4, 8):
+        raise ValueError(f'connectivity must be 4 or 8, got {connectivity!r}')
+    return K, a, int(connectivity)
+
+
+def _check_objects_sizes(N, H, W, what):
+    if H * W > OBJECTS_MAX_AREA or N * H * W >= 1 << 31:
+        raise ValueError(f'{what} takes fewer than 2^31 pixels in all, got {N} x {H} x {W}: too large')
+
+
+def components_workspace_bytes(N, H, W, connectivity=OBJECTS_CONNECTIVITY, min_area=1):
+    """``raft_components_workspace_bytes``: the bytes a component search on ``(N, H, W)`` masks needs (host arithmetic only)."""
+    nbytes = int(_ffi.load_library().raft_components_workspace_bytes(int(N), int(H), int(W), int(connectivity), int(min_area)))
+    if nbytes <= 0:
+        raise ValueError(f'a component search takes fewer than 2^31 pixels in all, connectivity 4 or 8 and min_area >= 1, got '
+                         f'{N} x {H} x {W}, connectivity = {connectivity}, min_area = {min_area}: too large')
+    return nbytes
+
+
+def _check_objects_masks(mask, exclude, what):
+    if not isinstance(mask, torch.Tensor) or mask.dim() != 3 or 0 in mask.shape:
+        raise ValueError(f'{what}: expected a contiguous uint8 mask (N, H, W), got '
+                         f'{tuple(mask.shape) if hasattr(mask, "shape") else type(mask)}')
+    N, H, W = mask.shape
+    _check_objects_sizes(N, H, W, what)
+    mask = _check_out(mask, (N, H, W), torch.uint8, mask.device)
+    if exclude is not None:
+        exclude = _check_out(exclude, (N, H, W), torch.uint8, mask.device)
+    return mask, exclude, N, H, W
+
+
+def _objects_workspace(workspace, dev, nbytes):
+    """The caller's workspace, checked, or the stream's grow-only one (inside ``torch.cuda.device(dev)``)."""
+    if workspace is None:
+        from . import losses
+        return losses._workspace(dev, nbytes)
+    if (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or workspace.numel() < nbytes
+            or workspace.device != dev or not workspace.is_contiguous() or workspace.data_ptr() % 8):
+        raise ValueError(f'workspace must be a contiguous uint8 tensor of at least {nbytes} bytes on {dev}, 8-byte aligned')
+    return workspace
+
+
+def label_components_launch(mask: torch.Tensor, exclude=None, connectivity: int = OBJECTS_CONNECTIVITY, out=None, workspace=None):
+    """The launches themselves (``raft_label_components``): a contiguous uint8 device ``mask`` ``(N, H, W)``
+    and an optional ``exclude`` of the same kind -> ``labels`` ``(N, H, W)`` int32 on the CURRENT stream (a plain tensor): 0 for
+    background, ``1 +`` the smallest raster index ``y * W + x`` of its component for a foreground pixel.  Three launches."""
+    _, _, conn = check_objects_args(1, 1, connectivity)
+    mask, exclude, N, H, W = _check_objects_masks(mask, exclude, 'label_components')
+    labels = _check_out(out, (N, H, W), torch.int32, mask.device)
+    nbytes = components_workspace_bytes(N, H, W, conn, 1)
+    with torch.cuda.device(mask.device):
+        ws = _objects_workspace(workspace, mask.device, nbytes)
+        check(_dev.lib().raft_label_components(_dev.ptr(mask), _dev.ptr(exclude) if exclude is not None else None, _dev.ptr(labels), N, H,
+                                               W, conn, _dev.ptr(ws), _dev.stream_ptr()), 'label_components')
+    return labels
+
+
+def find_objects_launch(mask: torch.Tensor, max_objects: int, min_area: int = OBJECTS_MIN_AREA, connectivity: int = OBJECTS_CONNECTIVITY,
+                        exclude=None, flow=None, want_labels: bool = True, workspace=None):
+    """The launches themselves (``raft_find_objects``): a contiguous uint8 device ``mask`` ``(N, H, W)``, an
+    optional ``exclude`` of the same kind and an optional contiguous float32 ``flow`` ``(N, H, W, 2)`` -> ``Objects`` of plain
+    tensors on the CURRENT stream (``labels`` None without ``want_labels``, ``mean_flow`` None without a flow).  One memset and
+    seven launches enqueued by one call, nothing synchronised."""
+    K, a, conn = check_objects_args(max_objects, min_area, connectivity)
+    mask, exclude, N, H, W = _check_objects_masks(mask, exclude, 'find_objects')
+    dev = mask.device
+    if flow is not None:
+        if not isinstance(flow, torch.Tensor) or tuple(flow.shape) != (N, H, W, 2) or flow.device != dev:
+            raise ValueError(f'find_objects: a mask {(N, H, W)} on {dev} needs a flow {(N, H, W, 2)}, got '
+                             f'{tuple(flow.shape) if hasattr(flow, "shape") else type(flow)}')
+        _check_flow(flow, 'find_objects')
+        flow = flow if type(flow) is torch.Tensor else flow.as_subclass(torch.Tensor)
+    labels = torch.empty((N, H, W), device=dev, dtype=torch.int32) if want_labels else None
+    count = torch.empty((N,), device=dev, dtype=torch.int32)
+    area = torch.empty((N, K), device=dev, dtype=torch.int32)
+    boxes = torch.empty((N, K, 4), device=dev, dtype=torch.int32)
+    centroid = torch.empty((N, K, 2), device=dev, dtype=torch.float32)
+    mean_flow = torch.empty((N, K, 2), device=dev, dtype=torch.float32) if flow is not None else None
+    nbytes = components_workspace_bytes(N, H, W, conn, a)
+    ptr = lambda t: None if t is None else _dev.ptr(t)       # noqa: E731
+    with torch.cuda.device(dev):
+        ws = _objects_workspace(workspace, dev, nbytes)
+        check(_dev.lib().raft_find_objects(_dev.ptr(mask), ptr(exclude), ptr(flow), ptr(labels), _dev.ptr(count), _dev.ptr(area),
+                                           _dev.ptr(boxes), _dev.ptr(centroid), ptr(mean_flow), N, H, W, conn, a, K, _dev.ptr(ws),
+                                           _dev.stream_ptr()), 'find_objects')
+    return Objects(labels, count, area, boxes, centroid, mean_flow)
+
+
+def remove_small_components_launch(mask: torch.Tensor, min_area: int, connectivity: int = OBJECTS_CONNECTIVITY, exclude=None, out=None,
+                                   workspace=None):
+    """The launches themselves (``raft_remove_small_components``): a contiguous uint8 device ``mask``
+    ``(N, H, W)`` and an optional ``exclude`` -> the uint8 mask ``(N, H, W)`` (a plain tensor) that is 1 where the pixel is
+    foreground and its component has at least ``min_area`` pixels.  ``out=mask`` cleans in place.  One memset and four launches on
+    the CURRENT stream."""
+    _, a, conn = check_objects_args(1, min_area, connectivity)
+    mask, exclude, N, H, W = _check_objects_masks(mask, exclude, 'remove_small_components')
+    out = _check_out(out, (N, H, W), torch.uint8, mask.device)
+    nbytes = components_workspace_bytes(N, H, W, conn, a)
+    with torch.cuda.device(mask.device):
+        ws = _objects_workspace(workspace, mask.device, nbytes)
+        check(_dev.lib().raft_remove_small_components(_dev.ptr(mask), _dev.ptr(exclude) if exclude is not None else None, _dev.ptr(out), N,
+                                                      H, W, conn, a, _dev.ptr(ws), _dev.stream_ptr()), 'remove_small_components')
+    return out
+
+
+def _objects_ahead(mask, exclude, what):
+    """Shape of a mask argument ``(..., H, W)`` with its leading axes folded, ``(shape, (N, H, W))``, checked ahead with ``exclude``."""
+    shape, dtype = _shape_and_type(mask, what)
+    if len(shape) < 2:
+        raise ValueError(f'{what} expects a mask (..., H, W), got {shape}')
+    if 0 in shape:
+        raise ValueError(f'empty input {shape}')
+    if dtype not in (torch.uint8, torch.bool):
+        raise TypeError(f'a mask is uint8 or bool, got {dtype}')
+    _mask_ahead(exclude, shape, what)
+    N, H, W = int(np.prod(shape[:-2], dtype=np.int64)), shape[-2], shape[-1]
+    _check_objects_sizes(N, H, W, what)
+    return shape, (N, H, W)
+
+
+def label_components(mask, exclude=None, connectivity=OBJECTS_CONNECTIVITY):
+    """Connected-component labelling (DESIGN.md section 30): a uint8 / bool mask ``(..., H, W)`` (NumPy or torch, host or device;
+    nonzero = foreground) -> int32 labels of the same shape on the device: 0 for background, and for a foreground pixel ``1 +`` the
+    smallest raster index ``y * W + x`` of its component -- a function of the mask alone.  ``exclude`` (same shape and kind):
+    pixels where it is nonzero are background, so a ``moving`` mask and an ``occluded_forward`` mask go in as they are.
+    ``connectivity`` 4 or 8; every ``(H, W)`` slice is labelled on its own."""
+    _, _, conn = check_objects_args(1, 1, connectivity)
+    shape, shape3 = _objects_ahead(mask, exclude, 'label_components')
+    labels = label_components_launch(_mask_on_device(mask, shape3), _mask_on_device(exclude, shape3), conn)
+    return _dev.wrap(labels.view(shape))
+
+
+def find_objects(mask, max_objects, min_area=OBJECTS_MIN_AREA, connectivity=OBJECTS_CONNECTIVITY, exclude=None, flow=None,
+                 return_labels=True):
+    """The objects of a mask: a uint8 / bool mask ``(..., H, W)`` (NumPy or torch, host or device) ->
+    ``Objects(labels, count, area, boxes, centroid, mean_flow)`` of device tensors with the mask's leading axes: per slice the up to
+    ``K = max_objects`` (1 .. 1024) connected components of at least ``min_area`` pixels, LARGEST FIRST (of equal areas the one
+    that starts earlier in raster order); the slots from ``count`` on hold area 0, box ``(0, 0, -1, -1)``, centroid ``(-1, -1)``
+    and mean flow 0.  ``boxes`` are inclusive ``x0, y0, x1, y1``, ``centroid`` is ``(x, y)``; ``labels`` (``return_labels``) holds
+    ``slot + 1`` on the pixels of a chosen component and 0 elsewhere.  With a float32 ``flow`` ``(..., H, W, 2)``, ``mean_flow`` is
+    the mean vector over the object's pixels, quantised to 1/256 pixel per vector (vectors that are not finite or longer than 2^20
+    per component are left out); without one it is None.  ``exclude``: as in ``label_components``.  ``min_area=64`` and
+    ``connectivity=8`` are choices, not tuned values.  Integer sums throughout: the result equals its NumPy restatement bit for bit
+    and repeats bit for bit."""
+    K, a, conn = check_objects_args(max_objects, min_area, connectivity)
+    shape, shape3 = _objects_ahead(mask, exclude, 'find_objects')
+    if flow is not None:
+        _flow_ahead(flow, shape, 'find_objects')
+    f = None if flow is None else _on_device(flow).reshape(shape3 + (2,))
+    res = find_objects_launch(_mask_on_device(mask, shape3), K, a, conn, _mask_on_device(exclude, shape3), f, bool(return_labels))
+    lead = shape[:-2]
+    return Objects(*(None if t is None else _dev.wrap(t.view(lead + tuple(t.shape[1:]))) for t in res))
+
+
+def remove_small_components(mask, min_area, connectivity=OBJECTS_CONNECTIVITY, exclude=None):
+    """A mask without its specks: a uint8 / bool mask ``(..., H, W)`` (NumPy or torch, host or device) -> the
+    uint8 device mask of the same shape that is 1 where the pixel is foreground and its connected component has at least
+    ``min_area`` pixels, else 0.  ``exclude`` and ``connectivity``: as in ``label_components``."""
+    _, a, conn = check_objects_args(1, min_area, connectivity)
+    shape, shape3 = _objects_ahead(mask, exclude, 'remove_small_components')
+    out = remove_small_components_launch(_mask_on_device(mask, shape3), a, conn, _mask_on_device(exclude, shape3))
+    return _dev.wrap(out.view(shape))
 
 
 # ------------------------------------------------------------------------------------------ temporal fusion (DESIGN.md section 28)

@@ -88,6 +88,25 @@ class CameraMotion(NamedTuple):
     occluded_forward: object
 
 
+class MovingObjects(NamedTuple):
+    """What ``moving_objects_step`` returns: ``CameraMotion``'s six fields, then the objects of ``moving`` outside
+    ``occluded_forward`` (``image_ops.Objects``): ``labels`` ``(N, H, W)`` int32 (slot + 1, 0 elsewhere), ``count`` ``(N,)`` int32,
+    ``area`` ``(N, K)`` int32, ``boxes`` ``(N, K, 4)`` int32 as inclusive ``x0, y0, x1, y1``, ``centroid`` ``(N, K, 2)`` float32 as
+    ``(x, y)`` and ``mean_flow`` ``(N, K, 2)`` float32, the object's mean motion relative to the camera in pixels per frame pair."""
+    motion: object
+    stats: object
+    residual: object
+    moving: object
+    forward: object
+    occluded_forward: object
+    labels: object
+    count: object
+    area: object
+    boxes: object
+    centroid: object
+    mean_flow: object
+
+
 def _hinted(hint):
     return _ffi.thread_concurrency(hint) if hint is not None else contextlib.nullcontext()
 
@@ -748,6 +767,25 @@ class RAFT:
         motion, stats = image_ops.fit_motion_launch(forward, occluded, True, model, iterations, scale)
         residual, moving = image_ops.residual_flow_launch(forward, motion, threshold)
         return CameraMotion(_dev.wrap(motion), _dev.wrap(stats), _dev.wrap(residual), _dev.wrap(moving), res.forward, res.occluded_forward)
+
+    def moving_objects_step(self, data, model='affine', threshold=1.0, max_objects=64, min_area=image_ops.OBJECTS_MIN_AREA,
+                            connectivity=image_ops.OBJECTS_CONNECTIVITY, occlusion_test='consistency',
+                            iterations=image_ops.MOTION_ITERATIONS, scale=image_ops.MOTION_SCALE, **occlusion):
+        """Which objects move on their own between ``data = (image1, image2)``: ``MovingObjects`` of device
+        tensors.  ONE ``camera_motion_step`` (``model``, ``threshold``, ``occlusion_test``, ``iterations``, ``scale``,
+        ``**occlusion``), then ``image_ops.find_objects_launch`` on its ``moving`` mask with the pixels of ``occluded_forward`` left
+        out and its ``residual`` as the flow: per pair the up to ``max_objects`` connected components (``connectivity`` 4 or 8) of
+        at least ``min_area`` pixels, largest first, with area, inclusive box, centroid and ``mean_flow``, the object's mean motion
+        relative to the camera in pixels per frame pair.  All coordinates are those of the frames the caller passed, whatever
+        ``target_size`` / ``fit`` is.  Nothing is synchronised or downloaded.  ``threshold``, ``max_objects`` and ``min_area`` are
+        choices, not tuned values: random weights and no footage say nothing about what is found."""
+        K, min_area, connectivity = image_ops.check_objects_args(max_objects, min_area, connectivity)
+        cam = self.camera_motion_step(data, model=model, occlusion_test=occlusion_test, iterations=iterations, scale=scale,
+                                      threshold=threshold, **occlusion)
+        plain = lambda t: t.as_subclass(torch.Tensor).contiguous()       # noqa: E731
+        objects = image_ops.find_objects_launch(plain(cam.moving), K, min_area, connectivity, plain(cam.occluded_forward),
+                                                plain(cam.residual), True)
+        return MovingObjects(*cam, *(_dev.wrap(t) for t in objects))
 
     def stabilize_video(self, frames, model='similarity', radius=15, iterations=image_ops.MOTION_ITERATIONS, scale=image_ops.MOTION_SCALE,
                         batch_size=4, occlusion_test='consistency', return_motion=False):
