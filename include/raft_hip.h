@@ -618,6 +618,63 @@ int raft_find_objects(const uint8_t *mask, const uint8_t *exclude, const float *
 int raft_remove_small_components(const uint8_t *mask, const uint8_t *exclude, uint8_t *out, int N, int H, int W, int connectivity,
                                  int min_area, void *workspace, void *stream);
 
+/* Object identity through a video (csrc/object_track.hip): which object of one frame pair is which object
+ * of the next.  Two consecutive raft_find_objects results deal their slots independently; these three entries carry the labels of
+ * the first along the flow into the frame of the second, count what lands on what, match the slots one to one and hand
+ * identities on.  Integer sums, integer maxima and one float64 comparison per pair: every output is a function of the input alone
+ * and repeats bit for bit.  K = the number of slots, 1 .. RAFT_TRACK_OBJECTS_MAX (128, a choice: the K x K table of one image is
+ * then 64 KiB).  There is no workspace, no entry synchronises or downloads, and no workgroup waits for another.
+ *
+ * raft_object_overlap: labels_prev, labels_next int32 (M, H, W) as raft_find_objects writes them (slot + 1, 0 = background; a
+ * value outside 0 .. K counts as background on either side and never indexes anything); flow float32 (M, H, W, 2) from the frame of
+ * labels_prev into the frame of labels_next.  Outputs overlap int32 (M, K, K) and landed int32 (M, K), both zeroed by the entry
+ * itself (memsets on `stream`).  Per pixel (m, y, x) with a = labels_prev - 1 in 0 .. K - 1 and (u, v) its vector:
+ *     skipped unless u and v are both finite;
+ *     fx = (float)x + u, fy = (float)y + v, ONE float32 addition each; qx = rintf(fx), qy = rintf(fy) (ties to even);
+ *     IN FRAME iff 0 <= qx <= W - 1 and 0 <= qy <= H - 1, compared before any conversion to an integer (the comparison is exact:
+ *     against the largest float32 that is <= W - 1, which for an integer-valued qx says the same; an infinite sum fails);
+ *     in frame: landed[m, a] += 1, and with b = labels_next[m, qy, qx] - 1 in 0 .. K - 1 also overlap[m, a, b] += 1.
+ * All sums are int32 and cannot overflow (M * H * W < 2^31).  One pass over the pixels in 32 x 16 tiles; a tile's counts are put
+ * together in LDS (a direct-mapped table of pairs, as raft_find_objects' statistics) before one integer atomic per pair the tile
+ * met goes to global memory.  No float atomic.
+ *
+ * raft_match_objects: overlap (M, K, K), landed (M, K) as above, area_next int32 (M, K) the areas of the next side's slots,
+ * min_overlap a float32 in (0, 1].  Per image:
+ *     a pair (a, b) is ADMISSIBLE iff overlap[a, b] >= 1 and (double)overlap[a, b] >= (double)min_overlap *
+ *         (double)min(landed[a], area_next[b]): one float64 product, one comparison;
+ *     key(a, b) = (uint64)overlap[a, b] << 32 | (uint32)(0xFFFF - a) << 16 | (0xFFFF - b): unique; of equal counts the smaller
+ *         previous slot wins, then the smaller next slot (smaller slots are larger objects);
+ *     THE MATCHING: walk the admissible pairs by key, largest first, and take a pair iff both its slots are still free.
+ *   match         (M, K) int32          for next slot b the previous slot it took, or -1
+ *   match_overlap (M, K) int32 or NULL  that pair's count, 0 where unmatched
+ *   origin        (M, K) int32 or NULL  the previous slot of the largest key in column b over ALL pairs with overlap >= 1, whatever
+ *                                       the threshold and whoever was matched; -1 for an all-zero column (after a split it names
+ *                                       the object that was divided)
+ * One launch, one workgroup per image.  The kernel does not sort: it repeats "every free a picks its best free admissible b, every
+ * free b its best free a, pairs that picked each other are matched" until a round matches nothing, at most K rounds, which gives
+ * the walk's matching because keys are unique and the largest remaining pair is always mutual.
+ *
+ * raft_chain_object_ids: identities through S consecutive steps of N videos in ONE launch, one workgroup per video.  match int32
+ * (S, N, K) (a value outside -1 .. K - 1 is treated as -1); count int32 (S, N), the filled slots of each step's objects (clamped to
+ * 0 .. K); ids_in, born_in int32 (N, K) the state before step 0; next_id int32 (N), updated in place once, at the end; ids, born
+ * int32 (S, N, K) the state after every step.  Step s reads the state of step s - 1 (ids_in / born_in for s == 0).  A filled slot
+ * b < count[s, n] with a = match[s, n, b] >= 0 gets the id and born of previous slot a; an unmatched filled slot gets ids =
+ * next_id[n] + r and born = t0 + s, r its rank among the unmatched filled slots of that step in ascending slot order
+ * (raft_refill_points' ordered scan), and next_id[n] grows by their number; an empty slot gets -1 / -1.  ids == ids_in and born ==
+ * born_in are allowed when S == 1 (every thread reads the previous state before any thread writes, behind a barrier).  The first
+ * objects of a video get 0 .. count - 1 from this entry too: match all -1 and next_id = 0.
+ *
+ * Errors, in this order, all before any launch: RAFT_E_NULL for a NULL pointer other than match_overlap and origin; RAFT_E_SHAPE
+ * for a non-positive size, K outside 1 .. RAFT_TRACK_OBJECTS_MAX, M * H * W >= 2^31, a min_overlap outside (0, 1] or NaN, a negative
+ * t0 (or t0 + S >= 2^31), S * N * K >= 2^31; RAFT_E_ALIGN for an array that is not 4-byte aligned. */
+#define RAFT_TRACK_OBJECTS_MAX 128
+int raft_object_overlap(const int32_t *labels_prev, const float *flow, const int32_t *labels_next, int32_t *overlap, int32_t *landed,
+                        int M, int H, int W, int K, void *stream);
+int raft_match_objects(const int32_t *overlap, const int32_t *landed, const int32_t *area_next, float min_overlap, int32_t *match,
+                       int32_t *match_overlap, int32_t *origin, int M, int K, void *stream);
+int raft_chain_object_ids(const int32_t *match, const int32_t *count, int t0, const int32_t *ids_in, const int32_t *born_in,
+                          int32_t *next_id, int32_t *ids, int32_t *born, int S, int N, int K, void *stream);
+
 /* ------------------------------------------------------------------ training augmentation */
 
 /* FlowAugmentor (reference tf_raft/datasets/augmentor.py:9-129, used at dataset.py:87-91) composed into one gather (the sparse

@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIBPATH = os.path.join(LIBDIR, 'libraft_hip.so')
 SOURCES = ['corr.hip', 'upsample.hip', 'conv.hip', 'update_block.hip', 'conv_halo_11.hip', 'conv_halo_33.hip', 'conv_halo_15.hip',
-           'conv_halo_51.hip', 'encoder.hip', 'ondemand.hip', 'host_util.hip', 'conv_wino.hip', 'conv_wino1d.hip', 'conv_wino4.hip', 'mask_upsample.hip', 'metrics.hip', 'backward.hip', 'image_ops.hip', 'augment.hip', 'flow_viz.hip', 'flow_check.hip', 'flow_track.hip', 'flow_motion.hip', 'flow_splat.hip', 'frame_splat.hip', 'frame_fuse.hip', 'point_detect.hip', 'components.hip', 'flow_init.hip', 'photometric_loss.hip', 'census_loss.hip', 'ssim_loss.hip', 'selfsup_loss.hip', 'student_view.hip', 'smooth2_loss.hip']
+           'conv_halo_51.hip', 'encoder.hip', 'ondemand.hip', 'host_util.hip', 'conv_wino.hip', 'conv_wino1d.hip', 'conv_wino4.hip', 'mask_upsample.hip', 'metrics.hip', 'backward.hip', 'image_ops.hip', 'augment.hip', 'flow_viz.hip', 'flow_check.hip', 'flow_track.hip', 'flow_motion.hip', 'flow_splat.hip', 'frame_splat.hip', 'frame_fuse.hip', 'point_detect.hip', 'components.hip', 'object_track.hip', 'flow_init.hip', 'photometric_loss.hip', 'census_loss.hip', 'ssim_loss.hip', 'selfsup_loss.hip', 'student_view.hip', 'smooth2_loss.hip']
 HEADERS = ['common.h', 'launch_plan.h', 'conv_mfma.h', 'conv_epilogue.h', 'conv_stage.h', 'conv_halo.h', 'conv_wino.h', 'conv_wino1d.h', 'conv_wino4.h', 'lookup_common.h', 'flow_sample.h', 'splat_geometry.h', 'loss_common.h', 'warped_gray.h', os.path.join('..', '..', 'include', 'raft_hip.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=on',
          '-Wall', '-Wno-unused-function']

@@ -69,6 +69,12 @@ tiles in which no workgroup waits for another, integer atomics throughout, so th
 (``raft_label_components`` / ``raft_find_objects`` / ``raft_remove_small_components``, tf_raft_amd/csrc/components.hip);
 ``RAFT.moving_objects_step`` is the list of what moves on its own above the model.
 
+``match_objects`` says which object of one such list is which object of the next: the labels of the first are
+carried along the flow to the nearest pixel of the next frame and counted against the labels there (``object_overlap_launch``),
+slots are matched one to one, most shared pixels first (``match_objects_launch``), and ``chain_object_ids_launch`` hands identities on
+through any number of steps in one launch -- integer sums and maxima only (``raft_object_overlap`` / ``raft_match_objects`` /
+``raft_chain_object_ids``, tf_raft_amd/csrc/object_track.hip); ``tf_raft_amd.video.ObjectTracker`` is the tracker above the model.
+
 ``forward_interpolate`` projects a low-resolution flow forward along itself: the start of the next pair's
 recurrence in a video stream (``raft_forward_interpolate_f32``, tf_raft_amd/csrc/flow_init.hip; ``tf_raft_amd.video``).
 
@@ -1756,6 +1762,166 @@ def remove_small_components(mask, min_area, connectivity=OBJECTS_CONNECTIVITY, e
     shape, shape3 = _objects_ahead(mask, exclude, 'remove_small_components')
     out = remove_small_components_launch(_mask_on_device(mask, shape3), a, conn, _mask_on_device(exclude, shape3))
     return _dev.wrap(out.view(shape))
+
+
+# ------------------------------------------------------------------------------------------ object identity
+OBJECT_TRACK_MAX = _ffi._CONSTANTS['RAFT_TRACK_OBJECTS_MAX']
+OBJECT_MIN_OVERLAP = 0.25                                             # a choice, not a tuned value
+
+
+class ObjectMatch(NamedTuple):
+    """What ``match_objects`` returns, per slot ``b`` of the NEXT side, ``(..., K)`` int32: ``match`` the previous slot it took
+    (-1: none), ``overlap`` the pixels of that previous object that landed on it (0 where unmatched), ``origin`` the previous slot
+    most of whose pixels landed on it whatever the threshold and whoever was matched (-1: nothing landed on it)."""
+    match: object
+    overlap: object
+    origin: object
+
+
+def check_object_track_args(max_objects=1, min_overlap=OBJECT_MIN_OVERLAP):
+    """``(max_objects, min_overlap)`` of an object matching: an integer (no bool) in 1 .. ``OBJECT_TRACK_MAX`` and a number whose
+    float32 value lies in (0, 1]."""
+    K = _int_in(max_objects, 'max_objects', 1, OBJECT_TRACK_MAX)
+    s = _float32_value(min_overlap, 'min_overlap')
+    if not 0.0 < s <= 1.0:
+        raise ValueError(f'min_overlap must lie in (0, 1] as a float32, got {min_overlap!r}')
+    return K, s
+
+
+def _int32_table(t, shape, device, what):
+    if (not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != torch.int32 or t.device != device
+            or not t.is_contiguous()):
+        raise ValueError(f'{what} must be a contiguous int32 tensor of shape {tuple(shape)} on {device}, got '
+                         f'{(tuple(t.shape), t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t)}')
+    return t if type(t) is torch.Tensor else t.as_subclass(torch.Tensor)
+
+
+def object_overlap_launch(labels_prev: torch.Tensor, flow: torch.Tensor, labels_next: torch.Tensor, K: int):
+    """The launch itself (``raft_object_overlap``): contiguous int32 device label maps ``(M, H, W)`` of two
+    consecutive ``find_objects`` results (slot + 1, 0 = background) and the contiguous float32 ``flow`` ``(M, H, W, 2)`` from the
+    frame of the first into the frame of the second -> ``(overlap (M, K, K), landed (M, K))`` int32 on the CURRENT stream:
+    ``landed[m, a]`` counts the pixels of previous slot ``a`` whose vector is finite and lands, rounded to the nearest pixel (ties
+    to even), inside the frame, ``overlap[m, a, b]`` those of them that land on next slot ``b``.  Two memsets and one launch."""
+    K, _ = check_object_track_args(K)
+    if not isinstance(labels_prev, torch.Tensor) or labels_prev.dim() != 3 or 0 in labels_prev.shape:
+        raise ValueError(f'object_overlap: expected int32 labels (M, H, W), got '
+                         f'{tuple(labels_prev.shape) if hasattr(labels_prev, "shape") else type(labels_prev)}')
+    M, H, W = labels_prev.shape
+    dev = labels_prev.device
+    _check_objects_sizes(M, H, W, 'object_overlap')
+    labels_prev = _int32_table(labels_prev, (M, H, W), dev, 'labels_prev')
+    labels_next = _int32_table(labels_next, (M, H, W), dev, 'labels_next')
+    if not isinstance(flow, torch.Tensor) or tuple(flow.shape) != (M, H, W, 2) or flow.device != dev:
+        raise ValueError(f'object_overlap: labels {(M, H, W)} on {dev} need a flow {(M, H, W, 2)}, got '
+                         f'{tuple(flow.shape) if hasattr(flow, "shape") else type(flow)}')
+    _check_flow(flow, 'object_overlap')
+    flow = flow if type(flow) is torch.Tensor else flow.as_subclass(torch.Tensor)
+    overlap = torch.empty((M, K, K), device=dev, dtype=torch.int32)
+    landed = torch.empty((M, K), device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        check(_dev.lib().raft_object_overlap(_dev.ptr(labels_prev), _dev.ptr(flow), _dev.ptr(labels_next), _dev.ptr(overlap),
+                                             _dev.ptr(landed), M, H, W, K, _dev.stream_ptr()), 'object_overlap')
+    return overlap, landed
+
+
+def match_objects_launch(overlap: torch.Tensor, landed: torch.Tensor, area_next: torch.Tensor, min_overlap: float = OBJECT_MIN_OVERLAP,
+                         want_overlap: bool = True, want_origin: bool = True):
+    """The launch itself (``raft_match_objects``): ``overlap`` ``(M, K, K)`` and ``landed`` ``(M, K)`` of
+    ``object_overlap_launch`` and the next side's ``area`` ``(M, K)``, contiguous int32 device tensors -> ``ObjectMatch`` of
+    ``(M, K)`` int32 tensors on the CURRENT stream.  A pair is admissible iff its count is at least ``min_overlap`` times the
+    smaller of ``landed[a]`` and ``area_next[b]`` (and at least 1); the admissible pairs are taken greedily, most pixels first (of
+    equal counts the smaller previous slot, then the smaller next slot), each slot once.  One launch, one workgroup per image."""
+    if not isinstance(overlap, torch.Tensor) or overlap.dim() != 3 or overlap.shape[1] != overlap.shape[2] or 0 in overlap.shape:
+        raise ValueError(f'match_objects: expected an int32 overlap table (M, K, K), got '
+                         f'{tuple(overlap.shape) if hasattr(overlap, "shape") else type(overlap)}')
+    M, K, _ = overlap.shape
+    K, share = check_object_track_args(K, min_overlap)
+    dev = overlap.device
+    overlap = _int32_table(overlap, (M, K, K), dev, 'overlap')
+    landed = _int32_table(landed, (M, K), dev, 'landed')
+    area_next = _int32_table(area_next, (M, K), dev, 'area_next')
+    match = torch.empty((M, K), device=dev, dtype=torch.int32)
+    count = torch.empty((M, K), device=dev, dtype=torch.int32) if want_overlap else None
+    origin = torch.empty((M, K), device=dev, dtype=torch.int32) if want_origin else None
+    ptr = lambda t: None if t is None else _dev.ptr(t)       # noqa: E731
+    with torch.cuda.device(dev):
+        check(_dev.lib().raft_match_objects(_dev.ptr(overlap), _dev.ptr(landed), _dev.ptr(area_next), share, _dev.ptr(match), ptr(count),
+                                            ptr(origin), M, K, _dev.stream_ptr()), 'match_objects')
+    return ObjectMatch(match, count, origin)
+
+
+def chain_object_ids_launch(match: torch.Tensor, count: torch.Tensor, t0: int, ids: torch.Tensor, born: torch.Tensor,
+                            next_id: torch.Tensor, out=None):
+    """The launch itself (``raft_chain_object_ids``): ``match`` ``(S, N, K)`` and ``count`` ``(S, N)`` of ``S``
+    consecutive steps of ``N`` videos, the state before them ``ids``, ``born`` ``(N, K)`` and ``next_id`` ``(N,)``, all contiguous
+    int32 device tensors, and the index ``t0`` of the first step -> ``(ids, born)`` ``(S, N, K)`` after every step (``out``: a pair
+    to write them into; with ``S == 1``, ``out=(ids[None], born[None])`` updates the state in place).  A matched slot inherits the
+    id and birth step of the previous slot it took; an unmatched filled slot takes the next id of its video, in ascending slot
+    order, and is born at ``t0 + s``; an empty slot holds -1 / -1.  ``next_id`` is updated in place.  One launch on the CURRENT
+    stream, one workgroup per video."""
+    t0 = check_track_time(t0)
+    if not isinstance(match, torch.Tensor) or match.dim() != 3 or 0 in match.shape:
+        raise ValueError(f'chain_object_ids: expected int32 matches (S, N, K), got '
+                         f'{tuple(match.shape) if hasattr(match, "shape") else type(match)}')
+    S, N, K = match.shape
+    check_object_track_args(K)
+    if S * N * K >= 1 << 31 or t0 + S >= 1 << 31:
+        raise ValueError(f'chain_object_ids takes fewer than 2^31 slots in all, got {S} x {N} x {K}: too large')
+    dev = match.device
+    match = _int32_table(match, (S, N, K), dev, 'match')
+    count = _int32_table(count, (S, N), dev, 'count')
+    ids = _int32_table(ids, (N, K), dev, 'ids')
+    born = _int32_table(born, (N, K), dev, 'born')
+    next_id = _int32_table(next_id, (N,), dev, 'next_id')
+    if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+        raise ValueError('out must be a pair (ids (S, N, K), born (S, N, K))')
+    ids_out = _check_out(None if out is None else out[0], (S, N, K), torch.int32, dev)
+    born_out = _check_out(None if out is None else out[1], (S, N, K), torch.int32, dev)
+    with torch.cuda.device(dev):
+        check(_dev.lib().raft_chain_object_ids(_dev.ptr(match), _dev.ptr(count), t0, _dev.ptr(ids), _dev.ptr(born), _dev.ptr(next_id),
+                                               _dev.ptr(ids_out), _dev.ptr(born_out), S, N, K, _dev.stream_ptr()), 'chain_object_ids')
+    return ids_out, born_out
+
+
+def _int32_ahead(x, what):
+    """Shape of an int32 argument (NumPy or torch), read without touching a device."""
+    if not isinstance(x, torch.Tensor):
+        x = x if isinstance(x, np.ndarray) else np.asarray(x)
+    if x.dtype not in (torch.int32, np.dtype(np.int32)):
+        raise TypeError(f'{what} is int32, got {x.dtype}')
+    return tuple(x.shape)
+
+
+def match_objects(prev, flow, next, min_overlap=OBJECT_MIN_OVERLAP):       # noqa: A002
+    """Which object of one frame pair is which object of the next: ``prev`` and ``next`` are the ``Objects``
+    of two consecutive ``find_objects`` calls (``prev`` needs ``labels`` ``(..., H, W)``, ``next`` ``labels`` and ``area`` ``(..., K)``,
+    all int32), NumPy or torch, host or device, and ``flow`` ``(..., H, W, 2)`` float32 leads from the frame of
+    ``prev.labels`` into the frame of ``next.labels`` -> ``ObjectMatch(match, overlap, origin)`` of ``(..., K)`` int32 device
+    tensors, ``K = next.area.shape[-1]`` (at most 128; labels above ``K`` count as background).  Every pixel of a previous object
+    is carried along its vector to the nearest pixel (vectors that are not finite or leave the frame drop out); a pair of slots is
+    admissible iff the pixels of ``a`` that landed on ``b`` are at least ``min_overlap`` times the smaller of ``a``'s landed pixels
+    and ``b``'s area; admissible pairs are taken greedily, most pixels first, each slot once.  ``min_overlap=0.25``, the nearest
+    pixel and the greedy one-to-one rule are choices, not tuned values.  Integer sums throughout: the result equals its NumPy
+    restatement bit for bit and repeats bit for bit."""
+    if getattr(prev, 'labels', None) is None or getattr(next, 'labels', None) is None or getattr(next, 'area', None) is None:
+        raise ValueError('match_objects needs prev.labels, next.labels and next.area: call find_objects with return_labels=True')
+    shape = _int32_ahead(prev.labels, 'prev.labels')
+    if len(shape) < 2 or 0 in shape:
+        raise ValueError(f'match_objects expects labels (..., H, W), got {shape}')
+    if _int32_ahead(next.labels, 'next.labels') != shape:
+        raise ValueError(f'match_objects expects next.labels {shape}, got {_int32_ahead(next.labels, "next.labels")}')
+    lead = shape[:-2]
+    area_shape = _int32_ahead(next.area, 'next.area')
+    if len(area_shape) != len(lead) + 1 or area_shape[:-1] != lead or area_shape[-1] < 1:
+        raise ValueError(f'match_objects expects next.area {lead + ("K",)}, got {area_shape}')
+    K, share = check_object_track_args(area_shape[-1], min_overlap)
+    _flow_ahead(flow, shape, 'match_objects')
+    M, H, W = int(np.prod(lead, dtype=np.int64)), shape[-2], shape[-1]
+    _check_objects_sizes(M, H, W, 'match_objects')
+    overlap, landed = object_overlap_launch(_on_device(prev.labels).reshape(M, H, W), _on_device(flow).reshape(M, H, W, 2),
+                                            _on_device(next.labels).reshape(M, H, W), K)
+    res = match_objects_launch(overlap, landed, _on_device(next.area).reshape(M, K), share)
+    return ObjectMatch(*(_dev.wrap(t.view(lead + (K,))) for t in res))
 
 
 # ------------------------------------------------------------------------------------------ temporal fusion (DESIGN.md section 28)

@@ -787,6 +787,25 @@ class RAFT:
                                                 plain(cam.residual), True)
         return MovingObjects(*cam, *(_dev.wrap(t) for t in objects))
 
+    def object_tracker(self, max_objects=64, min_overlap=image_ops.OBJECT_MIN_OVERLAP, **options):
+        """Moving objects with identities that last through a stream of frames (``tf_raft_amd.video.ObjectTracker``, DESIGN.md
+        section 31): ``push(frames)`` takes one frame ``(N, H, W, 3)`` of each of N videos, runs one ``moving_objects_step((previous,
+        frames), max_objects=max_objects, **options)`` and returns ``TrackedObjects`` -- ``MovingObjects``' fields, then ``ids``,
+        ``born``, ``match`` and ``origin`` ``(N, K)`` int32 -- for the objects of the PREVIOUS pushed frame (None after the first
+        push).  An object keeps its id while at least ``min_overlap`` of its pixels, carried along the flow, land on one object of
+        the next pair; ``max_objects`` is at most 128.  ``min_overlap`` is a choice, not a tuned value.  Serial schedule."""
+        from .video import ObjectTracker
+        return ObjectTracker(self, max_objects, min_overlap, **options)
+
+    def track_objects_video(self, frames, batch_size=4, max_objects=64, min_overlap=image_ops.OBJECT_MIN_OVERLAP, return_labels=False,
+                            **options):
+        """The moving objects of one video ``(T, H, W, 3)`` with identities that last, as host arrays over its ``T - 1`` pairs:
+        ``ObjectTracks(count, ids, born, area, boxes, centroid, mean_flow, labels)`` (``tf_raft_amd.video.track_objects_video``);
+        every pair predicted in a call of its own, ``batch_size`` pairs per upload and per identity launch, one download at the end,
+        the same result for every ``batch_size``."""
+        from .video import track_objects_video
+        return track_objects_video(self, frames, batch_size, max_objects, min_overlap, return_labels, **options)
+
     def stabilize_video(self, frames, model='similarity', radius=15, iterations=image_ops.MOTION_ITERATIONS, scale=image_ops.MOTION_SCALE,
                         batch_size=4, occlusion_test='consistency', return_motion=False):
         """One video ``(T, H, W, 3)`` steadied: the camera's motion fitted pair by pair on the device, its path smoothed on the host

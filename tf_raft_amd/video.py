@@ -21,8 +21,15 @@ correction (``image_ops.view_frames_launch``).  There is no streaming form: the 
 ``denoise_video`` filters footage along its motion: the bidirectional flows of consecutive frames are kept on
 the device, every frame's pixel grid is chained through its neighbours both ways in time (``image_ops.track_launch``), and one
 ``image_ops.fuse_frames_launch`` per frame averages the aligned neighbours robustly, read from the video where they lie.
+
+``ObjectTracker`` (``model.object_tracker()``) and ``track_objects_video`` keep the identity of moving objects through footage
+(DESIGN.md section 31): the labels of one ``moving_objects_step`` are carried along its forward flow and counted against the labels
+of the next (``image_ops.object_overlap_launch``), slots are matched one to one (``match_objects_launch``) and ids handed on
+(``chain_object_ids_launch``), a chunk of pairs per launch.
 """
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -556,3 +563,193 @@ def denoise_video(model, frames, radius=2, sigma=image_ops.FUSE_SIGMA, patch_rad
         image_ops.fuse_frames_launch(stack[t], stack, positions[:K].view(K, 1, H, W, 2), denoise_neighbours(t, T, radius),
                                      lost[:K].view(K, 1, H, W), True, sigma, patch_radius, center_weight, out=out[t:t + 1])
     return out.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------ object identity
+_OBJECT_STEP_OPTIONS = ('model', 'threshold', 'min_area', 'connectivity', 'occlusion_test', 'iterations', 'scale', 'alpha', 'beta',
+                        'range_threshold')
+
+
+class TrackedObjects(NamedTuple):
+    """What ``ObjectTracker.push`` returns: the twelve fields of ``MovingObjects`` for the pair (previous frames, pushed frames),
+    then per slot ``(N, K)`` int32: ``ids`` the identity of the object the slot holds (-1: empty), ``born`` the index of the pushed
+    frame its identity first appeared in, ``match`` the slot it held in the pair before (-1: a new object) and ``origin`` the slot
+    of the pair before most of whose pixels landed on it (-1: none; after a split, the object that was divided)."""
+    motion: object
+    stats: object
+    residual: object
+    moving: object
+    forward: object
+    occluded_forward: object
+    labels: object
+    count: object
+    area: object
+    boxes: object
+    centroid: object
+    mean_flow: object
+    ids: object
+    born: object
+    match: object
+    origin: object
+
+
+class ObjectTracks(NamedTuple):
+    """What ``track_objects_video`` returns, host arrays over the ``T - 1`` pairs of a video: ``count`` ``(T - 1,)``, ``ids``,
+    ``born``, ``area`` ``(T - 1, K)`` int32, ``boxes`` ``(T - 1, K, 4)`` int32, ``centroid`` and ``mean_flow`` ``(T - 1, K, 2)``
+    float32, and ``labels`` ``(T - 1, H, W)`` int32 (None without ``return_labels``).  Row ``t`` holds the objects of frame ``t``."""
+    count: object
+    ids: object
+    born: object
+    area: object
+    boxes: object
+    centroid: object
+    mean_flow: object
+    labels: object
+
+
+def check_object_tracker_args(max_objects=64, min_overlap=image_ops.OBJECT_MIN_OVERLAP, options=None):
+    """What ``ObjectTracker`` and ``track_objects_video`` ask of their arguments before anything reaches a device: ``(K,
+    min_overlap, options)`` with ``options`` the keyword arguments of ``RAFT.moving_objects_step`` other than ``max_objects``."""
+    K, share = image_ops.check_object_track_args(max_objects, min_overlap)
+    options = dict(options or {})
+    unknown = set(options) - set(_OBJECT_STEP_OPTIONS)
+    if unknown:
+        raise TypeError(f'unexpected keyword arguments {sorted(unknown)}: the options of moving_objects_step are {_OBJECT_STEP_OPTIONS}')
+    image_ops.check_objects_args(K, options.get('min_area', image_ops.OBJECTS_MIN_AREA),
+                                 options.get('connectivity', image_ops.OBJECTS_CONNECTIVITY))
+    image_ops.check_motion_args(options.get('model', 'affine'), options.get('iterations', image_ops.MOTION_ITERATIONS),
+                                options.get('scale', image_ops.MOTION_SCALE))
+    if image_ops.check_motion_threshold(options.get('threshold', 1.0)) is None:
+        raise ValueError('threshold must be a number, got None')
+    image_ops.check_occlusion_test(options.get('occlusion_test', 'consistency'))
+    return K, share, options
+
+
+def _plain(t):
+    return t.as_subclass(torch.Tensor).contiguous()
+
+
+class ObjectTracker:
+    """``model.object_tracker(max_objects=64, min_overlap=0.25, **moving_objects_step options)``: the moving objects of a stream
+    of frames with identities that last.  ``push(frames)`` takes one frame ``(N, H, W, 3)`` of each of N
+    independent videos (uint8 or float32, host or device), keeps the previous frames as ``FlowTracker(consistency=True)`` does and
+    runs ONE ``moving_objects_step((previous, frames))`` per push.  It returns None after the first push, then ``TrackedObjects``:
+    the fields of ``MovingObjects``, then ``ids``, ``born``, ``match`` and ``origin`` ``(N, K)`` int32, all device tensors, nothing
+    synchronised.  As with ``moving_objects_step`` the objects are those of the PREVIOUS pushed frame, in its coordinates: the
+    pair's flow says what moves in its first frame.
+
+    The second push numbers its objects ``0 .. count - 1``.  From the third push on the labels and the forward flow kept from the
+    pair before are matched against the new labels (``image_ops.object_overlap_launch`` / ``match_objects_launch``): a matched
+    object keeps its id and ``born``, an unmatched one takes the next id of its video (``image_ops.chain_object_ids_launch``);
+    ids never repeat within a video.  There is no memory beyond one pair: an object that is missed in one pair comes back under a
+    new id.  ``reset()`` forgets the stream; a change of shape or type without it raises.  ``min_overlap``, the nearest-pixel
+    landing and the greedy one-to-one rule are choices, not tuned values."""
+
+    def __init__(self, predictor, max_objects=64, min_overlap=image_ops.OBJECT_MIN_OVERLAP, **options):       # (`model` is an option)
+        self.max_objects, self.min_overlap, self._options = check_object_tracker_args(max_objects, min_overlap, options)
+        self.model = predictor
+        self.reset()
+
+    def reset(self):
+        self._signature = None
+        self._previous = None                    # the last frames, as they came
+        self._labels = self._forward = None      # of the pair before: labels in its first frame, the flow into its second
+        self.ids = self.born = self._next_id = None
+        self._t = 0                              # frames pushed so far
+
+    def push(self, frames):
+        shape = tuple(frames.shape) if hasattr(frames, 'shape') else np.shape(frames)
+        dtype = frames.dtype if hasattr(frames, 'dtype') else np.asarray(frames).dtype
+        if len(shape) != 4 or shape[-1] != 3 or 0 in shape:
+            raise ValueError(f'frames must be (N, H, W, 3), one frame per video, got {shape}')
+        signature = shape[:3] + (str(dtype).replace('torch.', ''),)
+        if self._signature is not None and signature != self._signature:
+            raise ValueError(f'this tracker holds frames (N, H, W, type) = {self._signature}, got {signature}: reset() it first')
+        frames = image_ops._on_device(frames)
+        previous, self._previous = self._previous, frames
+        self._signature = signature
+        self._t += 1
+        if previous is None:
+            return None
+        K, N, dev = self.max_objects, shape[0], frames.device
+        res = self.model.moving_objects_step((previous, frames), max_objects=K, **self._options)
+        labels, count, area, forward = _plain(res.labels), _plain(res.count), _plain(res.area), _plain(res.forward)
+        if self._labels is None:                 # the first pair: everybody is new
+            match = torch.full((N, K), -1, device=dev, dtype=torch.int32)
+            origin = match.clone()
+            self.ids, self.born = match.clone(), match.clone()
+            self._next_id = torch.zeros((N,), device=dev, dtype=torch.int32)
+        else:
+            overlap, landed = image_ops.object_overlap_launch(self._labels, self._forward, labels, K)
+            match, _, origin = image_ops.match_objects_launch(overlap, landed, area, self.min_overlap, want_overlap=False)
+        ids, born = image_ops.chain_object_ids_launch(match[None], count[None], self._t - 2, self.ids, self.born, self._next_id)
+        self.ids, self.born = ids[0], born[0]    # (new tensors every push: what an earlier push returned stays as it was)
+        self._labels, self._forward = labels, forward
+        return TrackedObjects(*res, _dev.wrap(self.ids), _dev.wrap(self.born), _dev.wrap(match), _dev.wrap(origin))
+
+
+def track_objects_video(predictor, frames, batch_size=4, max_objects=64, min_overlap=image_ops.OBJECT_MIN_OVERLAP, return_labels=False,
+                        **options):
+    """``RAFT.track_objects_video``: the moving objects of ONE video ``(T, H, W, 3)``, host or device, with identities that last
+    -> ``ObjectTracks`` of host arrays over its ``T - 1`` pairs (row ``t``: the objects of frame ``t``, from the pair ``t, t + 1``).
+    Every pair goes through a ``moving_objects_step`` call OF ITS OWN (its options go in as keywords): the predictor's launch plans
+    choose kernel shapes by batch, so the flow of a pair differs in its last bits with the batch it runs in, and a result that
+    must not depend on how the video is cut cannot batch the predictor.  ``batch_size`` is the number of
+    consecutive pairs per CHUNK: a chunk's frames are uploaded together, one chunk ahead of the compute stream, and its overlaps
+    come from ONE ``image_ops.object_overlap_launch`` -- pair i against pair i + 1 as batch slices, in front of them the pair
+    kept from the chunk before -- then one ``match_objects_launch`` and one ``chain_object_ids_launch`` over the chunk's steps.
+    Everything is downloaded once, at the end.  The result does not depend on ``batch_size`` and equals an ``ObjectTracker`` fed
+    the frames one by one.  Ids are ``ObjectTracker``'s: 0, 1, ... in order of appearance, never reused."""
+    from .prefetch import prefetch_to_device
+    K, share, options = check_object_tracker_args(max_objects, min_overlap, options)
+    shape, _ = image_ops._frames_ahead(frames, 'track_objects_video')
+    if len(shape) != 4 or shape[-1] != 3:
+        raise ValueError(f'frames must be one video (T, H, W, 3), got {shape}')
+    T, H, W, _ = shape
+    if T < 2:
+        raise ValueError(f'a video needs at least two frames, got T = {T}')
+    if isinstance(batch_size, (bool, np.bool_)) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
+        raise ValueError(f'batch_size must be an integer >= 1, got {batch_size!r}')
+    bs, P = int(batch_size), T - 1
+    dev = _dev.require_gpu()
+    i32 = dict(device=dev, dtype=torch.int32)
+    count = torch.empty((P, 1), **i32)
+    ids, born = torch.empty((P, 1, K), **i32), torch.empty((P, 1, K), **i32)
+    area, boxes = torch.empty((P, K), **i32), torch.empty((P, K, 4), **i32)
+    centroid = torch.empty((P, K, 2), device=dev, dtype=torch.float32)
+    mean_flow = torch.empty((P, K, 2), device=dev, dtype=torch.float32)
+    all_labels = torch.empty((P, H, W), **i32) if return_labels else None
+    # slice 0: the last pair of the chunk before; slices 1 .. k: this chunk's pairs
+    labels = torch.empty((bs + 1, H, W), **i32)
+    flows = torch.empty((bs + 1, H, W, 2), device=dev, dtype=torch.float32)
+    state = (torch.full((1, K), -1, **i32), torch.full((1, K), -1, **i32))
+    next_id = torch.zeros((1,), **i32)
+    chunks = ((frames[a:b],) for a, b in [(0, 1)] + [(s, min(s + bs, T)) for s in range(1, T, bs)])
+    previous, p = None, 0                        # the last frame of the chunk before; pairs done so far
+    for (chunk,) in prefetch_to_device(chunks, buffer_size=1, device=dev):
+        chunk = image_ops._on_device(chunk)
+        if previous is None:
+            previous = chunk[-1:]
+            continue
+        k = chunk.shape[0]
+        both = torch.cat([previous, chunk], dim=0)
+        previous = chunk[-1:]
+        for i in range(k):                       # one pair per call: what a pair gives must not depend on its neighbours
+            res = predictor.moving_objects_step((both[i:i + 1], both[i + 1:i + 2]), max_objects=K, **options)
+            labels[1 + i], flows[1 + i] = _plain(res.labels)[0], _plain(res.forward)[0]
+            count[p + i, 0], area[p + i], boxes[p + i] = _plain(res.count)[0], _plain(res.area)[0], _plain(res.boxes)[0]
+            centroid[p + i], mean_flow[p + i] = _plain(res.centroid)[0], _plain(res.mean_flow)[0]
+        if return_labels:
+            all_labels[p:p + k] = labels[1:k + 1]
+        first = 1 if p == 0 else 0               # the video's first pair has nothing in front of it
+        match = torch.full((k, 1, K), -1, **i32)
+        if k - first > 0:
+            overlap, landed = image_ops.object_overlap_launch(labels[first:k], flows[first:k], labels[first + 1:k + 1], K)
+            match[first:, 0] = image_ops.match_objects_launch(overlap, landed, area[p + first:p + k], share, False, False).match
+        image_ops.chain_object_ids_launch(match, count[p:p + k], p, state[0], state[1], next_id, out=(ids[p:p + k], born[p:p + k]))
+        state = (ids[p + k - 1], born[p + k - 1])
+        labels[0], flows[0] = labels[k], flows[k]
+        p += k
+    host = lambda t: t.cpu().numpy()             # noqa: E731
+    return ObjectTracks(host(count[:, 0]), host(ids[:, 0]), host(born[:, 0]), host(area), host(boxes), host(centroid), host(mean_flow),
+                        host(all_labels) if return_labels else None)
